@@ -7,7 +7,8 @@ and GPU (BASELINE.json configs[2]; weak scaling over GPUs = configs[3]).
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0.  ``roofline`` describes the dominant kernel (the bf16 MFMA implicit-GEMM that runs
+Prints ONE JSON line on rank 0; ``--dump-outputs DIR`` also writes what the last timed step computed as .npy files (see
+--help).  ``roofline`` describes the dominant kernel (the bf16 MFMA implicit-GEMM that runs
 the head 3x3 convolutions, their dgrads and every 1x1): algorithmic FLOPs per launch / average launch duration,
 both measured with HIP events on the launch stream during the timed steps.  ``cpu_baseline`` is the oracle
 (oracle/torch_oracle.py, a CPU restatement of the reference pinned to the reference's outputs) timed on the host.
@@ -24,6 +25,38 @@ if ROOT not in sys.path:
 
 MFMA_BF16_DENSE_PEAK_TFLOPS = 2500.0  # /opt/skills/guides/MI355X_MICROARCH.md, chip-level parameters
 HBM_PEAK_GBS = 8000.0                  # same guide: HBM3E peak (about 6.3 TB/s achievable)
+DUMP_BUDGET_BYTES = 64 << 20           # --dump-outputs: all files together
+DUMP_PARAM_SAMPLE = 1 << 22            # --dump-outputs, config 3: parameters sampled (params.npy and param_update.npy)
+DUMP_SEED = 20251015
+
+
+def dump_positions(n, k):
+    """k distinct positions of range(n) in ascending order, drawn with DUMP_SEED: the same sample for the same n on every
+    run and every build (None: k >= n, keep everything)."""
+    import numpy as np
+    if k >= n:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+
+
+def write_dump(dump_dir, arrays):
+    """--dump-outputs: arrays = [(name, tensor or ndarray)] -> dump_dir/<name>.npy, float64 kept, everything else as
+    float32.  The files stay within DUMP_BUDGET_BYTES: smallest first, an array larger than an equal share of what is left
+    is replaced by a seeded sample of its flattened elements (dump_positions)."""
+    import numpy as np
+    import torch
+    as_np = lambda a: (a.detach().cpu().to(torch.float64 if a.dtype == torch.float64 else torch.float32).numpy()
+                       if isinstance(a, torch.Tensor) else np.asarray(a))
+    arrays = [(n, as_np(a)) for n, a in arrays]
+    arrays = [(n, a if a.dtype == np.float64 else a.astype(np.float32)) for n, a in arrays]
+    budget = DUMP_BUDGET_BYTES - 1024 * len(arrays)  # room for the .npy headers
+    os.makedirs(dump_dir, exist_ok=True)
+    for i, (name, a) in enumerate(sorted(arrays, key=lambda na: na[1].nbytes)):
+        share = budget // (len(arrays) - i)
+        if a.nbytes > share:
+            a = a.reshape(-1)[dump_positions(a.size, share // a.itemsize)]
+        budget -= a.nbytes
+        np.save(os.path.join(dump_dir, name + '.npy'), a)
 
 
 def synthetic_batches(batch, hw, device, seed):
@@ -241,6 +274,11 @@ def run_forward_config(args, world, rank, device, dist):
         sync()
         elapsed = time.perf_counter() - t0
         out = [o.clone() for o in out]
+        if args.dump_outputs and rank == 0:
+            names = (['feature_%d' % i for i in range(len(out))] if args.config == 2 else
+                     ['rough_char_mask', 'rough_char_height', 'precise_char_prob', 'precise_char_up_left_corner_offset',
+                      'precise_char_corner_angle_distribution', 'precise_char_corner_distance'])
+            write_dump(args.dump_outputs, list(zip(names, out)))
         # per-kernel durations (the roofline object): HIP events cannot be recorded inside a graph replay, so the same steps run
         # once more eagerly with the launch timer, outside the timed region
         ops.TIMER = ops.LaunchTimer()
@@ -338,7 +376,15 @@ def main():
     ap.add_argument('--schedule', choices=('merged', 'two-pass'), default='merged',
                     help='merged: one backbone pass over the rough + precise batches and one backward of the summed loss '
                          '(same gradients); two-pass: the reference order, rough fwd/bwd then precise fwd/bwd')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32 or '
+                         'float64, at most 64 MB in all; larger outputs as a fixed, seeded sample of their elements).  '
+                         'Config 3: rough_loss, precise_loss, params (the updated parameters) and param_update (what the '
+                         'last step changed); config 2: the four backbone features; config 5: the post-processed maps '
+                         'of the last page.  The inputs depend on the arguments only, so two builds can be compared')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     import torch
     import torch.distributed as dist
@@ -397,6 +443,20 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    # --dump-outputs: what a caller of the step receives - the two losses and the updated parameters.  The parameters are
+    # sampled (dump_positions over the parameter elements in registration order, padding of the flat buffer skipped); the
+    # sample is also read just before the last timed step, so that param_update.npy is what that step changed.
+    dump_idx = params_before = None
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        starts = np.array([flat.offsets[n][0] for n in flat.names], dtype=np.int64)
+        sizes = np.array([flat.offsets[n][1] for n in flat.names], dtype=np.int64)
+        ends = np.cumsum(sizes)
+        pos = dump_positions(int(ends[-1]), DUMP_PARAM_SAMPLE)
+        pos = np.arange(int(ends[-1])) if pos is None else pos
+        j = np.searchsorted(ends, pos, side='right')
+        dump_idx = torch.from_numpy(starts[j] + pos - (ends[j] - sizes[j])).to(device)
+
     it = 0
     for _ in range(args.warmup):
         step(rough, precise, lr=cosine_warm_restarts_lr(it / 1000.0, 8e-4, 8e-6, 10, 10))
@@ -405,13 +465,20 @@ def main():
     ops.TIMER = ops.LaunchTimer()
     coll0 = reducer.collectives_issued if reducer is not None else 0
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if dump_idx is not None and i == args.steps - 1:
+            params_before = flat.flat_param.index_select(0, dump_idx)  # same stream as the step: ordered, no sync
         losses = step(rough, precise, lr=cosine_warm_restarts_lr(it / 1000.0, 8e-4, 8e-6, 10, 10))
         it += 1
     enqueue = time.perf_counter() - t0  # host time to enqueue the timed steps (no sync inside a step)
     sync()
     elapsed = time.perf_counter() - t0
     timer, ops.TIMER = ops.TIMER, None
+    if dump_idx is not None:  # before the side measurements below, which run further optimizer steps
+        params_after = flat.flat_param.index_select(0, dump_idx).double().cpu()
+        write_dump(args.dump_outputs, [('rough_loss', losses[0].double()), ('precise_loss', losses[1].double()),
+                                       ('params', params_after.float()),
+                                       ('param_update', (params_after - params_before.double().cpu()).float())])
     coll_per_step = ((reducer.collectives_issued - coll0) / args.steps) if reducer is not None else 0
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
