@@ -154,6 +154,31 @@ int vkas_conv_gemm_wgrad_ordered(const void* x, const vkas_conv_geom* g, const v
 int vkas_conv_gemm_wgrad_gelu(const void* x, const vkas_conv_geom* g, const void* dy, long lddy, int Np, float* gw,
                               float* gb, int dtype, void* stream);
 
+/* ---- nearest x f upsample followed by a 5x5 / pad 2 convolution, f in {3, 4} (FpnHead smoothing, fpn.py:41-48,170-174) -----
+ * Never materialises the upsample: each output phase (r, s) = pixels (f i + r, f j + s) is a 2 x 2 (f = 4) or up to 3 x 3
+ * (f = 3) convolution over the low-res input with folded taps (sums of the 5x5 taps).  16-bit storage only.
+ * g: B, Hin, Win = the low-res input, Hout = f Hin, Wout = f Win, Cp, ldx, KH = KW = 5, stride 1, pad 2.
+ * fold: w (N, C, 5, 5) fp32 -> `dtype` image of vkas_upconv5_fold_elems(Np, Cp, f, transposed) elements, sums in fp32.
+ * transposed = 0: the forward operand, per phase (Np, Gmax * Cp) rows in the (tap, Cp) layout of the implicit GEMMs;
+ * transposed = 1: the input-gradient operand (Cp, G * Np), one column block per (phase, tap). */
+size_t vkas_upconv5_fold_elems(int Np, int Cp, int f, int transposed);
+int vkas_upconv5_fold(const float* w, void* out, int N, int C, int Np, int Cp, int f, int transposed, int dtype, void* stream);
+/* out (B, Hout, Wout, Np) pixel stride ldo = conv5x5(nearest_up(x)) + bias (Np fp32, or NULL) */
+int vkas_upconv5_fwd(const void* x, const vkas_conv_geom* g, int f, const void* Bf, int Np, const float* bias, void* out,
+                     long ldo, int dtype, void* stream);
+/* dx (B, Hin, Win, Cp) pixel stride lddx = the input gradient for dy (B, Hout, Wout, Np) pixel stride lddy; every phase
+ * is summed in registers (no atomics: deterministic) */
+int vkas_upconv5_dgrad(const void* dy, long lddy, const vkas_conv_geom* g, int f, const void* Bt, int Np, void* dx, long lddx,
+                       int dtype, void* stream);
+/* per-phase folded weight gradient gwf (f*f blocks of Np * Gmax * Cp fp32, zero-filled by the caller) and the bias
+ * gradient gb (Np fp32, zero-filled, or NULL); both are added with fp32 atomics.  ws: vkas_upconv5_wgrad_ws_bytes bytes
+ * (the dy of one phase, compacted). */
+size_t vkas_upconv5_wgrad_ws_bytes(int B, int H, int W, int Np);
+int vkas_upconv5_wgrad(const void* x, const vkas_conv_geom* g, int f, const void* dy, long lddy, int Np, void* ws,
+                       size_t ws_bytes, float* gwf, float* gb, int dtype, void* stream);
+/* dw (N, C, 5, 5) fp32 (+)= the phases of gwf summed back onto the 5x5 taps */
+int vkas_upconv5_unfold_wgrad(const float* gwf, float* dw, int N, int C, int Np, int Cp, int f, int accumulate, void* stream);
+
 /* ---- fused ConvNeXt MLP (convnext.py:33-35,54-58), C % 8 == 0, C <= 512, 16-bit storage --------------------------------------
  * Linear(C,4C) -> GELU -> Linear(4C,C) -> layer scale -> stochastic depth -> residual as one kernel per direction; the
  * (M, 4C) activation is written once (h, for backward) and never read back between the two matrix products.

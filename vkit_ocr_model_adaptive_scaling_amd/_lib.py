@@ -86,6 +86,13 @@ _SIGS = {
     'vkas_conv_gemm_wgrad': (c_int, [_P, POINTER(ConvGeom), _P, c_long, c_int, _P, _P, c_int, _P]),
     'vkas_conv_gemm_wgrad_ordered': (c_int, [_P, POINTER(ConvGeom), _P, c_long, c_int, _P, c_int, _P]),
     'vkas_conv_gemm_wgrad_gelu': (c_int, [_P, POINTER(ConvGeom), _P, c_long, c_int, _P, _P, c_int, _P]),
+    'vkas_upconv5_fold_elems': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'vkas_upconv5_fold': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    'vkas_upconv5_fwd': (c_int, [_P, POINTER(ConvGeom), c_int, _P, c_int, _P, _P, c_long, c_int, _P]),
+    'vkas_upconv5_dgrad': (c_int, [_P, c_long, POINTER(ConvGeom), c_int, _P, c_int, _P, c_long, c_int, _P]),
+    'vkas_upconv5_wgrad_ws_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'vkas_upconv5_wgrad': (c_int, [_P, POINTER(ConvGeom), c_int, _P, c_long, c_int, _P, c_size_t, _P, _P, c_int, _P]),
+    'vkas_upconv5_unfold_wgrad': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     'vkas_mlp_chain_image_elems': (c_size_t, [c_int]),
     'vkas_mlp_chain_pack': (c_int, [_P, _P, _P, c_int, c_int, _P, c_int, _P]),
     'vkas_mlp_chain_fwd': (c_int, [_P, c_long, _P, _P, _P, c_long, _P, _P, c_int, _P, c_long, _P, c_long, _P, c_long,

@@ -123,9 +123,12 @@ class AdaptiveScaling(nn.Module):
         run their 3x3 convolutions as ONE implicit GEMM (output channels of the heads side by side, each padded to a
         multiple of 8), then per-head LayerNorm+GELU on channel slices, projection, NCHW, Softplus."""
         plain = [h[0] if isinstance(h, nn.Sequential) else h for h in heads]
-        up = plain[0].upsample_act(neck_feature)
         convs, norms, projs = zip(*[h.conv_norm_proj() for h in plain])
-        if ops.HeadsFused.eligible(up, [c.out_channels for c in convs], [hp.out_channels for hp in plain]):
+        conv5x5 = getattr(plain[0], 'conv5x5', False)
+        # FPN heads at factors 3 / 4: their 5x5 convolutions read the neck feature itself (ops.upconv5, folded phases) and
+        # the label-point forward falls back to dense maps
+        up = neck_feature if conv5x5 else plain[0].upsample_act(neck_feature)
+        if not conv5x5 and ops.HeadsFused.eligible(up, [c.out_channels for c in convs], [hp.out_channels for hp in plain]):
             # LayerNorm + GELU + projection run in the conv's epilogue: the per-head activations never reach HBM; the
             # heads' weights are packed side by side by the pack kernel (no torch.cat of parameters on the hot path)
             fused = []
@@ -150,7 +153,10 @@ class AdaptiveScaling(nn.Module):
             w_parts.append(F.pad(c.weight, (0, 0, 0, 0, 0, 0, 0, pad)) if pad else c.weight)
             b_parts.append(F.pad(c.bias, (0, pad)) if pad else c.bias)
         w_cat, b_cat = torch.cat(w_parts, 0), torch.cat(b_parts, 0)
-        z = ops.Conv.apply(up, w_cat, b_cat, 1, 1)
+        if conv5x5:
+            z = ops.upconv5(up, w_cat, b_cat, plain[0].upsampling_factor)
+        else:
+            z = ops.Conv.apply(up, w_cat, b_cat, 1, 1)
         affine = []
         for nm in norms:
             affine.extend([nm.weight, nm.bias])

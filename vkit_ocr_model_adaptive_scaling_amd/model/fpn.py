@@ -22,6 +22,12 @@ def build_conv3x3_block(in_channels: int, out_channels: int):
                          helper.ln(out_channels), helper.permute_bhwc_to_bchw(), helper.gelu())
 
 
+def build_conv5x5_block(in_channels: int, out_channels: int):
+    """fpn.py:41-48"""
+    return nn.Sequential(helper.conv5x5(in_channels, out_channels), helper.permute_bchw_to_bhwc(),
+                         helper.ln(out_channels), helper.permute_bhwc_to_bchw(), helper.gelu())
+
+
 def _init_kaiming(module: nn.Module):
     for m in module.modules():  # fpn.py:104-108,185-189
         if isinstance(m, (nn.Conv2d, nn.Linear)):
@@ -98,13 +104,17 @@ class FpnHead(nn.Module):
                  init_output_bias: float = 0.0):
         super().__init__()
         self.upsampling_factor = upsampling_factor
+        # factors 3 and 4: the smoothing convolution is 5x5 and reads the neck feature at its own resolution (ops.upconv5);
+        # such a head never takes upsample_act / ops.HeadsFused, which assume a 3x3 convolution of the upsampled feature
+        self.conv5x5 = upsampling_factor > 2
         self.out_channels = out_channels
         inner_channels = (in_channels + out_channels) // 2
         if 1 <= upsampling_factor <= 2:
             self.step1_conv = build_conv3x3_block(in_channels, inner_channels)
+        elif upsampling_factor <= 4:
+            # fpn.py:170-174: nearest x3 / x4 followed by a 5x5 convolution, run folded (ops.upconv5)
+            self.step1_conv = build_conv5x5_block(in_channels, inner_channels)
         else:
-            # fpn.py:170-176: 5x5 smoothing for factors in (2, 4] is unreachable at the reference's defaults
-            # (adaptive_scaling.py:45,47) and has no HIP kernel.
             raise NotImplementedError()
         self.step2_conv = nn.Sequential(helper.permute_bchw_to_bhwc(), helper.conv1x1(inner_channels, out_channels),
                                         helper.permute_bhwc_to_bchw())
@@ -119,7 +129,7 @@ class FpnHead(nn.Module):
         scripting.refresh_module_spec(self)
 
     def conv_norm_proj(self):
-        """(3x3 conv, its LayerNorm, the 1x1 projection) parameter holders."""
+        """(3x3 or 5x5 conv, its LayerNorm, the 1x1 projection) parameter holders."""
         return self.step1_conv[0], self.step1_conv[2], self.step2_conv[1]
 
     def upsample_act(self, x: torch.Tensor) -> torch.Tensor:
@@ -129,8 +139,16 @@ class FpnHead(nn.Module):
         return x
 
     def forward_act(self, x: torch.Tensor, upsampled: Optional[torch.Tensor] = None) -> torch.Tensor:
-        x = self.upsample_act(x) if upsampled is None else upsampled
-        x = helper.conv_block(x, self.step1_conv[0], self.step1_conv[2], 1, 1)
+        if self.conv5x5:
+            conv, norm = self.step1_conv[0], self.step1_conv[2]
+            if upsampled is None:
+                z = ops.upconv5(x, conv.weight, conv.bias, self.upsampling_factor)
+            else:
+                z = ops.Conv.apply(upsampled, conv.weight, conv.bias, 1, 2)
+            x = ops.LayerNorm.apply(z, norm.weight, norm.bias, True)
+        else:
+            x = self.upsample_act(x) if upsampled is None else upsampled
+            x = helper.conv_block(x, self.step1_conv[0], self.step1_conv[2], 1, 1)
         proj = self.step2_conv[1]
         y = ops.Conv.apply(x, proj.weight, proj.bias, 1, 0)
         return ops.ToNchw.apply(y, self.out_channels)

@@ -42,7 +42,7 @@ def conv3x3(in_channels: int, out_channels: int):
 
 
 def conv5x5(in_channels: int, out_channels: int):
-    """helper.py:34-40 (only reachable with upsampling_factor in (2, 4], fpn.py:170-174; not on the HIP path)."""
+    """helper.py:34-40 (FpnHead at upsampling factors 3 and 4, fpn.py:170-174: ops.upconv5)."""
     return nn.Conv2d(in_channels, out_channels, kernel_size=5, padding=2)
 
 

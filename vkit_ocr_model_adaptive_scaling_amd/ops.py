@@ -765,6 +765,87 @@ class Conv(Function):
         return dx, gw, gb, None, None, None
 
 
+def pack_upconv5_weight(w: torch.Tensor, f: int, Np: int, Cp: int, transposed: int, dtype: torch.dtype) -> torch.Tensor:
+    """Folded per-phase taps of a (N, C, 5, 5) weight (csrc/upconv5.hip, vkas_upconv5_fold)."""
+    def build():
+        N, C = w.shape[0], w.shape[1]
+        out = torch.empty((lib.vkas_upconv5_fold_elems(Np, Cp, f, transposed),), dtype=dtype, device=w.device)
+        check(lib.vkas_upconv5_fold(_p(w.contiguous()), _p(out), N, C, Np, Cp, f, transposed, _dtc(dtype), _stream()),
+              'upconv5_fold')
+        return out
+    return _cached_pack(w, ('upconv5', f, Np, Cp, transposed, dtype), build)
+
+
+class UpConv5(Function):
+    """Nearest x f upsample followed by helper.conv5x5 (pad 2), f in {3, 4}: the smoothing convolution of FpnHead at those
+    factors (fpn.py:41-48,170-174), without the upsampled tensor.  Each output phase is a small convolution over x with
+    folded taps (csrc/upconv5.hip).  x (B, H, W, Cp) 16-bit activation; weight (N, C, 5, 5); bias (N,) or None; the output
+    is (B, f H, f W, rup8(N)).  The backward reads dy densely, so a point-sparse dy (PreciseLoss) needs nothing special."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, f: int):
+        _require_cuda(x, weight)
+        x = as_act(x)
+        if x.dtype not in _MFMA_DTYPES:
+            raise TypeError('UpConv5: 16-bit activations only (fp32 takes upconv5(), the materialised composite)')
+        N, C, KH, KW = weight.shape
+        B, H, W, Cp = x.shape
+        if (KH, KW) != (5, 5) or Cp != rup8(C):
+            raise ValueError(f'UpConv5: weight {tuple(weight.shape)} does not fit a {Cp}-channel activation')
+        Np = rup8(N)
+        Bf = pack_upconv5_weight(weight, f, Np, Cp, 0, x.dtype)
+        out = new_act(B, f * H, f * W, Np, x)
+        geom = _geom(B, H, W, f * H, f * W, Cp, act_ld(x), 5, 5, 1, 2)
+        M = B * f * H * f * W
+        kt = (64 if f == 4 else 49) * C  # folded taps of all phases (16 x 2 x 2 at f = 4, 7 x 7 at f = 3) times C
+        _timed('upconv5_nt_kernel', x, 2.0 * (M // (f * f)) * N * kt, M, N, kt // (f * f),
+               lambda: check(lib.vkas_upconv5_fwd(_p(x), ctypes.byref(geom), f, _p(Bf), Np, _p(pad_vector(bias, Np)), _p(out),
+                                                  act_ld(out), _dt(x), _stream()), 'upconv5_fwd'))
+        ctx.save_for_backward(x, weight, bias if bias is not None else torch.empty(0, device=x.device))
+        ctx.cfg = (f, bias is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight, bias = ctx.saved_tensors
+        f, has_bias = ctx.cfg
+        dy = as_act(dy)
+        N, C = weight.shape[0], weight.shape[1]
+        B, H, W, Cp = x.shape
+        Np = dy.shape[3]
+        geom = _geom(B, H, W, f * H, f * W, Cp, act_ld(x), 5, 5, 1, 2)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            Bt = pack_upconv5_weight(weight, f, Np, Cp, 1, x.dtype)
+            dx = new_act(B, H, W, Cp, x)
+            check(lib.vkas_upconv5_dgrad(_p(dy), act_ld(dy), ctypes.byref(geom), f, _p(Bt), Np, _p(dx), act_ld(dx), _dt(x),
+                                         _stream()), 'upconv5_dgrad')
+        gw = gb = None
+        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
+            gm = 9 if f == 3 else 4
+            nw = f * f * Np * gm * Cp
+            buf = torch.zeros((nw + Np,), dtype=_FLOAT, device=x.device)
+            wsb = lib.vkas_upconv5_wgrad_ws_bytes(B, H, W, Np)
+            ws = _ws(wsb, x.device)
+            check(lib.vkas_upconv5_wgrad(_p(x), ctypes.byref(geom), f, _p(dy), act_ld(dy), Np, _p(ws), wsb, _p(buf[:nw]),
+                                         _p(buf[nw:]) if has_bias else None, _dt(x), _stream()), 'upconv5_wgrad')
+            gw = torch.empty((N, C, 5, 5), dtype=_FLOAT, device=x.device)
+            check(lib.vkas_upconv5_unfold_wgrad(_p(buf[:nw]), _p(gw), N, C, Np, Cp, f, 0, _stream()), 'upconv5_unfold_wgrad')
+            gb = buf[nw:nw + N] if has_bias else None
+        return dx, gw, gb, None
+
+
+def upconv5(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], f: int) -> torch.Tensor:
+    """conv5x5(nearest_up(x, f)) for f in {3, 4}: the folded kernels (UpConv5) for 16-bit activations.  The fp32 parity
+    mode runs the materialised composite instead - Resize (nearest) to (f H, f W), then the generic implicit GEMM with a
+    5x5 / pad 2 geometry - which is exact and simple and only meant for checking, not for speed."""
+    if f not in (3, 4):
+        raise ValueError(f'upconv5: upsampling factor {f} (3 or 4 only)')
+    if x.dtype == _FLOAT:
+        return Conv.apply(Resize.apply(x, (x.shape[1] * f, x.shape[2] * f), 1), weight, bias, 1, 2)
+    return UpConv5.apply(x, weight, bias, f)
+
+
 class LayerNorm(Function):
     """helper.ln (+ helper.gelu) on an NHWC activation: model/helper.py:96-101."""
 
