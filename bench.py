@@ -10,8 +10,15 @@ and GPU (BASELINE.json configs[2]; weak scaling over GPUs = configs[3]).
 Prints ONE JSON line on rank 0; ``--dump-outputs DIR`` also writes what the last timed step computed as .npy files (see
 --help).  ``roofline`` describes the dominant kernel (the bf16 MFMA implicit-GEMM that runs
 the head 3x3 convolutions, their dgrads and every 1x1): algorithmic FLOPs per launch / average launch duration,
-both measured with HIP events on the launch stream during the timed steps.  ``cpu_baseline`` is the oracle
-(oracle/torch_oracle.py, a CPU restatement of the reference pinned to the reference's outputs) timed on the host.
+both measured with HIP events on the launch stream during the timed steps.
+
+A plain run sets up, warms up, times the steps, writes the dump and prints the line.  ``--full`` adds what the headline
+figure does not need, all of it after the timed steps: ``cpu_baseline``, the oracle (oracle/torch_oracle.py, a CPU
+restatement of the reference pinned to the reference's outputs) timed on the host; config 3's ``config.per_pass`` (single
+passes, the other pass schedule, the dense point backward, the label-point forward); and for configs 2 / 5 the eager pass
+behind the timed region that their ``roofline`` and ``config.eager_ms_per_step`` come from.
+
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full
 """
 import argparse
 import json
@@ -279,17 +286,19 @@ def run_forward_config(args, world, rank, device, dist):
                      ['rough_char_mask', 'rough_char_height', 'precise_char_prob', 'precise_char_up_left_corner_offset',
                       'precise_char_corner_angle_distribution', 'precise_char_corner_distance'])
             write_dump(args.dump_outputs, list(zip(names, out)))
-        # per-kernel durations (the roofline object): HIP events cannot be recorded inside a graph replay, so the same steps run
-        # once more eagerly with the launch timer, outside the timed region
-        ops.TIMER = ops.LaunchTimer()
+        # --full: per-kernel durations (the roofline object).  HIP events cannot be recorded inside a graph replay, so the
+        # same steps run once more eagerly with the launch timer, outside the timed region
         n_k = min(args.steps, 5)
-        torch.cuda.synchronize()
-        tk = time.perf_counter()
-        for i in range(args.warmup, args.warmup + n_k):
-            eager_step(i)
-        torch.cuda.synchronize()
-        eager_elapsed = time.perf_counter() - tk
-    timer, ops.TIMER = ops.TIMER, None
+        timer = eager_elapsed = None
+        if args.full:
+            ops.TIMER = ops.LaunchTimer()
+            torch.cuda.synchronize()
+            tk = time.perf_counter()
+            for i in range(args.warmup, args.warmup + n_k):
+                eager_step(i)
+            torch.cuda.synchronize()
+            eager_elapsed = time.perf_counter() - tk
+            timer, ops.TIMER = ops.TIMER, None
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -314,10 +323,11 @@ def run_forward_config(args, world, rank, device, dist):
                       'megapixels_per_step': round(sum(h * w for h, w in timed_shapes) / len(timed_shapes) / 1e6 * B, 3),
                       'host_enqueue_ms_per_step': round(1000.0 * enqueue / args.steps, 2),
                       'hip_graph_replay': use_graphs, 'graphs_captured': cache.captures,
-                      'eager_ms_per_step': round(1000.0 * eager_elapsed / n_k, 3),
-                      'kernel_timing': 'eager pass of %d steps behind the timed region' % n_k},
-           'roofline': roofline_from_timer(timer, eager_elapsed, n_k)}
-    if world == 1 and not args.no_cpu_baseline:
+                      'eager_ms_per_step': round(1000.0 * eager_elapsed / n_k, 3) if args.full else None,
+                      'kernel_timing': 'eager pass of %d steps behind the timed region' % n_k if args.full else None,
+                      'full': args.full},
+           'roofline': roofline_from_timer(timer, eager_elapsed, n_k) if args.full else None}
+    if world == 1 and args.full and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline_forward(args.config)
     print(json.dumps(out), flush=True)
 
@@ -354,7 +364,7 @@ def cpu_baseline_forward(config):
                           f'scaled by pixel count to the mean page of the shape set ({mp_full:.2f} MP): {scaled:.1f} s/image'}
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=5)
@@ -362,10 +372,13 @@ def main():
     ap.add_argument('--batch', type=int, default=8)
     ap.add_argument('--size', type=int, default=1024)
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'f32'])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run the side measurements the headline figure does not need: '
+                         'cpu_baseline, config 3\'s per_pass figures, the eager kernel-timing pass of configs 2 / 5')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without cpu_baseline')
     ap.add_argument('--no-per-pass', action='store_true',
-                    help='skip the single-pass / other-schedule / dense-backward side measurements (profiling runs: the '
-                         'kernel statistics then cover warmup + timed steps only)')
+                    help='--full without the single-pass / other-schedule / dense-backward side measurements (profiling '
+                         'runs: the kernel statistics then cover warmup + timed steps only)')
     ap.add_argument('--no-graphs', action='store_true', help='--config 2 / 5: enqueue every launch from Python instead of '
                     'replaying one captured HIP graph per input shape')
     ap.add_argument('--detail', action='store_true', help='per-shape GEMM timing table on stderr')
@@ -382,9 +395,14 @@ def main():
                          'Config 3: rough_loss, precise_loss, params (the updated parameters) and param_update (what the '
                          'last step changed); config 2: the four backbone features; config 5: the post-processed maps '
                          'of the last page.  The inputs depend on the arguments only, so two builds can be compared')
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error('--steps must be at least 1 and --warmup at least 0')
+    return args
+
+
+def main():
+    args = parse_args()
 
     import torch
     import torch.distributed as dist
@@ -491,7 +509,7 @@ def main():
     # also the single-pass rates (forward + loss + backward of one batch of `batch` images, no optimizer),
     # so that either reading of "batch 8" is covered.  Outside the timed region; one rank only.
     per_pass = None
-    if world == 1 and not args.no_per_pass:
+    if world == 1 and args.full and not args.no_per_pass:
         def pass_ms(run, n=3):
             run()
             torch.cuda.synchronize()
@@ -569,9 +587,9 @@ def main():
                                                'label_point_backward': 'compact (B*P rows)' if ops._POINT_SPARSE else 'dense',
                                                'per_pass': per_pass,
                                                'host_enqueue_ms_per_step': round(1000.0 * enqueue / args.steps, 2),
-                                               'losses': [round(rl, 5), round(pl, 5)]},
+                                               'losses': [round(rl, 5), round(pl, 5)], 'full': args.full},
                'roofline': roof}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(hw, 1337)
         print(json.dumps(out), flush=True)
     if world > 1 or force_reducer:
