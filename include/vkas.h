@@ -409,6 +409,17 @@ int vkas_rough_postprocess(const float* mask_logit, const float* height, int B, 
 int vkas_precise_postprocess(const float* prob_logit, const float* offset, const float* angle, const float* dist, int B,
                              int H, int W, const int* valid_h, const int* valid_w, float* out_prob, float* out_offset,
                              float* out_angle, float* out_dist, void* stream);
+/* Character quadrilaterals from the precise maps (:399-465,481-491).  prob (B,H,W) as vkas_precise_postprocess writes it,
+ * offset (B,H,W,2), angle (B,H,W,4) softmaxed, dist (B,H,W,4), all fp32.  A pixel is a peak when prob equals the max over the
+ * size x size window [c - size/2, c + size - 1 - size/2] clamped to the map (scipy maximum_filter) and !(prob < thr).
+ * Outputs, capacity B*H*W rows in np.nonzero (b, y, x) order: *count (int32), points (cap,3) int32 (b, y, x), probs (cap),
+ * quads (cap,4,2) fp32 (y, x) corners up-left, up-right, down-right, down-left, at p = (y * scale_y, x * scale_x).
+ * Capture-safe: no allocation, no synchronisation, no atomics (deterministic).  B*H*W < 2^31, size >= 1; workspace
+ * 16-byte aligned, at least vkas_char_polygons_workspace_bytes (which returns -1 on bad arguments). */
+long vkas_char_polygons_workspace_bytes(int B, int H, int W, int size);
+int vkas_char_polygons(const float* prob, const float* offset, const float* angle, const float* dist, int B, int H, int W,
+                       int size, float thr, float scale_y, float scale_x, void* workspace, size_t workspace_bytes,
+                       int* count, int* points, float* probs, float* quads, void* stream);
 
 /* ---- optimizer on the flat parameter / gradient buffers: train.py:468-478 ------------------------------ */
 /* sumsq (1 double, zeroed by the call) = sum g^2 */

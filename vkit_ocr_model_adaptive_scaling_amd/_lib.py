@@ -150,6 +150,9 @@ _SIGS = {
     'vkas_pack_many_blocks': (c_int, [_P]),
     'vkas_rough_postprocess': (c_int, [_P, _P, c_int, c_int, c_int, _P, _P, c_float, c_float, _P, _P, _P]),
     'vkas_precise_postprocess': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
+    'vkas_char_polygons_workspace_bytes': (c_long, [c_int, c_int, c_int, c_int]),
+    'vkas_char_polygons': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, _P, c_size_t,
+                                   _P, _P, _P, _P, _P]),
     'vkas_l2norm_sq': (c_int, [_P, c_long, _P, _P]),
     'vkas_adamw_step': (c_int, [_P, _P, _P, _P, c_long, _P, c_float, c_float, c_float, c_float, c_float, c_float,
                                 c_float, c_int, _P]),

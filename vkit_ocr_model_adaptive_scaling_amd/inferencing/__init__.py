@@ -3,6 +3,8 @@ from .adaptive_scaling import (
     AdaptiveScalingInferencingConfig,
     AdaptiveScalingInferencingRoughInferResult,
     AdaptiveScalingInferencingPresiceInferResult,
+    AdaptiveScalingInferencingPreciseCharPolygons,
     AdaptiveScalingInferencing,
+    precise_group_char_polygons,
 )
 from .graphs import GraphCache, param_stamp

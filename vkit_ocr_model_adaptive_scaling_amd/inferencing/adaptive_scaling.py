@@ -1,13 +1,17 @@
 """Tensor side of the adaptive-scaling inference path (mirror of vkit_open_model/inferencing/adaptive_scaling.py:92-188,
 295-396 and the shape rules of :95-107): pad-to-32, the short-side-720 rule, the no-grad model calls and the
-sigmoid / threshold / softmax / padding-mask post-processing, which runs on the device (csrc/infer.hip).
+sigmoid / threshold / softmax / padding-mask post-processing, which runs on the device (csrc/infer.hip).  The step that
+turns the precise maps into characters - the maximum-filter peaks of the char probability map and one quadrilateral per
+peak (:399-465,481-491) - runs on the device too (csrc/charpoly.hip, ``precise_infer_char_polygons``), inside the same
+HIP graph as the model call; ``precise_group_char_polygons`` splits its points by a caller-given region label map on the
+host (the device-free half of :467-525).
 
-Out of scope: the CPU geometry around it - polygons from masks, text-region flattening / stacking,
-polygon building (vkit, cv2, scipy; third-party code that is absent here).  Images are plain (H, W, 3) uint8 arrays
-instead of ``vkit.element.Image``; results carry numpy arrays instead of ``Mask`` / ``ScoreMap``.  The reference loads
-a TorchScript file (``model_jit``, :85-90); so does this mirror (``torch.jit.save`` of ``torch.jit.script(model)``, see
-model/scripting.py), and it also takes the scripted or the eager ``AdaptiveScaling`` module itself, or a state-dict file in
-the reference's ``RestoreState`` schema.
+Out of scope: the CPU geometry around it - rough-side regions from masks, text-region flattening /
+stacking, building the region label map from them and remapping polygons through the flattening (vkit, cv2; third-party
+code that is absent here).  Images are plain (H, W, 3) uint8 arrays instead of ``vkit.element.Image``; results carry
+numpy arrays instead of ``Mask`` / ``ScoreMap`` / ``Polygon``.  The reference loads a TorchScript file (``model_jit``,
+:85-90); so does this mirror (``torch.jit.save`` of ``torch.jit.script(model)``, see model/scripting.py), and it also takes
+the scripted or the eager ``AdaptiveScaling`` module itself, or a state-dict file in the reference's ``RestoreState`` schema.
 """
 import ctypes
 import math
@@ -45,6 +49,9 @@ class AdaptiveScalingInferencingConfig:
     # replay one captured HIP graph per (pass, padded shape) instead of enqueuing its few hundred launches from Python; the
     # first call of a shape runs eagerly (inferencing/graphs.py).  Same results bit for bit.
     use_hip_graphs: bool = True
+    # :58-59, read by precise_infer_char_polygons (peak threshold, compared in fp32; scipy maximum_filter size, truncated)
+    precise_build_polygons_positive_char_prob_thr: float = 0.7
+    precise_build_polygons_maximum_filter_size: float = 5
 
 
 @attrs.define
@@ -65,6 +72,16 @@ class AdaptiveScalingInferencingPresiceInferResult:
     precise_np_char_up_left_corner_offset: np.ndarray      # (H/FDF, W/FDF, 2)
     precise_np_char_corner_angle_distribution: np.ndarray  # (H/FDF, W/FDF, 4)
     precise_np_char_corner_distance: np.ndarray            # (H/FDF, W/FDF, 4)
+
+
+@attrs.define
+class AdaptiveScalingInferencingPreciseCharPolygons:
+    """The characters of one page (:399-465,481-525): the peaks of the precise char probability map and their
+    quadrilaterals, in np.nonzero (row-major) order."""
+    padded_image: np.ndarray
+    points: np.ndarray    # (N, 2) int32 (y, x) in map pixels
+    probs: np.ndarray     # (N,) float32, the char probability at each point
+    polygons: np.ndarray  # (N, 4, 2) float32 (y, x) in padded-image pixels: up-left, up-right, down-right, down-left
 
 
 def rough_resized_shape(height: int, width: int, short_side: int) -> Tuple[int, int]:
@@ -172,34 +189,44 @@ class AdaptiveScalingInferencing:
             rough_char_mask=out_mask[0].cpu().numpy(), rough_char_height_score_map=out_height[0].cpu().numpy())
 
     # ---- precise pass --------------------------------------------------------------------------------------------
-    def precise_infer_batch(self, images: Sequence) -> Sequence[AdaptiveScalingInferencingPresiceInferResult]:
-        """:295-396 for a batch of stacked-region pages: each is padded to x32, pages of one padded size share a model
-        call (the reference feeds one page at a time)."""
+    def _precise_groups(self, images: Sequence):
+        """Pads each page to x32 and groups the pages by padded size: [(padded shape, indices)], the mats, the padded mats."""
         c = self.config
         mats = [_as_mat(im) for im in images]
         padded = [pad_mat_to_make_divisible(m, c.backbone_downsampling_factor) for m in mats]
-        fdf = 4 // c.precise_head_upsampling_factor
-        results = [None] * len(mats)
         groups = {}
         for i, p in enumerate(padded):
             groups.setdefault(p.shape[:2], []).append(i)
-        for shape, idxs in groups.items():
+        return list(groups.items()), mats, padded
+
+    def _precise_maps(self, x, vh, vw, H: int, W: int):
+        """The precise model call + the device post-processing (:318-396): prob (B,H,W), offset (B,H,W,2), softmaxed angle
+        (B,H,W,4) and distance (B,H,W,4), fp32."""
+        prob, offset, angle, dist = self.model.forward_precise(x)
+        B = prob.shape[0]
+        assert tuple(prob.shape) == (B, 1, H, W)
+        o_prob = torch.empty((B, H, W), dtype=torch.float32, device=x.device)
+        o_off = torch.empty((B, H, W, 2), dtype=torch.float32, device=x.device)
+        o_ang = torch.empty((B, H, W, 4), dtype=torch.float32, device=x.device)
+        o_dist = torch.empty((B, H, W, 4), dtype=torch.float32, device=x.device)
+        check(lib.vkas_precise_postprocess(_ptr(prob.contiguous()), _ptr(offset.contiguous()), _ptr(angle.contiguous()),
+                                           _ptr(dist.contiguous()), B, H, W, _ptr(vh), _ptr(vw), _ptr(o_prob),
+                                           _ptr(o_off), _ptr(o_ang), _ptr(o_dist), ops._stream()), 'precise_postprocess')
+        return o_prob, o_off, o_ang, o_dist
+
+    def precise_infer_batch(self, images: Sequence) -> Sequence[AdaptiveScalingInferencingPresiceInferResult]:
+        """:295-396 for a batch of stacked-region pages: each is padded to x32, pages of one padded size share a model
+        call (the reference feeds one page at a time)."""
+        fdf = 4 // self.config.precise_head_upsampling_factor
+        groups, mats, padded = self._precise_groups(images)
+        results = [None] * len(mats)
+        for shape, idxs in groups:
             x = self._to_device([padded[i] for i in idxs])
             H, W = shape[0] // fdf, shape[1] // fdf
             vh, vw = self._valid([mats[i].shape[:2] for i in idxs], fdf, x.device)
 
             def precise_pass(x, vh, vw):
-                prob, offset, angle, dist = self.model.forward_precise(x)
-                B = prob.shape[0]
-                assert tuple(prob.shape) == (B, 1, H, W)
-                o_prob = torch.empty((B, H, W), dtype=torch.float32, device=x.device)
-                o_off = torch.empty((B, H, W, 2), dtype=torch.float32, device=x.device)
-                o_ang = torch.empty((B, H, W, 4), dtype=torch.float32, device=x.device)
-                o_dist = torch.empty((B, H, W, 4), dtype=torch.float32, device=x.device)
-                check(lib.vkas_precise_postprocess(_ptr(prob.contiguous()), _ptr(offset.contiguous()), _ptr(angle.contiguous()),
-                                                   _ptr(dist.contiguous()), B, H, W, _ptr(vh), _ptr(vw), _ptr(o_prob),
-                                                   _ptr(o_off), _ptr(o_ang), _ptr(o_dist), ops._stream()), 'precise_postprocess')
-                return o_prob, o_off, o_ang, o_dist
+                return self._precise_maps(x, vh, vw, H, W)
 
             with torch.no_grad():
                 o_prob, o_off, o_ang, o_dist = self.graphs.run('precise', precise_pass, [x, vh, vw], param_stamp(self.model))
@@ -213,3 +240,70 @@ class AdaptiveScalingInferencing:
 
     def precise_infer(self, image) -> AdaptiveScalingInferencingPresiceInferResult:
         return self.precise_infer_batch([image])[0]
+
+    # ---- characters from the precise maps ----------------------------------------------------------------------
+    def precise_infer_char_polygons_batch(self, images: Sequence) -> Sequence[AdaptiveScalingInferencingPreciseCharPolygons]:
+        """The precise pass followed by peak finding and one quadrilateral per peak (:399-465,481-491) on the device, in
+        the same HIP graph (csrc/charpoly.hip): only the peak count and the peak rows cross PCIe, not the maps.  Pages are
+        grouped by padded size as in ``precise_infer_batch``.  A map point (y, x) sits at (y * Hp / H, x * Wp / W) of the
+        Hp x Wp padded image (vkit's ``Point.to_conducted_resized_point``, restated as proportional scaling)."""
+        c = self.config
+        fdf = 4 // c.precise_head_upsampling_factor
+        thr, size = float(c.precise_build_polygons_positive_char_prob_thr), c.precise_build_polygons_maximum_filter_size
+        groups, mats, padded = self._precise_groups(images)
+        results = [None] * len(mats)
+        for shape, idxs in groups:
+            x = self._to_device([padded[i] for i in idxs])
+            H, W = shape[0] // fdf, shape[1] // fdf
+            scale_y, scale_x = shape[0] / H, shape[1] / W
+            vh, vw = self._valid([mats[i].shape[:2] for i in idxs], fdf, x.device)
+
+            def char_polygons_pass(x, vh, vw):
+                o_prob, o_off, o_ang, o_dist = self._precise_maps(x, vh, vw, H, W)
+                return ops.char_polygons(o_prob, o_off, o_ang, o_dist, thr, size, scale_y, scale_x)
+
+            with torch.no_grad():
+                count, points, probs, quads = self.graphs.run(('precise_char_polygons', thr, size), char_polygons_pass,
+                                                              [x, vh, vw], param_stamp(self.model))
+            n = int(count.item())
+            points, probs, quads = (t[:n].cpu().numpy() for t in (points, probs, quads))
+            bounds = np.searchsorted(points[:, 0], np.arange(len(idxs) + 1))  # rows are sorted by page
+            for k, i in enumerate(idxs):
+                lo, hi = bounds[k], bounds[k + 1]
+                results[i] = AdaptiveScalingInferencingPreciseCharPolygons(
+                    padded_image=padded[i], points=np.ascontiguousarray(points[lo:hi, 1:]), probs=probs[lo:hi],
+                    polygons=quads[lo:hi])
+        return results
+
+    def precise_infer_char_polygons(self, image) -> AdaptiveScalingInferencingPreciseCharPolygons:
+        return self.precise_infer_char_polygons_batch([image])[0]
+
+    @staticmethod
+    def precise_group_char_polygons(result: AdaptiveScalingInferencingPreciseCharPolygons,
+                                    region_labels: np.ndarray) -> Sequence[AdaptiveScalingInferencingPreciseCharPolygons]:
+        """The module-level ``precise_group_char_polygons`` (host only)."""
+        return precise_group_char_polygons(result, region_labels)
+
+
+def precise_group_char_polygons(result: AdaptiveScalingInferencingPreciseCharPolygons,
+                                region_labels: np.ndarray) -> Sequence[AdaptiveScalingInferencingPreciseCharPolygons]:
+    """The device-free half of ``precise_build_grouped_polygons`` (:467-525): ``region_labels`` is an (H, W) integer map at
+    the precise map's resolution, 0 = no region; returns one result per label 1..max with the points that fall on it, in
+    the order of ``result`` - np.nonzero's, which is the reference's per-region order, since it restricts the peaks to a
+    region after the maximum filter.  Building the label map from the flattened text regions and their boxes stays with
+    the caller."""
+    labels = np.asarray(region_labels)
+    if labels.ndim != 2 or not np.issubdtype(labels.dtype, np.integer):
+        raise ValueError(f'region_labels must be a 2-D integer map, got {labels.dtype} {labels.shape}')
+    Hp, Wp = result.padded_image.shape[:2]
+    H, W = labels.shape
+    if H < 1 or W < 1 or Hp % H or Wp % W or Hp // H != Wp // W:
+        raise ValueError(f'region_labels {labels.shape} is not at the precise map resolution of a {(Hp, Wp)} page')
+    at = labels[result.points[:, 0], result.points[:, 1]]
+    groups = []
+    for label in range(1, int(labels.max()) + 1):
+        sel = at == label
+        groups.append(AdaptiveScalingInferencingPreciseCharPolygons(
+            padded_image=result.padded_image, points=result.points[sel], probs=result.probs[sel],
+            polygons=result.polygons[sel]))
+    return groups

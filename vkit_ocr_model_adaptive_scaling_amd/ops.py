@@ -2070,3 +2070,46 @@ class CrossEntropy(Function):
         check(lib.vkas_cross_entropy_bwd(_p(logits), _p(target), int(ctx.hard), rows, classes, _p(dloss), _p(d), _stream()),
               'cross_entropy_bwd')
         return d, None
+
+
+def char_polygons(prob: torch.Tensor, offset: torch.Tensor, angle: torch.Tensor, dist: torch.Tensor, thr: float, size,
+                  scale_y: float, scale_x: float):
+    """Peaks of the precise char-probability maps and their quadrilaterals (inferencing/adaptive_scaling.py:399-465,481-491,
+    csrc/charpoly.hip).  prob (B,H,W), offset (B,H,W,2), angle (B,H,W,4) softmaxed, dist (B,H,W,4), fp32 on the device.
+    ``size`` is scipy's maximum_filter size (a float is truncated, as scipy does); ``thr`` is compared in fp32.  Returns
+    ``(count, points, probs, quads)`` as device tensors of capacity B*H*W rows - (1,) int32, (cap,3) int32 (b, y, x),
+    (cap,) fp32, (cap,4,2) fp32 (y, x) - of which the first ``count`` are valid, in (b, y, x) order.  Never synchronises,
+    so it can be captured into a HIP graph."""
+    if prob.dim() != 3:
+        raise ValueError(f'char_polygons: prob must be (B, H, W), got {tuple(prob.shape)}')
+    B, H, W = prob.shape
+    for name, t, c in (('offset', offset, 2), ('angle', angle, 4), ('dist', dist, 4)):
+        if tuple(t.shape) != (B, H, W, c):
+            raise ValueError(f'char_polygons: {name} must be {(B, H, W, c)}, got {tuple(t.shape)}')
+    for name, t in (('prob', prob), ('offset', offset), ('angle', angle), ('dist', dist)):
+        if t.dtype != torch.float32:
+            raise ValueError(f'char_polygons: {name} must be float32, got {t.dtype}')
+    if H < 1 or W < 1:
+        raise ValueError(f'char_polygons: empty map {(H, W)}')
+    isize = int(size)
+    if isize < 1:
+        raise ValueError(f'char_polygons: maximum filter size {size} truncates to {isize} (< 1)')
+    if B * H * W >= 1 << 31:
+        raise ValueError(f'char_polygons: B*H*W = {B * H * W} must stay below 2^31')
+    _require_cuda(prob, offset, angle, dist)
+    prob, offset, angle, dist = (t.contiguous() for t in (prob, offset, angle, dist))
+    cap, dev = B * H * W, prob.device
+    nbytes = lib.vkas_char_polygons_workspace_bytes(B, H, W, isize)
+    if nbytes < 0:
+        check(-1, 'char_polygons')
+    ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+    count = torch.empty((1,), dtype=torch.int32, device=dev)
+    points = torch.empty((cap, 3), dtype=torch.int32, device=dev)
+    probs = torch.empty((cap,), dtype=_FLOAT, device=dev)
+    quads = torch.empty((cap, 4, 2), dtype=_FLOAT, device=dev)
+    if cap == 0:
+        return count.zero_(), points, probs, quads
+    check(lib.vkas_char_polygons(_p(prob), _p(offset), _p(angle), _p(dist), B, H, W, isize, float(thr), float(scale_y),
+                                 float(scale_x), _p(ws), ws.numel(), _p(count), _p(points), _p(probs), _p(quads), _stream()),
+          'char_polygons')
+    return count, points, probs, quads
