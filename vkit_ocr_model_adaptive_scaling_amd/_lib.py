@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get('VKAS_LIB_PATH') or os.path.join(_HERE, 'libvkas.so')
 F32, BF16, F16 = 0, 1, 2
 EPI_NONE, EPI_GELU, EPI_SCALE_RES, EPI_DGELU, EPI_ADD, EPI_PATCH, EPI_HEAD = range(7)
 LOSS_FOCAL, LOSS_DICE, LOSS_L1, LOSS_SMOOTH_L1, LOSS_L2 = range(5)
+LOSS_WAHR = 5
+PRECISE_LOSS_EX_SUMS = 16  # VKAS_PRECISE_LOSS_EX_SUMS
 
 
 class ConvGeom(Structure):
@@ -49,6 +51,11 @@ class PreciseLossCfg(Structure):
     _fields_ = [('pos_l2', c_float), ('neg_l2', c_float), ('offset_l1', c_float), ('reg_l1', c_float),
                 ('angle_ce', c_float), ('dist_l1', c_float), ('loss_factor', c_float), ('smooth_beta', c_float),
                 ('out_scale', c_float)]
+
+
+class PreciseLossExtraCfg(Structure):
+    _fields_ = [('mask_focal', c_float), ('prob_l1', c_float), ('prob_wahr', c_float), ('prob_l1_beta', c_float),
+                ('wahr_gamma', c_float), ('focal_alpha', c_float), ('focal_gamma', c_float)]
 
 
 class VkasError(RuntimeError):
@@ -136,6 +143,10 @@ _SIGS = {
     'vkas_points_margin': (c_int, [_P, _P, c_long, c_int, c_int, _P, _P]),
     'vkas_precise_loss_fwd': (c_int, [_P] * 11 + [c_int] * 8 + [POINTER(PreciseLossCfg), _P, _P, _P]),
     'vkas_precise_loss_bwd': (c_int, [_P] * 11 + [c_int] * 8 + [POINTER(PreciseLossCfg), _P, _P, _P, _P, _P, _P, _P]),
+    'vkas_precise_loss_ex_fwd': (c_int, [_P] * 11 + [c_int] * 8 + [POINTER(PreciseLossCfg), _P, POINTER(PreciseLossExtraCfg),
+                                                                     _P, _P, _P]),
+    'vkas_precise_loss_ex_bwd': (c_int, [_P] * 11 + [c_int] * 8 + [POINTER(PreciseLossCfg), _P, POINTER(PreciseLossExtraCfg)]
+                                 + [_P] * 8),
     'vkas_elementwise_loss_fwd': (c_int, [c_int, _P, _P, _P, c_long, c_float, c_float, c_float, _P, _P, _P]),
     'vkas_elementwise_loss_bwd': (c_int, [c_int, _P, _P, _P, c_long, c_float, c_float, c_float, _P, _P, _P, _P]),
     'vkas_cross_entropy_fwd': (c_int, [_P, _P, c_int, c_long, c_int, _P, _P, _P]),

@@ -1,13 +1,10 @@
 // Primitive loss callables of vkit_open_model/loss_function (the classes the composite adaptive-scaling losses are
-// built from and that loss_function/__init__.py:12-18 exports): focal-with-logits, dice, (smooth) L1, L2 and
-// soft-target cross entropy, each as one reduction pass (fp64 sums) + a one-thread finalize, and one elementwise
-// backward pass that uses the saved sums.  fp32 inputs; gradients are produced for `pred` only (targets are data).
+// built from and that loss_function/__init__.py:12-18 exports): focal-with-logits, dice, (smooth) L1, L2, weight-adaptive
+// heatmap regression and soft-target cross entropy, each as one reduction pass (fp64 sums) + a one-thread finalize, and one
+// elementwise backward pass that uses the saved sums.  fp32 inputs; gradients are produced for `pred` only (targets are data).
 #include "vkas_common.h"
 
 namespace {
-
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
-__device__ __forceinline__ float softplusf_(float x) { return fmaxf(x, 0.f) + log1pf(__expf(-fabsf(x))); }
 
 template <int N>
 __device__ __forceinline__ void block_accumulate(double* acc, double* __restrict__ sums) {
@@ -30,16 +27,15 @@ __device__ __forceinline__ void block_accumulate(double* acc, double* __restrict
 template <int KIND>
 __device__ __forceinline__ float elem_value(float x, float t, float p0, float p1) {
   if constexpr (KIND == VKAS_LOSS_FOCAL) {  // focal_with_logits.py:36-42 (torchvision sigmoid_focal_loss closed form)
-    const float p = sigmoidf_(x);
-    const float ce = softplusf_(x) - x * t;
-    const float pt = p * t + (1.f - p) * (1.f - t);
-    const float at = p0 >= 0.f ? p0 * t + (1.f - p0) * (1.f - t) : 1.f;
-    return at * ce * powf(1.f - pt, p1);
+    return vkas_focal_value(x, t, p0, p1);
   } else if constexpr (KIND == VKAS_LOSS_L1) {  // l1.py:38-39 (F.l1_loss)
     return fabsf(x - t);
   } else if constexpr (KIND == VKAS_LOSS_SMOOTH_L1) {  // l1.py:41 (F.smooth_l1_loss, beta = p0)
     const float a = fabsf(x - t);
     return a < p0 ? 0.5f * a * a / p0 : a - 0.5f * p0;
+  } else if constexpr (KIND == VKAS_LOSS_WAHR) {  // weight_adaptive_heatmap_regression.py:29-32 (gamma = p0)
+    const float s = powf(t, p0);
+    return (s * (1.f - x) + (1.f - s) * x) * (x - t) * (x - t);
   } else {  // l2.py:29-32 (F.mse_loss)
     return (x - t) * (x - t);
   }
@@ -48,21 +44,17 @@ __device__ __forceinline__ float elem_value(float x, float t, float p0, float p1
 template <int KIND>
 __device__ __forceinline__ float elem_grad(float x, float t, float p0, float p1) {
   if constexpr (KIND == VKAS_LOSS_FOCAL) {
-    const float p = sigmoidf_(x);
-    const float dp = p * (1.f - p);
-    const float ce = softplusf_(x) - x * t;
-    const float pt = p * t + (1.f - p) * (1.f - t);
-    const float at = p0 >= 0.f ? p0 * t + (1.f - p0) * (1.f - t) : 1.f;
-    const float om = 1.f - pt;
-    // d/dx [ce * om^g] = (p - t) om^g - ce g om^(g-1) dpt/dx,  dpt/dx = dp (2t - 1)
-    const float tail = p1 != 0.f ? ce * p1 * powf(om, p1 - 1.f) * dp * (2.f * t - 1.f) : 0.f;
-    return at * ((p - t) * powf(om, p1) - tail);
+    return vkas_focal_grad(x, t, p0, p1);
   } else if constexpr (KIND == VKAS_LOSS_L1) {
     const float d = x - t;
     return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
   } else if constexpr (KIND == VKAS_LOSS_SMOOTH_L1) {
     const float d = x - t;
     return fabsf(d) < p0 ? d / p0 : (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f));
+  } else if constexpr (KIND == VKAS_LOSS_WAHR) {
+    // d/dx [w (x - t)^2] with the weight w = s (1 - x) + (1 - s) x also depending on x: (1 - 2s)(x - t)^2 + 2 w (x - t)
+    const float s = powf(t, p0), d = x - t;
+    return (1.f - 2.f * s) * d * d + 2.f * (s * (1.f - x) + (1.f - s) * x) * d;
   } else {
     return 2.f * (x - t);
   }
@@ -193,6 +185,7 @@ static unsigned prim_grid(long n) {
     case VKAS_LOSS_L1: { constexpr int KIND = VKAS_LOSS_L1; __VA_ARGS__ } break;               \
     case VKAS_LOSS_SMOOTH_L1: { constexpr int KIND = VKAS_LOSS_SMOOTH_L1; __VA_ARGS__ } break; \
     case VKAS_LOSS_L2: { constexpr int KIND = VKAS_LOSS_L2; __VA_ARGS__ } break;               \
+    case VKAS_LOSS_WAHR: { constexpr int KIND = VKAS_LOSS_WAHR; __VA_ARGS__ } break;           \
     default:                                                              \
       vkas_set_error("vkas_elementwise_loss: unknown kind %d", (int)(kind)); \
       return VKAS_E_ARG;                                                  \
@@ -203,6 +196,7 @@ extern "C" int vkas_elementwise_loss_fwd(int kind, const float* pred, const floa
   VKAS_CHECK(pred && gt && sums && loss, "vkas_elementwise_loss_fwd: null pointer");
   VKAS_CHECK(n >= 0, "vkas_elementwise_loss_fwd: negative size");
   VKAS_CHECK(kind != VKAS_LOSS_SMOOTH_L1 || p0 > 0.f, "vkas_elementwise_loss_fwd: smooth-L1 beta must be positive");
+  VKAS_CHECK(kind != VKAS_LOSS_WAHR || !mask, "vkas_elementwise_loss_fwd: WAHR takes no mask");
   hipStream_t st = vkas_stream(stream);
   (void)hipMemsetAsync(sums, 0, 4 * sizeof(double), st);
   if (n > 0) {
@@ -218,6 +212,7 @@ extern "C" int vkas_elementwise_loss_bwd(int kind, const float* pred, const floa
                                          void* stream) {
   VKAS_CHECK(pred && gt && sums && dloss && dpred, "vkas_elementwise_loss_bwd: null pointer");
   VKAS_CHECK(n >= 0, "vkas_elementwise_loss_bwd: negative size");
+  VKAS_CHECK(kind != VKAS_LOSS_WAHR || !mask, "vkas_elementwise_loss_bwd: WAHR takes no mask");
   if (n == 0) return VKAS_OK;
   hipStream_t st = vkas_stream(stream);
   VKAS_PRIM_KIND(kind, { prim_bwd_kernel<KIND><<<prim_grid(n), 256, 0, st>>>(pred, gt, mask, n, p0, p1, eps, sums, dloss, dpred); })

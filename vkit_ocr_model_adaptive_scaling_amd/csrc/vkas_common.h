@@ -284,6 +284,29 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// Sigmoid focal loss of one logit x against target t (torchvision sigmoid_focal_loss closed form, focal_with_logits.py:36-42)
+// and its d/dx; alpha < 0: no alpha weighting.  Shared by the focal primitive (loss_prims.hip) and the precise loss's mask
+// focal term (loss.hip).
+__device__ __forceinline__ float vkas_sigmoidf(float x) { return 1.f / (1.f + __expf(-x)); }
+__device__ __forceinline__ float vkas_softplusf(float x) { return fmaxf(x, 0.f) + log1pf(__expf(-fabsf(x))); }
+__device__ __forceinline__ float vkas_focal_value(float x, float t, float alpha, float gamma) {
+  const float p = vkas_sigmoidf(x);
+  const float ce = vkas_softplusf(x) - x * t;
+  const float pt = p * t + (1.f - p) * (1.f - t);
+  const float at = alpha >= 0.f ? alpha * t + (1.f - alpha) * (1.f - t) : 1.f;
+  return at * ce * powf(1.f - pt, gamma);
+}
+__device__ __forceinline__ float vkas_focal_grad(float x, float t, float alpha, float gamma) {
+  const float p = 1.f / (1.f + __expf(-x));
+  const float dp = p * (1.f - p);
+  const float ce = fmaxf(x, 0.f) + log1pf(__expf(-fabsf(x))) - x * t;
+  const float pt = p * t + (1.f - p) * (1.f - t);
+  const float at = alpha >= 0.f ? alpha * t + (1.f - alpha) * (1.f - t) : 1.f;
+  const float om = 1.f - pt;
+  // d/dx [ce * om^g] = (p - t) om^g - ce g om^(g-1) dpt/dx,  dpt/dx = dp (2t - 1)
+  const float tail = gamma != 0.f ? ce * gamma * powf(om, gamma - 1.f) * dp * (2.f * t - 1.f) : 0.f;
+  return at * ((p - t) * powf(om, gamma) - tail);
+}
 template <> __device__ __forceinline__ float dgelu_t<f16_t>(float x) { return dgelu_t<bf16_t>(x); }
 
 // ---- LDS-DMA with the waits in the kernel's hands ------------------------------------------------------------------

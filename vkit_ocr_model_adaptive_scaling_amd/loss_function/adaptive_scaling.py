@@ -2,10 +2,10 @@
 vkit_open_model/loss_function/adaptive_scaling.py) as single fused HIP ops.
 
 Same config classes (including the reference's spelling ``...LossFunctionConifg``), same call signatures.
-Only the terms that are active under the reference's default factors have HIP kernels: focal + dice + masked
-log-space smooth-L1 (rough); masked L2 x2, smooth-L1 offsets, distance regulariser, soft-target cross entropy,
-corner distances (precise).  Enabling one of the default-off terms (weighted BCE, precise mask focal, prob L1,
-weight-adaptive heatmap regression) raises NotImplementedError instead of silently computing something else.
+Rough: focal + dice + masked log-space smooth-L1.  Precise: masked L2 x2, smooth-L1 offsets, distance regulariser,
+soft-target cross entropy, corner distances, and the default-off mask focal, prob smooth-L1 and weight-adaptive heatmap
+regression terms (ops.PreciseLossEx, used only when one of their factors is > 0).  The one default-off term without a HIP
+kernel, weighted BCE (rough ``bce_factor``), raises NotImplementedError instead of silently computing something else.
 """
 from typing import Any, Optional, Tuple
 
@@ -13,7 +13,7 @@ import attrs
 import torch
 
 from .. import ops
-from .._lib import RoughLossCfg, PreciseLossCfg
+from .._lib import RoughLossCfg, PreciseLossCfg, PreciseLossExtraCfg
 
 
 @attrs.define
@@ -79,11 +79,15 @@ class AdaptiveScalingPreciseLossFunctionConifg:
 class AdaptiveScalingPreciseLossFunction:
     """loss_function/adaptive_scaling.py:148-346"""
 
-    def __init__(self, config: AdaptiveScalingPreciseLossFunctionConifg, smooth_beta: float = 2.5):
-        if config.char_mask_focal_factor > 0 or config.char_prob_l1_factor > 0 or config.char_prob_wahr_factor > 0:
-            raise NotImplementedError('mask focal / prob L1 / WAHR terms are off by default and have no HIP kernel')
+    def __init__(self, config: AdaptiveScalingPreciseLossFunctionConifg, smooth_beta: float = 2.5,
+                 prob_smooth_beta: float = 0.25, focal_alpha: float = 0.25, focal_gamma: float = 2.0,
+                 wahr_gamma: float = 0.01):
         self.config = config
         self.smooth_beta = smooth_beta  # :159-165
+        self.prob_smooth_beta = prob_smooth_beta  # :156
+        self.focal_alpha = focal_alpha  # :154 -> focal_with_logits.py:21-23
+        self.focal_gamma = focal_gamma
+        self.wahr_gamma = wahr_gamma  # :158 -> weight_adaptive_heatmap_regression.py:20
 
     @classmethod
     def get_label_point_feature(cls, feature: torch.Tensor, label_point_y: torch.Tensor, label_point_x: torch.Tensor):
@@ -106,9 +110,24 @@ class AdaptiveScalingPreciseLossFunction:
         box = downsampled_core_box
         assert tuple(downsampled_char_mask.shape[1:]) == (box.down - box.up + 1, box.right - box.left + 1)
         c = self.config
+        if c.char_mask_focal_factor > 0:
+            assert precise_char_mask_feature is not None  # :273
+            if precise_char_mask_feature.shape != precise_char_prob_feature.shape:  # :213
+                raise ValueError(f'precise loss: mask feature must be {tuple(precise_char_prob_feature.shape)}, got '
+                                 f'{tuple(precise_char_mask_feature.shape)}')
         cfg = PreciseLossCfg(c.char_prob_pos_l2_factor, c.char_prob_neg_l2_factor, c.char_up_left_offset_l1_factor,
                              c.char_up_left_distance_regulation_l1_factor, c.char_corner_angle_cross_entropy_factor,
                              c.char_corner_distance_l1_factor, c.loss_factor, self.smooth_beta, scale)
+        if c.char_mask_focal_factor > 0 or c.char_prob_l1_factor > 0 or c.char_prob_wahr_factor > 0:
+            ex = PreciseLossExtraCfg(max(c.char_mask_focal_factor, 0.0), max(c.char_prob_l1_factor, 0.0),
+                                     max(c.char_prob_wahr_factor, 0.0), self.prob_smooth_beta, self.wahr_gamma,
+                                     self.focal_alpha, self.focal_gamma)
+            mask = precise_char_mask_feature if c.char_mask_focal_factor > 0 else None  # unused otherwise, as today
+            return ops.PreciseLossEx.apply(precise_char_prob_feature, mask, precise_char_up_left_corner_offset_feature,
+                                           precise_char_corner_angle_feature, precise_char_corner_distance_feature,
+                                           downsampled_char_prob_score_map, downsampled_char_mask,
+                                           downsampled_label_point_y, downsampled_label_point_x, char_up_left_offsets,
+                                           char_corner_angles, char_corner_distances, int(box.up), int(box.left), cfg, ex)
         return ops.PreciseLoss.apply(precise_char_prob_feature, precise_char_up_left_corner_offset_feature,
                                      precise_char_corner_angle_feature, precise_char_corner_distance_feature,
                                      downsampled_char_prob_score_map, downsampled_char_mask,

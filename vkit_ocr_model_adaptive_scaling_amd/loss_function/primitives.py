@@ -2,6 +2,9 @@
 small HIP reduction kernel behind the reference's constructor / call signature.  Inputs live on the GPU (there is no
 CPU fallback); the result is a 0-d fp32 tensor that back-propagates into ``pred``.
 
+Every class the reference exports has a kernel except weighted BCE (``WeightedBceWithLogitsLossFunction``), which is
+off on the adaptive-scaling path (``bce_factor = 0``) and raises NotImplementedError.
+
 Differences from the reference, all deliberate: ``gt`` is never modified (dice.py:28-30 multiplies the caller's
 tensor by the mask in place, SURVEY.md App. A "aliasing bugs"), and gradients are produced for ``pred`` only.
 """
@@ -10,7 +13,7 @@ from typing import Optional
 import torch
 
 from .. import ops
-from .._lib import LOSS_FOCAL, LOSS_DICE, LOSS_L1, LOSS_SMOOTH_L1, LOSS_L2
+from .._lib import LOSS_FOCAL, LOSS_DICE, LOSS_L1, LOSS_SMOOTH_L1, LOSS_L2, LOSS_WAHR
 
 
 class FocalWithLogitsLossFunction:
@@ -87,7 +90,11 @@ class WeightedBceWithLogitsLossFunction:
 
 
 class WeightAdaptiveHeatmapRegressionLossFunction:
-    """weight_adaptive_heatmap_regression.py — inactive under the default factors (wahr_factor = 0); no HIP kernel."""
+    """weight_adaptive_heatmap_regression.py:17-32: mean of (s (1 - p) + (1 - s) p) (p - gt)^2 with s = gt^gamma;
+    ``pred`` are probabilities (the reference's callers apply the sigmoid first)."""
 
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError('WAHR is off by default on the adaptive-scaling path and has no HIP kernel')
+    def __init__(self, gamma: float = 0.01):
+        self.gamma = gamma
+
+    def __call__(self, pred: torch.Tensor, gt: torch.Tensor):
+        return ops.ElementwiseLoss.apply(pred, gt, None, LOSS_WAHR, float(self.gamma), 0.0, 0.0)
