@@ -275,6 +275,15 @@ size_t vkas_resize_bwd_ws_bytes(int B, int Hin, int Win, int Hout, int Wout, int
 int vkas_resize_bwd_ws(const void* dy, long lddy, void* dx, long lddx, float* ws, size_t ws_bytes, int B, int Hin, int Win,
                        int Hout, int Wout, int Cp, int mode, int accumulate, int dtype, void* stream);
 
+/* ---- head backward at the neck's resolution: z = conv3x3(U x), U = x2 bilinear (upernext.py:237-244) ---- */
+/* dz (B, 2h, 2w, N) bf16 / fp16 with row stride lddz -> E (B, h, w, 9 N) dense, column k * N + n:
+ * E_k[s, n] = sum_q U[q, s] * dz[q + (k - 1), n], k = (ky, kx) the tap of the dgrad convolution (the K order of the mode-1
+ * weight image), zero where q + (k - 1) leaves the map.  Then dx = E . Bt^T and dW[n][c][8 - k] = sum_s E_k[s, n] x[s, c]. */
+int vkas_upconv_adj(const void* dz, long lddz, void* E, int B, int h, int w, int N, int dtype, void* stream);
+/* gE (9 N, Cp) fp32, row k * N + n [the weight-gradient GEMM of E against x] added onto the packed gradient of the forward
+ * taps: gwp (N, 3, 3, Cp)[n][8 - k][c] += gE[k * N + n][c] */
+int vkas_upconv_adj_unpack_wgrad(const float* gE, float* gwp, int N, int Cp, void* stream);
+
 /* ---- nn.AdaptiveAvgPool2d(s): upernext.py:62 ------------------------------------------------------ */
 int vkas_adaptive_avgpool_fwd(const void* x, long ldx, void* y, long ldy, int B, int H, int W, int s, int Cp,
                               int dtype, void* stream);

@@ -130,7 +130,9 @@ _SIGS = {
     'vkas_resize_bwd_ws_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     'vkas_resize_bwd_ws': (c_int, [_P, c_long, _P, c_long, _P, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                    c_int, _P]),
-    'vkas_adaptive_avgpool_fwd': (c_int, [_P, c_long, _P, c_long, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    'vkas_upconv_adj': (c_int, [_P, c_long, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    'vkas_upconv_adj_unpack_wgrad': (c_int, [_P, _P, c_int, c_int, _P]),
+    'vkas_adaptive_avgpool_fwd':(c_int, [_P, c_long, _P, c_long, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     'vkas_adaptive_avgpool_bwd': (c_int, [_P, c_long, _P, c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     'vkas_copy_channels': (c_int, [_P, c_long, _P, c_long, c_long, c_int, c_int, c_int, _P]),
     'vkas_copy_channel_range': (c_int, [_P, c_long, c_int, _P, c_long, c_int, c_long, c_int, c_int, c_int, _P]),

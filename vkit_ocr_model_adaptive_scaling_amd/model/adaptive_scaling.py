@@ -127,8 +127,28 @@ class AdaptiveScaling(nn.Module):
         conv5x5 = getattr(plain[0], 'conv5x5', False)
         # FPN heads at factors 3 / 4: their 5x5 convolutions read the neck feature itself (ops.upconv5, folded phases) and
         # the label-point forward falls back to dense maps
+        chans, ocs = [c.out_channels for c in convs], [hp.out_channels for hp in plain]
+        # x2 bilinear heads (UperNext at the default factor): upsample + fused heads as one autograd node whose backward runs
+        # at the neck's resolution (ops.UpHeadsFused); the opt-in label-point forward reads the upsample that node returns
+        at_points = label_points is not None and torch.is_grad_enabled() and 0 < n_dense < len(heads)
+        if (isinstance(plain[0], UperNextHead) and plain[0].upsampling_factor == 2
+                and ops.UpHeadsFused.eligible(neck_feature, chans, ocs)):
+            fused = []
+            for cv, nm, proj in zip(convs, norms, projs):
+                fused.extend([cv.weight, cv.bias, nm.weight, nm.bias, proj.weight, proj.bias])
+            if at_points:
+                py, px = label_points
+                *ys, up = ops.UpHeadsFused.apply(neck_feature, True, True, *fused[:6 * n_dense])
+                ys = tuple(ys) + ops.HeadsAtPoints.apply(up, py, px, *fused[6 * n_dense:])
+            else:
+                ys = ops.UpHeadsFused.apply(neck_feature, torch.is_grad_enabled(), False, *fused)
+            outs = []
+            for h, hp, y in zip(heads, plain, ys):
+                y = ops.ToNchw.apply(y, hp.out_channels)
+                outs.append(h[1](y) if isinstance(h, nn.Sequential) else y)
+            return tuple(outs)
         up = neck_feature if conv5x5 else plain[0].upsample_act(neck_feature)
-        if not conv5x5 and ops.HeadsFused.eligible(up, [c.out_channels for c in convs], [hp.out_channels for hp in plain]):
+        if not conv5x5 and ops.HeadsFused.eligible(up, chans, ocs):
             # LayerNorm + GELU + projection run in the conv's epilogue: the per-head activations never reach HBM; the
             # heads' weights are packed side by side by the pack kernel (no torch.cat of parameters on the hot path)
             fused = []

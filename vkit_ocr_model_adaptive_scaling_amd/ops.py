@@ -1013,6 +1013,11 @@ class HeadsFused(Function):
     @staticmethod
     def forward(ctx, x, keep: bool, *params):
         """keep: torch.is_grad_enabled() at the call site (Function.forward itself always runs with grad mode off)."""
+        return HeadsFused._forward(ctx, x, None, keep, params)
+
+    @staticmethod
+    def _forward(ctx, x, x_low, keep: bool, params):
+        """x_low (UpHeadsFused): the neck feature x is the x2 bilinear upsample of; backward then runs at its resolution."""
         _require_cuda(x, params[0])
         x = as_act(x)
         n_heads = len(params) // 6
@@ -1063,8 +1068,9 @@ class HeadsFused(Function):
             conv_gemm(x, geom, Bw, Nt, z, _lib.EPI_NONE, bias=b_cat, nk=(sum(cs), C * 9))
             check(lib.vkas_head_tail_fwd(_p(z), Nt, ctypes.byref(head), M, _dt(x), _stream()), 'head_tail_fwd')
         if keep:
-            ctx.save_for_backward(x, z, stats, hp, *ws, *bs, *gammas, *betas, *wps, *bps)
+            ctx.save_for_backward(x, z, stats, hp, *ws, *bs, *gammas, *betas, *wps, *bps, *(() if x_low is None else (x_low,)))
         ctx.meta = (cs, ocs, nps, pw, C)
+        ctx.low = x_low is not None
         return tuple(proj[h] for h in range(n_heads))
 
     @staticmethod
@@ -1114,22 +1120,84 @@ class HeadsFused(Function):
         sp = _point_sparse_run(dprojs, B, H, W) if _POINT_SPARSE else None
         d0, d1 = (0, n_heads) if sp is None else ((0, sp[0]) if sp[0] > 0 else (sp[1], n_heads))
         es = x.element_size()
-        dx = new_act(B, H, W, Cp, x) if ctx.needs_input_grad[0] else None
-        if d1 > d0:
-            Nd = offs[d1] - offs[d0]
-            dz = new_act(B, H, W, Nd, x)
-            tail_bwd(d0, d1, z.data_ptr() + offs[d0] * es, Nt, stats.data_ptr() + d0 * M * 8,
-                     [dps[h].data_ptr() for h in range(d0, d1)], M, dz)
+        # low: x is the x2 bilinear upsample U of the neck feature x_low (UpHeadsFused).  The dense heads' gradients are then
+        # matrix products over the h*w rows of E (csrc/upconv_adj.hip) and dx is the gradient of x_low itself; the label-point
+        # heads scatter into an upsampled-resolution buffer that U^T (resize2x_bwd) adds onto it.
+        low = ctx.low
+        x_low = saved[4 + 6 * n_heads] if low else None
+        h_, w_ = H // 2, W // 2
+        need_dx = ctx.needs_input_grad[0]
+        dx = (new_act(B, h_, w_, Cp, x) if low else new_act(B, H, W, Cp, x)) if need_dx else None
+
+        def dense_dz(r0, r1):
+            dz = new_act(B, H, W, offs[r1] - offs[r0], x)
+            tail_bwd(r0, r1, z.data_ptr() + offs[r0] * es, Nt, stats.data_ptr() + r0 * M * 8,
+                     [dps[h].data_ptr() for h in range(r0, r1)], M, dz)
+            return dz
+
+        def dense_upres(r0, r1, dx_up):
+            """heads [r0, r1) on the convolution kernels at x's resolution; dx_up (B,H,W,Cp) is written, not added to"""
+            Nd = offs[r1] - offs[r0]
+            dz = dense_dz(r0, r1)
             geom = _geom(B, H, W, H, W, Cp, act_ld(x), 3, 3, 1, 1)
-            conv_wgrad(x, geom, dz, Nd, nk=(sum(cs[d0:d1]), C * 9), with_bias=True,
-                       gw_into=gwp[offs[d0] * K:offs[d1] * K], gb_into=gbp[offs[d0]:offs[d1]])
-            if dx is not None:
-                Bt = pack_head_weights(ws[d0:d1], nps[d0:d1], Cp, 1, x.dtype)
+            conv_wgrad(x, geom, dz, Nd, nk=(sum(cs[r0:r1]), C * 9), with_bias=True,
+                       gw_into=gwp[offs[r0] * K:offs[r1] * K], gb_into=gbp[offs[r0]:offs[r1]])
+            if dx_up is not None:
+                Bt = pack_head_weights(ws[r0:r1], nps[r0:r1], Cp, 1, x.dtype)
                 g2 = _geom(B, H, W, H, W, Nd, Nd, 3, 3, 1, 1)
-                conv_gemm(dz, g2, Bt, Cp, dx, _lib.EPI_NONE, nk=(C, sum(cs[d0:d1]) * 9))
+                conv_gemm(dz, g2, Bt, Cp, dx_up, _lib.EPI_NONE, nk=(C, sum(cs[r0:r1]) * 9))
+
+        def dense_lowres(r0, r1):
+            """heads [r0, r1) at x_low's resolution: E = U^T of the nine moved copies of dz, then two matrix products"""
+            Nd = offs[r1] - offs[r0]
+            dz = dense_dz(r0, r1)
+            E = new_act(B, h_, w_, 9 * Nd, x)
+            _timed('upconv_adj_kernel', x, 0.0, M // 4, 9 * Nd, 0,
+                   lambda: check(lib.vkas_upconv_adj(_p(dz), act_ld(dz), _p(E), B, h_, w_, Nd, _dt(x), _stream()), 'upconv_adj'),
+                   float(M) * Nd * es * 3.25)
+            # conv bias gradient: column sums of dz, as the convolution's weight-gradient kernel delivers them (the column sums
+            # of E's centre tap are the same sum, but of values rounded once more)
+            nbytes = lib.vkas_colsum_ws_bytes(M, Nd)
+            ws_cs = _ws(nbytes, dev)
+            _timed('colsum_partial_kernel', x, 0.0, M, Nd, 0,
+                   lambda: check(lib.vkas_colsum(_p(dz), act_ld(dz), M, Nd, _p(gbp[offs[r0]:offs[r1]]), 1, _p(ws_cs), nbytes,
+                                                 _dt(x), _stream()), 'colsum'), float(M) * Nd * es)
             del dz
-        elif dx is not None:
-            dx.zero_()
+            g1 = _geom(B, h_, w_, h_, w_, Cp, act_ld(x_low), 1, 1, 1, 0)
+            gE = conv_wgrad(x_low, g1, E, 9 * Nd, nk=(9 * sum(cs[r0:r1]), C), step_scratch=True)
+            check(lib.vkas_upconv_adj_unpack_wgrad(_p(gE), _p(gwp[offs[r0] * K:offs[r1] * K]), Nd, Cp, _stream()),
+                  'upconv_adj_unpack_wgrad')
+            if dx is not None:
+                Bt = pack_head_weights(ws[r0:r1], nps[r0:r1], Cp, 1, x.dtype)
+                g2 = _geom(B, h_, w_, h_, w_, 9 * Nd, 9 * Nd, 1, 1, 1, 0)
+                conv_gemm(E, g2, Bt, Cp, dx, _lib.EPI_NONE, nk=(C, sum(cs[r0:r1]) * 9))
+
+        dx_pts = dx      # where the label-point heads add their input gradient: x's resolution
+        dx_low_set = False
+        if not low:
+            if d1 > d0:
+                dense_upres(d0, d1, dx)
+            elif dx is not None:
+                dx.zero_()
+        else:
+            # A dense head whose gradient still carries a label-point mark (compact path switched off or not applicable) keeps
+            # the convolution kernels: its dz is zero off B*P rows, and the compact path it is compared with sums exactly what
+            # those kernels sum.  Such heads are a prefix or a suffix of the dense run, like the compact ones.
+            marked = [point_mark(dprojs[h]) is not None for h in range(d0, d1)]
+            plain = [d0 + i for i, m in enumerate(marked) if not m]
+            e0, e1 = (plain[0], plain[-1] + 1) if plain else (d0, d0)
+            if plain != list(range(e0, e1)) or (e0 > d0 and e1 < d1):
+                e0, e1 = d0, d0  # not one run at either end: everything on the convolution kernels
+            u0, u1 = (e1, d1) if e0 == d0 else (d0, e0)
+            dx_pts = None
+            if u1 > u0:
+                dx_pts = new_act(B, H, W, Cp, x) if need_dx else None
+                dense_upres(u0, u1, dx_pts)
+            elif sp is not None and need_dx:
+                dx_pts = torch.zeros((B, H, W, Cp), dtype=x.dtype, device=dev)
+            if e1 > e0:
+                dense_lowres(e0, e1)
+                dx_low_set = True
         if sp is not None:
             s0, s1, py, px = sp
             Ns = offs[s1] - offs[s0]
@@ -1163,8 +1231,16 @@ class HeadsFused(Function):
                 dzt = dzs.view(Mp, Ns).t().contiguous().view(1, 1, Ns, Mp)
                 g3 = _geom(1, 1, Ns, 1, Ns, K, K, 1, 1, 1, 0)
                 D = conv_wgrad(Wf, g3, dzt, Mp, nk=(B * P, C * 9), step_scratch=True, ordered=True)
-                check(lib.vkas_points_scatter3x3(_p(D), _p(pix), _p(pmap), Mp, B, H, W, Cp, _p(dx), act_ld(dx), _dt(x),
+                check(lib.vkas_points_scatter3x3(_p(D), _p(pix), _p(pmap), Mp, B, H, W, Cp, _p(dx_pts), act_ld(dx_pts), _dt(x),
                                                  _stream()), 'points_scatter3x3')
+        if low and dx is not None:
+            if dx_pts is not None:  # dx (+)= U^T dx_pts
+                _timed('resize2x_bwd_kernel', x, 0.0, M, Cp, 0,
+                       lambda: check(lib.vkas_resize_bwd(_p(dx_pts), act_ld(dx_pts), _p(dx), act_ld(dx), B, h_, w_, H, W, Cp, 0,
+                                                         int(dx_low_set), _dt(x), _stream()), 'resize_bwd'),
+                       B * Cp * es * (h_ * w_ * (2 if dx_low_set else 1) + H * W))
+            elif not dx_low_set:
+                dx.zero_()
         gws, gbs = [], []
         for h in range(n_heads):
             gslice = gwp[offs[h] * K:offs[h + 1] * K]
@@ -1213,6 +1289,54 @@ class HeadsFused(Function):
         for sk in delivered:
             sk[0].grad_delivered(sk[1])
         return (dx, None, *grads)
+
+
+_HEAD_BWD_UPRES = os.environ.get('VKAS_HEAD_BWD_UPRES') is not None  # A/B switch: head backward at the upsampled resolution
+
+
+class UpHeadsFused(Function):
+    """HeadsFused on the x2 bilinear upsample of the neck feature, as ONE autograd node: forward is Resize + HeadsFused
+    launch for launch (resize2x_fwd, then the fused head GEMM: bit-identical outputs); backward of the dense heads runs at the
+    neck's resolution.  With U the upsample, z = conv3x3(U x) and E_k = U^T (dz moved by tap k) (vkas_upconv_adj, nine maps of
+    h x w x N), the input gradient is E (M/4 x 9N) . W (9N x C) - of the neck feature directly - and the weight gradient
+    E^T . x: a quarter of the products of the two convolutions at 2h x 2w, neither dx at 2h x 2w nor its U^T pass.  Same sums,
+    other order; E is rounded to the storage type once.  VKAS_HEAD_BWD_UPRES=1 keeps Resize + HeadsFused (model side).
+
+    inputs: x (B,h,w,Cp) 16-bit with h, w > 1, keep, with_up, then the parameters of HeadsFused; outputs as HeadsFused at
+    (2h, 2w)."""
+
+    @staticmethod
+    def eligible(x, channels, out_channels) -> bool:
+        B, h, w, _ = x.shape
+        return (not _HEAD_BWD_UPRES and x.dtype in _MFMA_DTYPES and h > 1 and w > 1 and 4 * B * h * w >= 16384
+                and len(channels) <= 4 and max(rup8(c) for c in channels) <= 512 and max(out_channels) <= 4)
+
+    @staticmethod
+    def forward(ctx, x, keep: bool, with_up: bool, *params):
+        """with_up: also return the upsampled feature (last output) for another consumer - the opt-in label-point forward
+        (HeadsAtPoints) reads it; the gradient it receives goes through U^T onto dx in backward."""
+        _require_cuda(x, params[0])
+        x = as_act(x)
+        up = resize_fwd(x, (2 * x.shape[1], 2 * x.shape[2]), 0)
+        ctx.with_up = with_up
+        outs = HeadsFused._forward(ctx, up, x, keep, params)
+        return (*outs, up) if with_up else outs
+
+    @staticmethod
+    def backward(ctx, *gs):
+        d_up = None
+        if ctx.with_up:
+            gs, d_up = gs[:-1], gs[-1]
+        out = HeadsFused.backward(ctx, *gs)
+        dx = out[0]
+        if d_up is not None and dx is not None:  # dx += U^T d_up
+            d_up = as_act(d_up)
+            B, H, W, Cp = d_up.shape
+            _timed('resize2x_bwd_kernel', d_up, 0.0, B * H * W, Cp, 0,
+                   lambda: check(lib.vkas_resize_bwd(_p(d_up), act_ld(d_up), _p(dx), act_ld(dx), B, H // 2, W // 2, H, W, Cp, 0, 1,
+                                                     _dt(d_up), _stream()), 'resize_bwd'),
+                   B * Cp * d_up.element_size() * (H * W // 2 + H * W))
+        return (dx, None, None, *out[2:])
 
 
 class HeadsAtPoints(Function):
