@@ -290,6 +290,7 @@ torch.save(out, sys.argv[1])
 
 # ------------------------------------------------------------------------------------------------ ConvNeXt layer
 # (the depthwise 7x7 kernels on their own, through the C ABI: tests/test_gpu_dwconv.py)
+# (the fused MLP kernels likewise: tests/test_gpu_mlp_chain.py; here, at 256 < C <= 384 with fewer than 16384 rows, the layer runs the two-GEMM path)
 @pytest.mark.parametrize('dtype', DTYPES, ids=['f32', 'bf16', 'f16'])
 @pytest.mark.parametrize('shape', [(2, 24, 19, 37), (1, 16, 8, 8), (2, 96, 40, 33), (1, 40, 5, 3),
                                    # every instantiation of the fused MLP kernel (C <= 32 / 64 / 96 / 128 / 192 / 256 / 384 /
