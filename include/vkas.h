@@ -461,6 +461,20 @@ long vkas_char_polygons_workspace_bytes(int B, int H, int W, int size);
 int vkas_char_polygons(const float* prob, const float* offset, const float* angle, const float* dist, int B, int H, int W,
                        int size, float thr, float scale_y, float scale_x, void* workspace, size_t workspace_bytes,
                        int* count, int* points, float* probs, float* quads, void* stream);
+/* Text regions of the rough maps (the step between the passes, :190-279, restated on pixels).  mask (B,H,W) uint8 and height
+ * (B,H,W) fp32 as vkas_rough_postprocess writes them.  A region is an 8-connected component of mask != 0; the regions of each
+ * image are numbered 1..N by their first pixel in row-major order.  Outputs: count (B) = the true N of each image; labels
+ * (B,H,W) int32, 0 = background; and, with R = max_regions rows per image, row r-1 for region r <= R: boxes (B,R,4) =
+ * (y0, x0, y1, x1) inclusive, areas (B,R), valid (B,R) = the region's pixels with height > 0, medians (B,R) = the fp32 median
+ * of those heights (the middle element, (a + b) * 0.5f of the two middle ones, 0 without any) - np.median's bits.  Rows
+ * beyond an image's count are zero.  An image with N > R regions keeps its true count and labels (values above R occur)
+ * and fills R rows; nothing is written beyond them.  Capture-safe: no allocation, no synchronisation, every workspace word
+ * and table row is (re)written by the call's own kernels; integer atomics only (deterministic).  B, H, W, max_regions >= 1,
+ * B*H*W < 2^31; workspace 16-byte aligned, at least vkas_text_regions_workspace_bytes (which returns -1 on bad arguments). */
+long long vkas_text_regions_workspace_bytes(int B, int H, int W, int max_regions);
+int vkas_text_regions(const unsigned char* mask, const float* height, int B, int H, int W, int max_regions, void* workspace,
+                      long long workspace_bytes, int* count, int* labels, int* boxes, int* areas, int* valid, float* medians,
+                      void* stream);
 
 /* ---- optimizer on the flat parameter / gradient buffers: train.py:468-478 ------------------------------ */
 /* sumsq (1 double, zeroed by the call) = sum g^2 */

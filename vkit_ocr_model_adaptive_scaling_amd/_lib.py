@@ -6,7 +6,7 @@ or a symbol cannot be resolved, importing this module raises.
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int64, c_long, c_size_t, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int64, c_long, c_longlong, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # VKAS_LIB_PATH: profiling aid only (timing-only ablation builds from profiles/build_*_variants.sh)
@@ -166,6 +166,8 @@ _SIGS = {
     'vkas_char_polygons_workspace_bytes': (c_long, [c_int, c_int, c_int, c_int]),
     'vkas_char_polygons': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, _P, c_size_t,
                                    _P, _P, _P, _P, _P]),
+    'vkas_text_regions_workspace_bytes': (c_longlong, [c_int, c_int, c_int, c_int]),
+    'vkas_text_regions': (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, c_longlong, _P, _P, _P, _P, _P, _P, _P]),
     'vkas_l2norm_sq': (c_int, [_P, c_long, _P, _P]),
     'vkas_adamw_step': (c_int, [_P, _P, _P, _P, c_long, _P, c_float, c_float, c_float, c_float, c_float, c_float,
                                 c_float, c_int, _P]),

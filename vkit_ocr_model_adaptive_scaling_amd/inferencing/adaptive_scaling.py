@@ -6,7 +6,13 @@ peak (:399-465,481-491) - runs on the device too (csrc/charpoly.hip, ``precise_i
 HIP graph as the model call; ``precise_group_char_polygons`` splits its points by a caller-given region label map on the
 host (the device-free half of :467-525).
 
-Out of scope: the CPU geometry around it - rough-side regions from masks, text-region flattening /
+The step between the passes - the text regions of the rough mask, the median character height of each and the scale that
+brings it to 35 px (:190-279) - runs on the device as well (csrc/regions.hip, ``rough_infer_text_regions``), in the rough
+pass's HIP graph, restated on pixels: a region is an 8-connected component of the rough mask, not an external contour (a
+hole is not filled, a component inside a hole is a region of its own), and its axis-aligned box stands in for vkit's
+flattened region in the scale rule (inferencing/regions.py states the rule and holds the host oracle).
+
+Out of scope: the CPU geometry around it - polygons of the rough regions, text-region flattening /
 stacking, building the region label map from them and remapping polygons through the flattening (vkit, cv2; third-party
 code that is absent here).  Images are plain (H, W, 3) uint8 arrays instead of ``vkit.element.Image``; results carry
 numpy arrays instead of ``Mask`` / ``ScoreMap`` / ``Polygon``.  The reference loads a TorchScript file (``model_jit``,
@@ -23,6 +29,7 @@ import torch
 
 from .opt import pad_mat_to_make_divisible
 from .graphs import GraphCache, param_stamp
+from .regions import region_scales
 from .. import ops
 from .._lib import lib, check
 from ..model import AdaptiveScaling, AdaptiveScalingConfig
@@ -52,6 +59,12 @@ class AdaptiveScalingInferencingConfig:
     # :58-59, read by precise_infer_char_polygons (peak threshold, compared in fp32; scipy maximum_filter size, truncated)
     precise_build_polygons_positive_char_prob_thr: float = 0.7
     precise_build_polygons_maximum_filter_size: float = 5
+    # :53-54, read by rough_infer_text_regions: the median character height a text region is rescaled to, and the share of
+    # it below which a rescaled region (both sides) is dropped
+    precise_flattened_text_region_resized_char_height_median: int = 35
+    precise_flattened_text_region_resized_ratio_min: float = 0.25
+    # table rows of rough_infer_text_regions; a page with more regions reports its true count and the first rows
+    rough_text_regions_max: int = 4096
 
 
 @attrs.define
@@ -61,6 +74,23 @@ class AdaptiveScalingInferencingRoughInferResult:
     padded_image: np.ndarray
     rough_char_mask: np.ndarray              # (H/FDF, W/FDF) uint8
     rough_char_height_score_map: np.ndarray  # (H/FDF, W/FDF) float32
+
+
+@attrs.define
+class AdaptiveScalingInferencingRoughTextRegions:
+    """The text regions of one page and their scales (:190-279 on pixels, see inferencing/regions.py): region r is row
+    r - 1; N = min(num_regions, config.rough_text_regions_max) rows."""
+    resized_shape: Tuple[int, int]
+    padded_image: np.ndarray
+    num_regions: int                  # the true number of regions, also when it exceeds the table
+    labels: Optional[np.ndarray]      # (H/FDF, W/FDF) int32, 0 = background, regions 1..num_regions; None if not asked for
+    boxes: np.ndarray                 # (N, 4) int32 inclusive (y0, x0, y1, x1) in map pixels
+    areas: np.ndarray                 # (N,) int32 pixels
+    valid: np.ndarray                 # (N,) int32 pixels with a valid character height
+    char_height_medians: np.ndarray   # (N,) float32 median of the valid heights, as predicted (0 without any)
+    scales: np.ndarray                # (N,) float64, 0 for a region without a valid height
+    resized_shapes: np.ndarray        # (N, 2) int64 (height, width) of the rescaled region
+    keep: np.ndarray                  # (N,) bool: False for the regions the reference skips
 
 
 @attrs.define
@@ -187,6 +217,57 @@ class AdaptiveScalingInferencing:
         return AdaptiveScalingInferencingRoughInferResult(
             resized_shape=(math.ceil(h / fdf), math.ceil(w / fdf)), padded_image=padded,
             rough_char_mask=out_mask[0].cpu().numpy(), rough_char_height_score_map=out_height[0].cpu().numpy())
+
+    def rough_infer_text_regions(self, image, resize_fn=None,
+                                 return_labels: bool = True) -> AdaptiveScalingInferencingRoughTextRegions:
+        """The rough pass followed by the text regions of its mask, the exact median of the valid character heights of
+        each (csrc/regions.hip, in the same HIP graph) and the reference's scale rule on the host (:190-279 restated on
+        pixels, inferencing/regions.py): the region count, the table rows and - if ``return_labels`` - the int32 label map
+        cross PCIe, the mask and the height map do not.  ``image`` and ``resize_fn`` as in ``rough_infer``, whose maps this
+        labels: the result equals ``text_regions_host`` + ``region_scales`` on them."""
+        c = self.config
+        mat = _as_mat(image)
+        image_shape = mat.shape[:2]
+        h, w = rough_resized_shape(mat.shape[0], mat.shape[1], c.rough_downsample_short_side_legnth)
+        if (h, w) != mat.shape[:2]:
+            if resize_fn is None:
+                raise ValueError(f'image {mat.shape[:2]} exceeds the short-side limit {c.rough_downsample_short_side_legnth}: '
+                                 f'pass resize_fn or an image already resized to {(h, w)}')
+            mat = np.asarray(resize_fn(mat, h, w))
+            assert mat.shape[:2] == (h, w)
+        padded = pad_mat_to_make_divisible(mat, c.backbone_downsampling_factor)
+        fdf = 4 // c.rough_head_upsampling_factor
+        x = self._to_device([padded])
+        H, W = padded.shape[0] // fdf, padded.shape[1] // fdf
+        vh, vw = self._valid([(h, w)], fdf, x.device)
+        thr, hmin = float(c.rough_char_mask_positive_thr), float(c.rough_valid_char_height_min)
+        cap = int(c.rough_text_regions_max)
+
+        def rough_regions_pass(x, vh, vw):  # model call, post-processing and region table: one HIP graph per padded shape
+            mask_feat, height_feat = self.model.forward_rough(x)
+            B = mask_feat.shape[0]
+            assert tuple(mask_feat.shape) == (B, 1, H, W) and height_feat.shape == mask_feat.shape
+            out_mask = torch.empty((B, H, W), dtype=torch.uint8, device=x.device)
+            out_height = torch.empty((B, H, W), dtype=torch.float32, device=x.device)
+            check(lib.vkas_rough_postprocess(_ptr(mask_feat.contiguous()), _ptr(height_feat.contiguous()), B, H, W, _ptr(vh),
+                                             _ptr(vw), thr, hmin, _ptr(out_mask), _ptr(out_height), ops._stream()),
+                  'rough_postprocess')
+            return ops.text_regions(out_mask, out_height, cap)
+
+        with torch.no_grad():
+            count, labels, boxes, areas, valid, medians = self.graphs.run(
+                ('rough_text_regions', thr, hmin, cap), rough_regions_pass, [x, vh, vw], param_stamp(self.model))
+        num = int(count[0].item())
+        n = min(num, cap)
+        boxes, areas, valid, medians = (t[0, :n].cpu().numpy() for t in (boxes, areas, valid, medians))
+        resized_shape = (math.ceil(h / fdf), math.ceil(w / fdf))
+        scales, resized_shapes, keep = region_scales(
+            boxes, medians, image_shape, resized_shape, c.precise_flattened_text_region_resized_char_height_median,
+            c.precise_flattened_text_region_resized_ratio_min)
+        return AdaptiveScalingInferencingRoughTextRegions(
+            resized_shape=resized_shape, padded_image=padded, num_regions=num,
+            labels=labels[0].cpu().numpy() if return_labels else None, boxes=boxes, areas=areas, valid=valid,
+            char_height_medians=medians, scales=scales, resized_shapes=resized_shapes, keep=keep)
 
     # ---- precise pass --------------------------------------------------------------------------------------------
     def _precise_groups(self, images: Sequence):

@@ -2302,3 +2302,49 @@ def char_polygons(prob: torch.Tensor, offset: torch.Tensor, angle: torch.Tensor,
                                  float(scale_x), _p(ws), ws.numel(), _p(count), _p(points), _p(probs), _p(quads), _stream()),
           'char_polygons')
     return count, points, probs, quads
+
+
+def text_regions(mask: torch.Tensor, height: torch.Tensor, max_regions: int):
+    """Text regions of the rough maps and the median character height of each (the step between the two passes,
+    inferencing/adaptive_scaling.py:190-279 restated on pixels, csrc/regions.hip).  mask (B,H,W) uint8 and height (B,H,W)
+    fp32 on the device, as ``vkas_rough_postprocess`` writes them.  A region is an 8-connected component of ``mask != 0``;
+    the regions of each image are numbered 1..N by their first pixel in row-major order.  Returns device tensors ``(count,
+    labels, boxes, areas, valid, medians)`` - (B,) int32 true region counts, (B,H,W) int32 labels (0 = background), and with
+    R = ``max_regions`` rows per image (row r-1 for region r; zero beyond an image's count): (B,R,4) int32 inclusive (y0, x0,
+    y1, x1), (B,R) int32 pixel counts, (B,R) int32 counts of pixels with height > 0, (B,R) fp32 exact medians of those
+    heights (0 without any).  An image with more than R regions keeps its true count and labels and fills R rows.  Never
+    synchronises, so it can be captured into a HIP graph."""
+    if mask.dim() != 3:
+        raise ValueError(f'text_regions: mask must be (B, H, W), got {tuple(mask.shape)}')
+    B, H, W = mask.shape
+    if tuple(height.shape) != (B, H, W):
+        raise ValueError(f'text_regions: height must be {(B, H, W)}, got {tuple(height.shape)}')
+    if mask.dtype != torch.uint8:
+        raise ValueError(f'text_regions: mask must be uint8, got {mask.dtype}')
+    if height.dtype != torch.float32:
+        raise ValueError(f'text_regions: height must be float32, got {height.dtype}')
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError(f'text_regions: empty maps {(B, H, W)}')
+    R = int(max_regions)
+    if R != max_regions or R < 1:
+        raise ValueError(f'text_regions: max_regions must be an integer >= 1, got {max_regions}')
+    if B * H * W >= 1 << 31:
+        raise ValueError(f'text_regions: B*H*W = {B * H * W} must stay below 2^31')
+    _require_cuda(mask, height)
+    if mask.device != height.device:
+        raise ValueError(f'text_regions: mask is on {mask.device}, height on {height.device}')
+    mask, height = mask.contiguous(), height.contiguous()
+    dev = mask.device
+    nbytes = lib.vkas_text_regions_workspace_bytes(B, H, W, R)
+    if nbytes < 0:
+        check(-1, 'text_regions')
+    ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+    count = torch.empty((B,), dtype=torch.int32, device=dev)
+    labels = torch.empty((B, H, W), dtype=torch.int32, device=dev)
+    boxes = torch.empty((B, R, 4), dtype=torch.int32, device=dev)
+    areas = torch.empty((B, R), dtype=torch.int32, device=dev)
+    valid = torch.empty((B, R), dtype=torch.int32, device=dev)
+    medians = torch.empty((B, R), dtype=_FLOAT, device=dev)
+    check(lib.vkas_text_regions(_p(mask), _p(height), B, H, W, R, _p(ws), ws.numel(), _p(count), _p(labels), _p(boxes),
+                                _p(areas), _p(valid), _p(medians), _stream()), 'text_regions')
+    return count, labels, boxes, areas, valid, medians
