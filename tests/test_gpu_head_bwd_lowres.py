@@ -148,3 +148,19 @@ def test_up_heads_fused_gradients_within_1p5x_of_upres_path(case, dtype):
         print('%-16s lowres %.3e  upres %.3e  ratio %.2f' % (n, e_low[n], e_up[n], e_low[n] / max(e_up[n], 1e-300)))
     for n in e_low:
         assert e_low[n] <= 1.5 * e_up[n], (n, e_low[n], e_up[n])
+
+
+@pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16], ids=['bf16', 'f16'])
+@pytest.mark.parametrize('case', [c for c in HEAD_CASES if c[2]], ids=lambda c: 'c%s_oc%s' % ('-'.join(map(str, c[0])),
+                                                                                                '-'.join(map(str, c[1]))))
+def test_up_heads_fused_gradients_within_1p5x_of_upres_path_compact_path_off(case, dtype):
+    """The label-point cases with the compact path switched off (VKAS_POINT_SPARSE_BWD=0): the marked heads stay dense and keep
+    the convolution kernels, the unmarked head takes the neck-resolution path, and both input gradients meet in the U^T add.
+    Same shapes, same fp64 reference, same criterion."""
+    ops = ops_mod()
+    old = ops._POINT_SPARSE
+    ops._POINT_SPARSE = False
+    try:
+        test_up_heads_fused_gradients_within_1p5x_of_upres_path(case, dtype)
+    finally:
+        ops._POINT_SPARSE = old

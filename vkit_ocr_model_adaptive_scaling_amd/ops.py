@@ -7,6 +7,7 @@ the consumer side.  Parameters stay fp32 in the reference's own layouts; each op
 needs with the pack kernels.  Every op launches on torch's current HIP stream and allocates through
 torch's caching allocator; nothing here falls back to torch math or to the CPU.
 """
+import copy
 import ctypes
 import os
 import weakref
@@ -392,8 +393,6 @@ def _timed(kind, x, flops, M, N, K, fn, nbytes=0.0):
 def conv_gemm(x: torch.Tensor, geom: ConvGeom, Bw: torch.Tensor, Np: int, out: torch.Tensor, mode=_lib.EPI_NONE,
               bias=None, out2=None, aux=None, colscale=None, rowscale=None, rows_per_image=0, patch=0, patch_hw=(0, 0),
               patch_Cp=0, nk=None, head=None):
-    if head is not None:
-        assert TIMER is None or True
     if TIMER is not None:
         # algorithmic FLOPs use the logical (unpadded) N and K when the caller knows them
         M = geom.B * geom.Hout * geom.Wout
@@ -437,6 +436,17 @@ def grad_sink(param: Optional[torch.Tensor]):
     return s if s is not None and s[0].grad_view_ok(s[1]) else None
 
 
+def _accumulate_pieces(pieces):
+    """pieces: [(source address, destination address, fp32 count)]; destination += source, 16 pieces per launch"""
+    for i in range(0, len(pieces), 16):
+        part = pieces[i:i + 16]
+        n = len(part)
+        src = (ctypes.c_void_p * n)(*[a for a, _, _ in part])
+        dst = (ctypes.c_void_p * n)(*[b for _, b, _ in part])
+        cnt = (ctypes.c_int * n)(*[c for _, _, c in part])
+        check(lib.vkas_accumulate_many(n, src, dst, cnt, _stream()), 'accumulate_many')
+
+
 def deliver_small_grads(pairs):
     """pairs: [(parameter, gradient tensor or None)].  Gradients of parameters with a flat .grad view (grad_sink) are
     added onto it by ONE vkas_accumulate_many launch and reported as delivered; returns the list to hand to autograd
@@ -449,13 +459,7 @@ def deliver_small_grads(pairs):
         else:
             todo.append((s, param, g.contiguous()))
             out.append(None)
-    for i in range(0, len(todo), 16):
-        part = todo[i:i + 16]
-        n = len(part)
-        src = (ctypes.c_void_p * n)(*[g.data_ptr() for _, _, g in part])
-        dst = (ctypes.c_void_p * n)(*[p.grad.data_ptr() for _, p, _ in part])
-        cnt = (ctypes.c_int * n)(*[g.numel() for _, _, g in part])
-        check(lib.vkas_accumulate_many(n, src, dst, cnt, _stream()), 'accumulate_many')
+    _accumulate_pieces([(g.data_ptr(), p.grad.data_ptr(), g.numel()) for _, p, g in todo])
     for s, _, _ in todo:
         s[0].grad_delivered(s[1])
     return out
@@ -992,6 +996,250 @@ def pack_head_bias(bs: Sequence[torch.Tensor], cs: Sequence[int], nps: Sequence[
     return _cached_pack_multi(list(bs), key, build)
 
 
+class _HeadSet:
+    """The heads of one fused pass (HeadsFused, UpHeadsFused, HeadsAtPoints), from the flat parameter tuple: per head conv
+    weight (c_h, C, 3, 3), conv bias, gamma, beta, wproj (oc_h, c_h), bproj.  Head h owns the columns [offs[h], offs[h + 1])
+    of the Nt stacked output channels (np_h = c_h rounded up to a multiple of 8)."""
+
+    def __init__(self, params, Cp: int):
+        self.ws, self.bs = params[0::6], params[1::6]
+        self.gammas, self.betas, self.wps, self.bps = params[2::6], params[3::6], params[4::6], params[5::6]
+        self.n = len(self.ws)
+        self.cs = [g.numel() for g in self.gammas]
+        self.ocs = [w.shape[0] for w in self.wps]
+        self.nps = [rup8(c) for c in self.cs]
+        self.offs = [sum(self.nps[:h]) for h in range(self.n + 1)]
+        self.Nt, self.C, self.Cp = self.offs[-1], self.ws[0].shape[1], Cp
+        assert all(tuple(w.shape) == (c, self.C, 3, 3) for w, c in zip(self.ws, self.cs)) and Cp == rup8(self.C)
+
+    def desc(self, h0: int, h1: int, pw: int, params_ptr, stats_ptr, proj_ptr) -> _lib.HeadDesc:
+        """HeadDesc of the heads [h0, h1), their columns counted from offs[h0]"""
+        head = _lib.HeadDesc()
+        head.n_heads, head.pw = h1 - h0, pw
+        for j, h in enumerate(range(h0, h1)):
+            head.n0[j], head.np[j], head.c[j], head.oc[j] = self.offs[h] - self.offs[h0], self.nps[h], self.cs[h], self.ocs[h]
+        head.params, head.stats, head.proj = params_ptr, stats_ptr, proj_ptr
+        return head
+
+    def packed_params(self, pw: int) -> torch.Tensor:
+        """(n, 6 pw + 8) fp32: per head gamma | beta | four projection rows | projection bias, each pw wide"""
+        def build():
+            t = torch.empty((self.n, 6 * pw + 8), dtype=_FLOAT, device=self.ws[0].device)
+            for h in range(self.n):
+                check(lib.vkas_pack_head_params(_p(self.gammas[h].contiguous()), _p(self.betas[h].contiguous()),
+                                                _p(self.wps[h].contiguous()), _p(self.bps[h].contiguous()), self.cs[h],
+                                                self.ocs[h], pw, _p(t[h]), _stream()), 'pack_head_params')
+            return t
+        return _cached_pack_multi([*self.gammas, *self.betas, *self.wps, *self.bps], ('head_params', pw), build)
+
+    def weights(self, mode: int, dtype: torch.dtype, h0: int = 0, h1: Optional[int] = None) -> torch.Tensor:
+        return pack_head_weights(self.ws[h0:h1], self.nps[h0:h1], self.Cp, mode, dtype)
+
+    def bias(self) -> torch.Tensor:
+        return pack_head_bias(self.bs, self.cs, self.nps)
+
+    def saved(self, small: bool = True):
+        """the parameters in the order they go into save_for_backward; small: the affine and projection ones too"""
+        return (*self.ws, *self.bs, *((*self.gammas, *self.betas, *self.wps, *self.bps) if small else ()))
+
+    def from_saved(self, tensors) -> '_HeadSet':
+        """this head set around the parameters as autograd hands them back (the tail of ctx.saved_tensors from saved() on)"""
+        n, hs = self.n, copy.copy(self)
+        hs.ws, hs.bs = tensors[:n], tensors[n:2 * n]
+        if len(tensors) >= 6 * n:
+            hs.gammas, hs.betas, hs.wps, hs.bps = (tensors[i * n:(i + 1) * n] for i in range(2, 6))
+        return hs
+
+    def small_grad_views(self, h: int, pw: int, d: torch.Tensor, gbp: torch.Tensor):
+        """head h's small gradients - conv bias, gamma, beta, projection weight, projection bias - as views of the packed
+        bias gradient gbp (Nt,) and of the head's row d of vkas_head_tail_bwd's dparams"""
+        c, oc, o = self.cs[h], self.ocs[h], self.offs[h]
+        return [gbp[o:o + c], d[:c], d[pw:pw + c], d[2 * pw:6 * pw].view(4, pw)[:oc, :c], d[6 * pw:6 * pw + oc]]
+
+
+def _head_bwd_plan(n_heads: int, sp_range, marked, low: bool):
+    """The heads' backward paths as ranges (compact, upres, lowres), each (a, b) and possibly empty.  sp_range: None or the
+    (s0, s1) of _point_sparse_run, the compact label-point rows; the other heads are the dense run.  It takes the convolution
+    kernels at the upsampled resolution (upres); with ``low`` (UpHeadsFused) its heads without a valid label-point mark take the
+    matrix products at the neck's resolution (lowres), if they are a prefix or a suffix of it.  A marked dense head (compact path
+    off or not applicable) keeps the convolution kernels: its dz is zero off B*P rows, and they sum what the compact path sums."""
+    s0, s1 = sp_range if sp_range is not None else (0, 0)
+    d0, d1 = (0, n_heads) if sp_range is None else ((0, s0) if s0 > 0 else (s1, n_heads))
+    e0, e1 = d0, d0
+    if low:
+        plain = [h for h in range(d0, d1) if not marked[h]]
+        if plain:
+            e0, e1 = plain[0], plain[-1] + 1
+        if plain != list(range(e0, e1)) or (e0 > d0 and e1 < d1):
+            e0, e1 = d0, d0  # not one run at either end: everything on the convolution kernels
+    return (s0, s1), ((e1, d1) if e0 == d0 else (d0, e0)), (e0, e1)
+
+
+def _points_prepare(py: torch.Tensor, px: torch.Tensor, B: int, H: int, W: int):
+    """(scratch, pmap, pix, Mp): pixel -> point map (M,) and the points' pixels (Mp = B*P rounded up to 64), views of scratch"""
+    P = py.shape[1]
+    M, Mp = B * H * W, -(-(B * P) // 64) * 64
+    scratch = torch.empty((M + Mp,), dtype=torch.int32, device=py.device)
+    pmap, pix = scratch[:M], scratch[M:]
+    check(lib.vkas_points_prepare(_p(py), _p(px), B, P, H, W, _p(pmap), _p(pix), Mp, _stream()), 'points_prepare')
+    return scratch, pmap, pix, Mp
+
+
+def _points_gather_patches(x: torch.Tensor, pix: torch.Tensor, Mp: int) -> torch.Tensor:
+    """(1, 1, Mp, 9 Cp): the 3x3 patches of x (B,H,W,Cp) around the pixels pix"""
+    B, H, W, Cp = x.shape
+    xs = new_act(1, 1, Mp, 9 * Cp, x)
+    check(lib.vkas_points_gather_patches(_p(x), act_ld(x), Cp, B, H, W, _p(pix), Mp, _p(xs), _dt(x), _stream()),
+          'points_gather_patches')
+    return xs
+
+
+def _head_tail_bwd(heads, h0, h1, pw, hp, z_ptr, ldz, stats_ptr, dp_ptrs, rows, dz, dparams):
+    """vkas_head_tail_bwd for heads [h0, h1) whose z columns start at z_ptr: dz (rows, width) and dparams[h0:h1]."""
+    PS = 6 * pw + 8
+    head = heads.desc(h0, h1, pw, hp.data_ptr() + h0 * PS * 4, stats_ptr, None)
+    ptrs = (ctypes.c_void_p * 4)(*dp_ptrs)
+    nbytes = lib.vkas_head_tail_bwd_ws_bytes(rows, pw)
+    ws_buf = _ws(nbytes, dz.device)
+    width = heads.offs[h1] - heads.offs[h0]
+    _timed('head_tail_bwd_kernel', dz, 0.0, rows, width, 0,
+           lambda: check(lib.vkas_head_tail_bwd(ctypes.c_void_p(z_ptr), ldz, ctypes.byref(head), ptrs, _p(dz), width,
+                                                ctypes.c_void_p(dparams.data_ptr() + h0 * PS * 4), _p(ws_buf), nbytes,
+                                                rows, _dt(dz), _stream()), 'head_tail_bwd'),
+           float(rows) * (2 * width * dz.element_size() + (h1 - h0) * 40))
+
+
+def _heads_dense_dz(heads, r0, r1, pw, hp, x, z, stats, dps, dparams):
+    """dz (B,H,W,width) of the heads [r0, r1) from the dense z, the row statistics and the output gradients dps"""
+    B, H, W, _ = x.shape
+    M = B * H * W
+    dz = new_act(B, H, W, heads.offs[r1] - heads.offs[r0], x)
+    _head_tail_bwd(heads, r0, r1, pw, hp, z.data_ptr() + heads.offs[r0] * x.element_size(), heads.Nt,
+                   stats.data_ptr() + r0 * M * 8, [dps[h].data_ptr() for h in range(r0, r1)], M, dz, dparams)
+    return dz
+
+
+def _heads_dense_upres(heads, r0, r1, pw, hp, x, z, stats, dps, dparams, gwp, gbp, dx_up):
+    """heads [r0, r1) on the convolution kernels at x's resolution: weight / bias gradient into their slices of gwp / gbp;
+    dx_up (B,H,W,Cp) or None is written, not added to"""
+    B, H, W, Cp = x.shape
+    offs, K, C = heads.offs, 9 * Cp, heads.C
+    Nd = offs[r1] - offs[r0]
+    dz = _heads_dense_dz(heads, r0, r1, pw, hp, x, z, stats, dps, dparams)
+    geom = _geom(B, H, W, H, W, Cp, act_ld(x), 3, 3, 1, 1)
+    conv_wgrad(x, geom, dz, Nd, nk=(sum(heads.cs[r0:r1]), C * 9), with_bias=True,
+               gw_into=gwp[offs[r0] * K:offs[r1] * K], gb_into=gbp[offs[r0]:offs[r1]])
+    if dx_up is not None:
+        Bt = heads.weights(1, x.dtype, r0, r1)
+        g2 = _geom(B, H, W, H, W, Nd, Nd, 3, 3, 1, 1)
+        conv_gemm(dz, g2, Bt, Cp, dx_up, _lib.EPI_NONE, nk=(C, sum(heads.cs[r0:r1]) * 9))
+
+
+def _heads_dense_lowres(heads, r0, r1, pw, hp, x, z, stats, dps, dparams, gwp, gbp, x_low, dx):
+    """heads [r0, r1) at x_low's resolution (x is its x2 bilinear upsample): E = U^T of the nine moved copies of dz, then two
+    matrix products; dx (B,h,w,Cp) or None, the gradient of x_low itself, is written, not added to"""
+    B, H, W, Cp = x.shape
+    h_, w_, M = H // 2, W // 2, B * H * W
+    offs, K, C, es = heads.offs, 9 * Cp, heads.C, x.element_size()
+    Nd = offs[r1] - offs[r0]
+    dz = _heads_dense_dz(heads, r0, r1, pw, hp, x, z, stats, dps, dparams)
+    E = new_act(B, h_, w_, 9 * Nd, x)
+    _timed('upconv_adj_kernel', x, 0.0, M // 4, 9 * Nd, 0,
+           lambda: check(lib.vkas_upconv_adj(_p(dz), act_ld(dz), _p(E), B, h_, w_, Nd, _dt(x), _stream()), 'upconv_adj'),
+           float(M) * Nd * es * 3.25)
+    # conv bias gradient: column sums of dz, as the convolution's weight-gradient kernel delivers them (the column sums
+    # of E's centre tap are the same sum, but of values rounded once more)
+    nbytes = lib.vkas_colsum_ws_bytes(M, Nd)
+    ws_cs = _ws(nbytes, x.device)
+    _timed('colsum_partial_kernel', x, 0.0, M, Nd, 0,
+           lambda: check(lib.vkas_colsum(_p(dz), act_ld(dz), M, Nd, _p(gbp[offs[r0]:offs[r1]]), 1, _p(ws_cs), nbytes,
+                                         _dt(x), _stream()), 'colsum'), float(M) * Nd * es)
+    del dz
+    g1 = _geom(B, h_, w_, h_, w_, Cp, act_ld(x_low), 1, 1, 1, 0)
+    gE = conv_wgrad(x_low, g1, E, 9 * Nd, nk=(9 * sum(heads.cs[r0:r1]), C), step_scratch=True)
+    check(lib.vkas_upconv_adj_unpack_wgrad(_p(gE), _p(gwp[offs[r0] * K:offs[r1] * K]), Nd, Cp, _stream()),
+          'upconv_adj_unpack_wgrad')
+    if dx is not None:
+        Bt = heads.weights(1, x.dtype, r0, r1)
+        g2 = _geom(B, h_, w_, h_, w_, 9 * Nd, 9 * Nd, 1, 1, 1, 0)
+        conv_gemm(E, g2, Bt, Cp, dx, _lib.EPI_NONE, nk=(C, sum(heads.cs[r0:r1]) * 9))
+
+
+def _heads_points_grads(heads, h0, h1, pw, hp, patches, zs, stats_s, dp_ptrs, pix, pmap, n_points, dparams, gw_into, gb_into,
+                        step_scratch, dx_into):
+    """Backward of the heads [h0, h1) on compact label-point rows: zs (1,1,Mp,Ns) their z, stats_s their row statistics, dp_ptrs
+    their gathered (Mp, 8) output gradients; patches (1,1,Mp,9 Cp) the 3x3 input patches at the points, or a function that
+    gathers them (called after the tail backward).  Returns the packed (weight, bias) gradient - accumulated into gw_into /
+    gb_into when given, else a fresh buffer (step_scratch: see conv_wgrad); dx_into (B,H,W,Cp) or None receives the input
+    gradient, summed per touched pixel on top of what it holds."""
+    Mp, Ns, K, C = zs.shape[2], zs.shape[3], 9 * heads.Cp, heads.C
+    dzs = new_act(1, 1, Mp, Ns, zs)
+    _head_tail_bwd(heads, h0, h1, pw, hp, zs.data_ptr(), Ns, stats_s.data_ptr(), dp_ptrs, Mp, dzs, dparams)
+    # weight / bias gradient: (Ns x Mp) . (Mp x 9 Cp) on the gathered 3x3 patches
+    xs = patches() if callable(patches) else patches
+    g1 = _geom(1, 1, Mp, 1, Mp, K, K, 1, 1, 1, 0)
+    gw, gb = conv_wgrad(xs, g1, dzs, Ns, nk=(sum(heads.cs[h0:h1]), C * 9), with_bias=True, gw_into=gw_into, gb_into=gb_into,
+                        step_scratch=step_scratch)
+    if dx_into is not None:
+        # input gradient: D (Mp x 9 Cp, fp32) = dz_s . W with W (Ns x 9 Cp) the rows of the forward weight image -
+        # the reduction runs over W's ROWS, i.e. this is the weight-gradient GEMM shape with dz_s^T as the "dy"
+        # operand (fp32 result, no 16-bit rounding of the per-tap terms) - then summed per touched pixel onto dx_into
+        B, H, W, Cp = dx_into.shape
+        Wf = heads.weights(0, zs.dtype)[heads.offs[h0] * K:heads.offs[h1] * K].view(1, 1, Ns, K)
+        dzt = dzs.view(Mp, Ns).t().contiguous().view(1, 1, Ns, Mp)
+        g3 = _geom(1, 1, Ns, 1, Ns, K, K, 1, 1, 1, 0)
+        D = conv_wgrad(Wf, g3, dzt, Mp, nk=(n_points, C * 9), step_scratch=True, ordered=True)
+        check(lib.vkas_points_scatter3x3(_p(D), _p(pix), _p(pmap), Mp, B, H, W, Cp, _p(dx_into), act_ld(dx_into), _dt(zs),
+                                         _stream()), 'points_scatter3x3')
+    return gw, gb
+
+
+def _deliver_head_weight_grads(heads, gwp, K):
+    """per head the 3x3 weight gradient out of the packed (Nt, K) image gwp: unpacked straight into the flat gradient view and
+    reported as delivered (None in the returned list), else the unpacked tensor for autograd"""
+    gws = []
+    for h in range(heads.n):
+        sw = grad_sink(heads.ws[h])
+        g = unpack_wgrad(gwp[heads.offs[h] * K:heads.offs[h + 1] * K], (heads.cs[h], heads.C, 3, 3), heads.nps[h], heads.Cp,
+                         into=heads.ws[h].grad if sw is not None else None)
+        if sw is not None:
+            sw[0].grad_delivered(sw[1])
+        gws.append(None if sw is not None else g)
+    return gws
+
+
+def _deliver_head_small_grads(heads, pw, dparams, gbp, flat_sinks):
+    """The heads' small gradients (conv bias, LayerNorm affine, projection), per head in parameter order: with flat .grad views
+    they are added in place by vkas_accumulate_many, 16 contiguous pieces per launch (a projection weight row by row), instead
+    of one autograd add per parameter (30 launches per step) - None in the returned lists; else the tensor for autograd."""
+    outs, pieces, delivered = [], [], []
+    for h in range(heads.n):
+        c, oc = heads.cs[h], heads.ocs[h]
+        out, views = [], heads.small_grad_views(h, pw, dparams[h], gbp)
+        for j, (param, g) in enumerate(zip((heads.bs[h], heads.gammas[h], heads.betas[h], heads.wps[h], heads.bps[h]), views)):
+            sk = grad_sink(param)
+            if sk is None or not param.grad.is_contiguous():
+                # handed to autograd: never a view of the step's zero arena (see conv_param_grads)
+                out.append(g.clone() if (flat_sinks and j == 0) else g)
+                continue
+            if g.dim() == 2:  # projection weight: its oc rows lie pw apart
+                pieces.extend((g.data_ptr() + 4 * q * pw, param.grad.data_ptr() + 4 * q * c, c) for q in range(oc))
+            else:
+                pieces.append((g.data_ptr(), param.grad.data_ptr(), g.numel()))
+            delivered.append(sk)
+            out.append(None)
+        outs.append(out)
+    _accumulate_pieces(pieces)
+    for sk in delivered:
+        sk[0].grad_delivered(sk[1])
+    return outs
+
+
+def _heads_eligible(dtype, M: int, channels, out_channels) -> bool:
+    return (dtype in _MFMA_DTYPES and M >= 16384 and len(channels) <= 4 and max(rup8(c) for c in channels) <= 512
+            and max(out_channels) <= 4)
+
+
 class HeadsFused(Function):
     """All heads of a pass (model/upernext.py:215-223 or model/fpn.py:165-183, shared upsampled input) as ONE implicit
     GEMM whose epilogue applies each head's LayerNorm -> GELU -> Linear(C -> out_channels) per pixel: forward writes
@@ -1006,9 +1254,7 @@ class HeadsFused(Function):
 
     @staticmethod
     def eligible(x, channels, out_channels) -> bool:
-        M = x.shape[0] * x.shape[1] * x.shape[2]
-        return (x.dtype in _MFMA_DTYPES and M >= 16384 and len(channels) <= 4 and max(rup8(c) for c in channels) <= 512
-                and max(out_channels) <= 4)
+        return _heads_eligible(x.dtype, x.shape[0] * x.shape[1] * x.shape[2], channels, out_channels)
 
     @staticmethod
     def forward(ctx, x, keep: bool, *params):
@@ -1020,192 +1266,72 @@ class HeadsFused(Function):
         """x_low (UpHeadsFused): the neck feature x is the x2 bilinear upsample of; backward then runs at its resolution."""
         _require_cuda(x, params[0])
         x = as_act(x)
-        n_heads = len(params) // 6
-        ws, bs = params[0::6], params[1::6]
-        gammas, betas, wps, bps = params[2::6], params[3::6], params[4::6], params[5::6]
-        cs = [g.numel() for g in gammas]
-        ocs = [w.shape[0] for w in wps]
-        nps = [rup8(c) for c in cs]
-        Nt = sum(nps)
         B, H, W, Cp = x.shape
-        C = ws[0].shape[1]
-        assert all(tuple(w.shape) == (c, C, 3, 3) for w, c in zip(ws, cs)) and Cp == rup8(C)
-        M = B * H * W
-        wmax = max(nps)
+        heads = _HeadSet(params, Cp)
+        n_heads, Nt, C = heads.n, heads.Nt, heads.C
+        M, wmax, dev = B * H * W, max(heads.nps), x.device
         # up to 224 columns the tail runs in the convolution's epilogue (one 256 x pw tile per head); wider heads
         # (ConvNeXt-Base / Large) take the plain epilogue + vkas_head_tail_fwd over z
         in_epilogue = wmax <= 224
         pw = (128 if wmax <= 128 else (192 if wmax <= 192 else 224)) if in_epilogue else wmax
-        dev = x.device
-
-        def build_hp():
-            t = torch.empty((n_heads, 6 * pw + 8), dtype=_FLOAT, device=dev)
-            for h in range(n_heads):
-                check(lib.vkas_pack_head_params(_p(gammas[h].contiguous()), _p(betas[h].contiguous()),
-                                                _p(wps[h].contiguous()), _p(bps[h].contiguous()), cs[h], ocs[h], pw,
-                                                _p(t[h]), _stream()), 'pack_head_params')
-            return t
-
-        hp = _cached_pack_multi(list(gammas) + list(betas) + list(wps) + list(bps), ('head_params', pw), build_hp)
-        b_cat = pack_head_bias(bs, cs, nps)
+        hp = heads.packed_params(pw)
+        b_cat = heads.bias()
         # z and the row statistics only serve the backward pass: an inference (no-grad) call does not write them
         # (the wide-head path needs z as the tail kernel's input either way)
         z = new_act(B, H, W, Nt, x) if (keep or not in_epilogue) else None
         stats = torch.empty((n_heads, M, 2), dtype=_FLOAT, device=dev) if keep else None
         proj = torch.empty((n_heads, B, H, W, 8), dtype=_FLOAT, device=dev)
-        head = _lib.HeadDesc()
-        head.n_heads, head.pw = n_heads, pw
-        off = 0
-        for h in range(n_heads):
-            head.n0[h], head.np[h], head.c[h], head.oc[h] = off, nps[h], cs[h], ocs[h]
-            off += nps[h]
-        head.params, head.stats, head.proj = hp.data_ptr(), stats.data_ptr() if keep else None, proj.data_ptr()
+        head = heads.desc(0, n_heads, pw, hp.data_ptr(), stats.data_ptr() if keep else None, proj.data_ptr())
         geom = _geom(B, H, W, H, W, Cp, act_ld(x), 3, 3, 1, 1)
-        Bw = pack_head_weights(ws, nps, Cp, 0, x.dtype)
+        Bw = heads.weights(0, x.dtype)
         if in_epilogue:
-            conv_gemm(x, geom, Bw, Nt, z, _lib.EPI_HEAD, bias=b_cat, nk=(sum(cs), C * 9), head=head)
+            conv_gemm(x, geom, Bw, Nt, z, _lib.EPI_HEAD, bias=b_cat, nk=(sum(heads.cs), C * 9), head=head)
         else:
-            conv_gemm(x, geom, Bw, Nt, z, _lib.EPI_NONE, bias=b_cat, nk=(sum(cs), C * 9))
+            conv_gemm(x, geom, Bw, Nt, z, _lib.EPI_NONE, bias=b_cat, nk=(sum(heads.cs), C * 9))
             check(lib.vkas_head_tail_fwd(_p(z), Nt, ctypes.byref(head), M, _dt(x), _stream()), 'head_tail_fwd')
         if keep:
-            ctx.save_for_backward(x, z, stats, hp, *ws, *bs, *gammas, *betas, *wps, *bps, *(() if x_low is None else (x_low,)))
-        ctx.meta = (cs, ocs, nps, pw, C)
-        ctx.low = x_low is not None
+            ctx.save_for_backward(x, z, stats, hp, *heads.saved(), *(() if x_low is None else (x_low,)))
+        ctx.heads, ctx.pw, ctx.low = heads, pw, x_low is not None
         return tuple(proj[h] for h in range(n_heads))
 
     @staticmethod
     def backward(ctx, *dprojs):
-        cs, ocs, nps, pw, C = ctx.meta
-        n_heads = len(cs)
         saved = ctx.saved_tensors
         x, z, stats, hp = saved[:4]
-        ws, bs = saved[4:4 + n_heads], saved[4 + n_heads:4 + 2 * n_heads]
+        pw, n_heads = ctx.pw, ctx.heads.n
+        heads = ctx.heads.from_saved(saved[4:4 + 6 * n_heads])
         B, H, W, Cp = x.shape
-        Nt = z.shape[3]
-        M = B * H * W
-        K = 9 * Cp
-        dev = x.device
-        PS = 6 * pw + 8
-        offs = [sum(nps[:h]) for h in range(n_heads + 1)]
-        dparams = torch.empty((n_heads, PS), dtype=_FLOAT, device=dev)
+        Nt, M, K, dev = heads.Nt, B * H * W, 9 * Cp, x.device
+        dparams = torch.empty((n_heads, 6 * pw + 8), dtype=_FLOAT, device=dev)
         # packed weight gradient | bias gradient; with flat gradient sinks both are unpacked / added into the sinks below
-        flat_sinks = all(grad_sink(p) is not None for p in list(ws) + list(bs))
+        flat_sinks = all(grad_sink(p) is not None for p in list(heads.ws) + list(heads.bs))
         gbuf = zeros_f32(Nt * K + Nt, dev, flat_sinks)
         gwp, gbp = gbuf[:Nt * K], gbuf[Nt * K:]
-        dps = []
-        for h in range(n_heads):
-            dp = dprojs[h]
-            dps.append(torch.zeros((B, H, W, 8), dtype=_FLOAT, device=dev) if dp is None else dp.contiguous().float())
-
-        def tail_bwd(h0, h1, z_ptr, ldz, stats_ptr, dp_ptrs, rows, dz):
-            """vkas_head_tail_bwd for heads [h0, h1) whose z columns start at z_ptr: dz (rows, width) and dparams[h0:h1]."""
-            head = _lib.HeadDesc()
-            head.n_heads, head.pw = h1 - h0, pw
-            ptrs = (ctypes.c_void_p * 4)()
-            for j, h in enumerate(range(h0, h1)):
-                head.n0[j], head.np[j], head.c[j], head.oc[j] = offs[h] - offs[h0], nps[h], cs[h], ocs[h]
-                ptrs[j] = dp_ptrs[j]
-            head.params, head.stats, head.proj = hp.data_ptr() + h0 * PS * 4, stats_ptr, None
-            nbytes = lib.vkas_head_tail_bwd_ws_bytes(rows, pw)
-            ws_buf = _ws(nbytes, dev)
-            width = offs[h1] - offs[h0]
-            _timed('head_tail_bwd_kernel', x, 0.0, rows, width, 0,
-                   lambda: check(lib.vkas_head_tail_bwd(ctypes.c_void_p(z_ptr), ldz, ctypes.byref(head), ptrs, _p(dz), width,
-                                                        ctypes.c_void_p(dparams.data_ptr() + h0 * PS * 4), _p(ws_buf), nbytes,
-                                                        rows, _dt(x), _stream()), 'head_tail_bwd'),
-                   float(rows) * (2 * width * x.element_size() + (h1 - h0) * 40))
-
-        # Heads whose gradient arrives from a label-point loss (PreciseLoss marks it, see point_sparse) have B*P non-zero
-        # rows: they take the compact path below and only the remaining heads pay for the dense backward.
+        dps = [torch.zeros((B, H, W, 8), dtype=_FLOAT, device=dev) if dp is None else dp.contiguous().float() for dp in dprojs]
+        # heads whose gradient a label-point loss marked (point_sparse) have B*P non-zero rows: they take the compact path
         sp = _point_sparse_run(dprojs, B, H, W) if _POINT_SPARSE else None
-        d0, d1 = (0, n_heads) if sp is None else ((0, sp[0]) if sp[0] > 0 else (sp[1], n_heads))
-        es = x.element_size()
         # low: x is the x2 bilinear upsample U of the neck feature x_low (UpHeadsFused).  The dense heads' gradients are then
         # matrix products over the h*w rows of E (csrc/upconv_adj.hip) and dx is the gradient of x_low itself; the label-point
         # heads scatter into an upsampled-resolution buffer that U^T (resize2x_bwd) adds onto it.
-        low = ctx.low
+        low, h_, w_ = ctx.low, H // 2, W // 2
         x_low = saved[4 + 6 * n_heads] if low else None
-        h_, w_ = H // 2, W // 2
+        (s0, s1), (u0, u1), (e0, e1) = _head_bwd_plan(n_heads, sp and sp[:2], [point_mark(d) is not None for d in dprojs], low)
         need_dx = ctx.needs_input_grad[0]
         dx = (new_act(B, h_, w_, Cp, x) if low else new_act(B, H, W, Cp, x)) if need_dx else None
-
-        def dense_dz(r0, r1):
-            dz = new_act(B, H, W, offs[r1] - offs[r0], x)
-            tail_bwd(r0, r1, z.data_ptr() + offs[r0] * es, Nt, stats.data_ptr() + r0 * M * 8,
-                     [dps[h].data_ptr() for h in range(r0, r1)], M, dz)
-            return dz
-
-        def dense_upres(r0, r1, dx_up):
-            """heads [r0, r1) on the convolution kernels at x's resolution; dx_up (B,H,W,Cp) is written, not added to"""
-            Nd = offs[r1] - offs[r0]
-            dz = dense_dz(r0, r1)
-            geom = _geom(B, H, W, H, W, Cp, act_ld(x), 3, 3, 1, 1)
-            conv_wgrad(x, geom, dz, Nd, nk=(sum(cs[r0:r1]), C * 9), with_bias=True,
-                       gw_into=gwp[offs[r0] * K:offs[r1] * K], gb_into=gbp[offs[r0]:offs[r1]])
-            if dx_up is not None:
-                Bt = pack_head_weights(ws[r0:r1], nps[r0:r1], Cp, 1, x.dtype)
-                g2 = _geom(B, H, W, H, W, Nd, Nd, 3, 3, 1, 1)
-                conv_gemm(dz, g2, Bt, Cp, dx_up, _lib.EPI_NONE, nk=(C, sum(cs[r0:r1]) * 9))
-
-        def dense_lowres(r0, r1):
-            """heads [r0, r1) at x_low's resolution: E = U^T of the nine moved copies of dz, then two matrix products"""
-            Nd = offs[r1] - offs[r0]
-            dz = dense_dz(r0, r1)
-            E = new_act(B, h_, w_, 9 * Nd, x)
-            _timed('upconv_adj_kernel', x, 0.0, M // 4, 9 * Nd, 0,
-                   lambda: check(lib.vkas_upconv_adj(_p(dz), act_ld(dz), _p(E), B, h_, w_, Nd, _dt(x), _stream()), 'upconv_adj'),
-                   float(M) * Nd * es * 3.25)
-            # conv bias gradient: column sums of dz, as the convolution's weight-gradient kernel delivers them (the column sums
-            # of E's centre tap are the same sum, but of values rounded once more)
-            nbytes = lib.vkas_colsum_ws_bytes(M, Nd)
-            ws_cs = _ws(nbytes, dev)
-            _timed('colsum_partial_kernel', x, 0.0, M, Nd, 0,
-                   lambda: check(lib.vkas_colsum(_p(dz), act_ld(dz), M, Nd, _p(gbp[offs[r0]:offs[r1]]), 1, _p(ws_cs), nbytes,
-                                                 _dt(x), _stream()), 'colsum'), float(M) * Nd * es)
-            del dz
-            g1 = _geom(B, h_, w_, h_, w_, Cp, act_ld(x_low), 1, 1, 1, 0)
-            gE = conv_wgrad(x_low, g1, E, 9 * Nd, nk=(9 * sum(cs[r0:r1]), C), step_scratch=True)
-            check(lib.vkas_upconv_adj_unpack_wgrad(_p(gE), _p(gwp[offs[r0] * K:offs[r1] * K]), Nd, Cp, _stream()),
-                  'upconv_adj_unpack_wgrad')
-            if dx is not None:
-                Bt = pack_head_weights(ws[r0:r1], nps[r0:r1], Cp, 1, x.dtype)
-                g2 = _geom(B, h_, w_, h_, w_, 9 * Nd, 9 * Nd, 1, 1, 1, 0)
-                conv_gemm(E, g2, Bt, Cp, dx, _lib.EPI_NONE, nk=(C, sum(cs[r0:r1]) * 9))
-
-        dx_pts = dx      # where the label-point heads add their input gradient: x's resolution
-        dx_low_set = False
-        if not low:
-            if d1 > d0:
-                dense_upres(d0, d1, dx)
-            elif dx is not None:
-                dx.zero_()
-        else:
-            # A dense head whose gradient still carries a label-point mark (compact path switched off or not applicable) keeps
-            # the convolution kernels: its dz is zero off B*P rows, and the compact path it is compared with sums exactly what
-            # those kernels sum.  Such heads are a prefix or a suffix of the dense run, like the compact ones.
-            marked = [point_mark(dprojs[h]) is not None for h in range(d0, d1)]
-            plain = [d0 + i for i, m in enumerate(marked) if not m]
-            e0, e1 = (plain[0], plain[-1] + 1) if plain else (d0, d0)
-            if plain != list(range(e0, e1)) or (e0 > d0 and e1 < d1):
-                e0, e1 = d0, d0  # not one run at either end: everything on the convolution kernels
-            u0, u1 = (e1, d1) if e0 == d0 else (d0, e0)
-            dx_pts = None
-            if u1 > u0:
-                dx_pts = new_act(B, H, W, Cp, x) if need_dx else None
-                dense_upres(u0, u1, dx_pts)
-            elif sp is not None and need_dx:
-                dx_pts = torch.zeros((B, H, W, Cp), dtype=x.dtype, device=dev)
-            if e1 > e0:
-                dense_lowres(e0, e1)
-                dx_low_set = True
+        dx_pts = dx  # where the convolution kernels write and the label-point heads add their input gradient, at x's resolution
+        if low and need_dx and u1 == u0:  # low: a buffer of its own; here only the label-point heads add to it, if any
+            dx_pts = torch.zeros((B, H, W, Cp), dtype=x.dtype, device=dev) if sp is not None else None
+        elif low:
+            dx_pts = new_act(B, H, W, Cp, x) if need_dx else None
+        elif u1 == u0 and dx is not None:
+            dx.zero_()
+        if u1 > u0:
+            _heads_dense_upres(heads, u0, u1, pw, hp, x, z, stats, dps, dparams, gwp, gbp, dx_pts)
+        if e1 > e0:
+            _heads_dense_lowres(heads, e0, e1, pw, hp, x, z, stats, dps, dparams, gwp, gbp, x_low, dx)
         if sp is not None:
-            s0, s1, py, px = sp
-            Ns = offs[s1] - offs[s0]
-            P = py.shape[1]
-            Mp = -(-(B * P) // 64) * 64
-            scratch = torch.empty((M + Mp,), dtype=torch.int32, device=dev)
-            pmap, pix = scratch[:M], scratch[M:]
-            check(lib.vkas_points_prepare(_p(py), _p(px), B, P, H, W, _p(pmap), _p(pix), Mp, _stream()), 'points_prepare')
+            offs, Ns, py, px = heads.offs, heads.offs[s1] - heads.offs[s0], sp[2], sp[3]
+            _, pmap, pix, Mp = _points_prepare(py, px, B, H, W)
             zs = new_act(1, 1, Mp, Ns, x)
             fbuf = torch.empty(((s1 - s0) * Mp * 10,), dtype=_FLOAT, device=dev)
             stats_s, dproj_s = fbuf[:(s1 - s0) * Mp * 2], fbuf[(s1 - s0) * Mp * 2:]
@@ -1213,82 +1339,20 @@ class HeadsFused(Function):
             check(lib.vkas_points_gather_rows(_p(z), Nt, offs[s0], Ns, ctypes.c_void_p(stats.data_ptr() + s0 * M * 8), ptrs,
                                               s1 - s0, M, _p(pix), Mp, _p(zs), _p(stats_s), _p(dproj_s), _dt(x), _stream()),
                   'points_gather_rows')
-            dzs = new_act(1, 1, Mp, Ns, x)
-            tail_bwd(s0, s1, zs.data_ptr(), Ns, stats_s.data_ptr(),
-                     [dproj_s.data_ptr() + j * Mp * 32 for j in range(s1 - s0)], Mp, dzs)
-            # weight / bias gradient: (Ns x Mp) . (Mp x 9 Cp) on the gathered 3x3 patches
-            xs = new_act(1, 1, Mp, K, x)
-            check(lib.vkas_points_gather_patches(_p(x), act_ld(x), Cp, B, H, W, _p(pix), Mp, _p(xs), _dt(x), _stream()),
-                  'points_gather_patches')
-            g1 = _geom(1, 1, Mp, 1, Mp, K, K, 1, 1, 1, 0)
-            conv_wgrad(xs, g1, dzs, Ns, nk=(sum(cs[s0:s1]), C * 9), with_bias=True,
-                       gw_into=gwp[offs[s0] * K:offs[s1] * K], gb_into=gbp[offs[s0]:offs[s1]])
-            if dx is not None:
-                # input gradient: D (Mp x 9 Cp, fp32) = dz_s . W with W (Ns x 9 Cp) the rows of the forward weight image -
-                # the reduction runs over W's ROWS, i.e. this is the weight-gradient GEMM shape with dz_s^T as the "dy"
-                # operand (fp32 result, no 16-bit rounding of the per-tap terms) - then summed per touched pixel onto dx
-                Wf = pack_head_weights(ws, nps, Cp, 0, x.dtype)[offs[s0] * K:offs[s1] * K].view(1, 1, Ns, K)
-                dzt = dzs.view(Mp, Ns).t().contiguous().view(1, 1, Ns, Mp)
-                g3 = _geom(1, 1, Ns, 1, Ns, K, K, 1, 1, 1, 0)
-                D = conv_wgrad(Wf, g3, dzt, Mp, nk=(B * P, C * 9), step_scratch=True, ordered=True)
-                check(lib.vkas_points_scatter3x3(_p(D), _p(pix), _p(pmap), Mp, B, H, W, Cp, _p(dx_pts), act_ld(dx_pts), _dt(x),
-                                                 _stream()), 'points_scatter3x3')
+            _heads_points_grads(heads, s0, s1, pw, hp, lambda: _points_gather_patches(x, pix, Mp), zs, stats_s,
+                                [dproj_s.data_ptr() + j * Mp * 32 for j in range(s1 - s0)], pix, pmap, py.numel(), dparams,
+                                gwp[offs[s0] * K:offs[s1] * K], gbp[offs[s0]:offs[s1]], False, dx_pts)
         if low and dx is not None:
             if dx_pts is not None:  # dx (+)= U^T dx_pts
                 _timed('resize2x_bwd_kernel', x, 0.0, M, Cp, 0,
                        lambda: check(lib.vkas_resize_bwd(_p(dx_pts), act_ld(dx_pts), _p(dx), act_ld(dx), B, h_, w_, H, W, Cp, 0,
-                                                         int(dx_low_set), _dt(x), _stream()), 'resize_bwd'),
-                       B * Cp * es * (h_ * w_ * (2 if dx_low_set else 1) + H * W))
-            elif not dx_low_set:
+                                                         int(e1 > e0), _dt(x), _stream()), 'resize_bwd'),
+                       B * Cp * x.element_size() * (h_ * w_ * (2 if e1 > e0 else 1) + H * W))
+            elif e1 == e0:
                 dx.zero_()
-        gws, gbs = [], []
-        for h in range(n_heads):
-            gslice = gwp[offs[h] * K:offs[h + 1] * K]
-            sw = grad_sink(ws[h])
-            if sw is not None:  # straight into the flat gradient view
-                unpack_wgrad(gslice, (cs[h], C, 3, 3), nps[h], Cp, into=ws[h].grad)
-                sw[0].grad_delivered(sw[1])
-                gws.append(None)
-            else:
-                gws.append(unpack_wgrad(gslice, (cs[h], C, 3, 3), nps[h], Cp))
-            gbs.append(gbp[offs[h]:offs[h] + cs[h]])
-        # the heads' small gradients (conv bias, LayerNorm affine, projection): with flat .grad views they are added in place by
-        # vkas_accumulate_many, 16 contiguous pieces per launch (a projection weight row by row), instead of one autograd add
-        # per parameter (30 launches per step)
-        small = saved[4 + 2 * n_heads:]
-        gammas, betas = small[:n_heads], small[n_heads:2 * n_heads]
-        wps, bps = small[2 * n_heads:3 * n_heads], small[3 * n_heads:4 * n_heads]
-        grads, pieces, delivered = [], [], []
-        for h in range(n_heads):
-            d = dparams[h]
-            per = [(bs[h], gbs[h], [(gbs[h], 0, cs[h])]), (gammas[h], d[:cs[h]], [(d, 0, cs[h])]),
-                   (betas[h], d[pw:pw + cs[h]], [(d, pw, cs[h])]),
-                   (wps[h], d[2 * pw:6 * pw].view(4, pw)[:ocs[h], :cs[h]], [(d, (2 + q) * pw, cs[h]) for q in range(ocs[h])]),
-                   (bps[h], d[6 * pw:6 * pw + ocs[h]], [(d, 6 * pw, ocs[h])])]
-            out = [gws[h]]
-            for param, g, rows in per:
-                sk = grad_sink(param)
-                if sk is None or not param.grad.is_contiguous():
-                    # handed to autograd: never a view of the step's zero arena (see conv_param_grads)
-                    out.append(g.clone() if (flat_sinks and g is gbs[h]) else g)
-                    continue
-                off = 0
-                for src, so, cnt in rows:
-                    pieces.append((src.data_ptr() + 4 * so, param.grad.data_ptr() + 4 * off, cnt))
-                    off += cnt
-                delivered.append(sk)
-                out.append(None)
-            grads.extend(out)
-        for i in range(0, len(pieces), 16):
-            part = pieces[i:i + 16]
-            n = len(part)
-            src = (ctypes.c_void_p * n)(*[a for a, _, _ in part])
-            dst = (ctypes.c_void_p * n)(*[b for _, b, _ in part])
-            cnt = (ctypes.c_int * n)(*[c for _, _, c in part])
-            check(lib.vkas_accumulate_many(n, src, dst, cnt, _stream()), 'accumulate_many')
-        for sk in delivered:
-            sk[0].grad_delivered(sk[1])
-        return (dx, None, *grads)
+        gws = _deliver_head_weight_grads(heads, gwp, K)
+        small = _deliver_head_small_grads(heads, pw, dparams, gbp, flat_sinks)
+        return (dx, None, *[g for h in range(n_heads) for g in (gws[h], *small[h])])
 
 
 _HEAD_BWD_UPRES = os.environ.get('VKAS_HEAD_BWD_UPRES') is not None  # A/B switch: head backward at the upsampled resolution
@@ -1308,8 +1372,7 @@ class UpHeadsFused(Function):
     @staticmethod
     def eligible(x, channels, out_channels) -> bool:
         B, h, w, _ = x.shape
-        return (not _HEAD_BWD_UPRES and x.dtype in _MFMA_DTYPES and h > 1 and w > 1 and 4 * B * h * w >= 16384
-                and len(channels) <= 4 and max(rup8(c) for c in channels) <= 512 and max(out_channels) <= 4)
+        return not _HEAD_BWD_UPRES and h > 1 and w > 1 and _heads_eligible(x.dtype, 4 * B * h * w, channels, out_channels)
 
     @staticmethod
     def forward(ctx, x, keep: bool, with_up: bool, *params):
@@ -1356,78 +1419,43 @@ class HeadsAtPoints(Function):
         x = as_act(x)
         if x.dtype not in _MFMA_DTYPES:
             raise ValueError('HeadsAtPoints: 16-bit activations only')
-        n_heads = len(params) // 6
-        ws, bs = params[0::6], params[1::6]
-        gammas, betas, wps, bps = params[2::6], params[3::6], params[4::6], params[5::6]
-        cs = [g.numel() for g in gammas]
-        ocs = [w.shape[0] for w in wps]
-        nps = [rup8(c) for c in cs]
-        Ns = sum(nps)
         B, H, W, Cp = x.shape
-        C = ws[0].shape[1]
-        assert all(tuple(w.shape) == (c, C, 3, 3) for w, c in zip(ws, cs)) and Cp == rup8(C)
-        if n_heads > 4 or max(ocs) > 4 or max(nps) > 512:
+        heads = _HeadSet(params, Cp)
+        n_heads, Ns, C = heads.n, heads.Nt, heads.C
+        if n_heads > 4 or max(heads.ocs) > 4 or max(heads.nps) > 512:
             raise ValueError('HeadsAtPoints: at most 4 heads of at most 512 channels and 4 outputs')
         py, px = py.contiguous().long(), px.contiguous().long()
         if py.dim() != 2 or py.shape[0] != B or px.shape != py.shape or py.shape[1] == 0:
             raise ValueError(f'HeadsAtPoints: label points must be (B={B}, P > 0)')
-        P = py.shape[1]
-        M, K = B * H * W, 9 * Cp
-        Mp = -(-(B * P) // 64) * 64
-        pw = max(nps)
-        dev = x.device
-        scratch = torch.empty((M + Mp,), dtype=torch.int32, device=dev)
-        pmap, pix = scratch[:M], scratch[M:]
-        check(lib.vkas_points_prepare(_p(py), _p(px), B, P, H, W, _p(pmap), _p(pix), Mp, _stream()), 'points_prepare')
-        xs = new_act(1, 1, Mp, K, x)
-        check(lib.vkas_points_gather_patches(_p(x), act_ld(x), Cp, B, H, W, _p(pix), Mp, _p(xs), _dt(x), _stream()),
-              'points_gather_patches')
-
-        def build_hp():
-            t = torch.empty((n_heads, 6 * pw + 8), dtype=_FLOAT, device=dev)
-            for h in range(n_heads):
-                check(lib.vkas_pack_head_params(_p(gammas[h].contiguous()), _p(betas[h].contiguous()),
-                                                _p(wps[h].contiguous()), _p(bps[h].contiguous()), cs[h], ocs[h], pw,
-                                                _p(t[h]), _stream()), 'pack_head_params')
-            return t
-
-        hp = _cached_pack_multi(list(gammas) + list(betas) + list(wps) + list(bps), ('head_params', pw), build_hp)
-        b_cat = pack_head_bias(bs, cs, nps)
-        Wf = pack_head_weights(ws, nps, Cp, 0, x.dtype)
+        K, pw, dev = 9 * Cp, max(heads.nps), x.device
+        scratch, _, pix, Mp = _points_prepare(py, px, B, H, W)
+        xs = _points_gather_patches(x, pix, Mp)
+        hp = heads.packed_params(pw)
+        b_cat = heads.bias()
+        Wf = heads.weights(0, x.dtype)
         zs = new_act(1, 1, Mp, Ns, x)
         g1 = _geom(1, 1, Mp, 1, Mp, K, K, 1, 1, 1, 0)
-        conv_gemm(xs, g1, Wf, Ns, zs, _lib.EPI_NONE, bias=b_cat, nk=(sum(cs), C * 9))
+        conv_gemm(xs, g1, Wf, Ns, zs, _lib.EPI_NONE, bias=b_cat, nk=(sum(heads.cs), C * 9))
         fbuf = torch.empty((n_heads * Mp * 10,), dtype=_FLOAT, device=dev)
         stats_s, proj_s = fbuf[:n_heads * Mp * 2], fbuf[n_heads * Mp * 2:]
-        head = _lib.HeadDesc()
-        head.n_heads, head.pw = n_heads, pw
-        off = 0
-        for h in range(n_heads):
-            head.n0[h], head.np[h], head.c[h], head.oc[h] = off, nps[h], cs[h], ocs[h]
-            off += nps[h]
-        head.params, head.stats, head.proj = hp.data_ptr(), stats_s.data_ptr(), proj_s.data_ptr()
+        head = heads.desc(0, n_heads, pw, hp.data_ptr(), stats_s.data_ptr(), proj_s.data_ptr())
         check(lib.vkas_head_tail_fwd(_p(zs), Ns, ctypes.byref(head), Mp, _dt(x), _stream()), 'head_tail_fwd')
         proj = torch.zeros((n_heads, B, H, W, 8), dtype=_FLOAT, device=dev)
         for h in range(n_heads):
             check(lib.vkas_points_scatter_vec8(ctypes.c_void_p(proj_s.data_ptr() + h * Mp * 32), _p(pix), Mp, _p(proj[h]),
                                                _stream()), 'points_scatter_vec8')
-        ctx.save_for_backward(xs, zs, stats_s, hp, scratch, *ws, *bs)
-        ctx.meta = (cs, ocs, nps, pw, C, (B, H, W, Cp), P, Mp, x.dtype)
+        ctx.save_for_backward(xs, zs, stats_s, hp, scratch, *heads.saved(small=False))
+        ctx.heads, ctx.meta = heads, (pw, (B, H, W, Cp), py.shape[1], Mp, x.dtype)
         return tuple(proj[h] for h in range(n_heads))
 
     @staticmethod
     def backward(ctx, *dprojs):
-        cs, ocs, nps, pw, C, (B, H, W, Cp), P, Mp, dtype = ctx.meta
-        n_heads = len(cs)
+        pw, (B, H, W, Cp), P, Mp, dtype = ctx.meta
         saved = ctx.saved_tensors
         xs, zs, stats_s, hp, scratch = saved[:5]
-        ws, bs = saved[5:5 + n_heads], saved[5 + n_heads:5 + 2 * n_heads]
-        M, K = B * H * W, 9 * Cp
-        Ns = sum(nps)
-        dev = xs.device
+        heads = ctx.heads.from_saved(saved[5:])
+        n_heads, M, K, dev = heads.n, B * H * W, 9 * Cp, xs.device
         pmap, pix = scratch[:M], scratch[M:]
-        PS = 6 * pw + 8
-        offs = [sum(nps[:h]) for h in range(n_heads + 1)]
         dproj_s = torch.empty((n_heads, Mp, 8), dtype=_FLOAT, device=dev)
         for h in range(n_heads):
             if dprojs[h] is None:
@@ -1435,44 +1463,14 @@ class HeadsAtPoints(Function):
             else:
                 check(lib.vkas_points_gather_vec8(_p(dprojs[h].contiguous().float()), _p(pix), Mp, _p(dproj_s[h]), _stream()),
                       'points_gather_vec8')
-        dparams = torch.empty((n_heads, PS), dtype=_FLOAT, device=dev)
-        head = _lib.HeadDesc()
-        head.n_heads, head.pw = n_heads, pw
-        ptrs = (ctypes.c_void_p * 4)()
-        for h in range(n_heads):
-            head.n0[h], head.np[h], head.c[h], head.oc[h] = offs[h], nps[h], cs[h], ocs[h]
-            ptrs[h] = dproj_s[h].data_ptr()
-        head.params, head.stats, head.proj = hp.data_ptr(), stats_s.data_ptr(), None
-        nbytes = lib.vkas_head_tail_bwd_ws_bytes(Mp, pw)
-        ws_buf = _ws(nbytes, dev)
-        dzs = new_act(1, 1, Mp, Ns, xs)
-        check(lib.vkas_head_tail_bwd(_p(zs), Ns, ctypes.byref(head), ptrs, _p(dzs), Ns, _p(dparams), _p(ws_buf), nbytes, Mp,
-                                     _dtc(dtype), _stream()), 'head_tail_bwd')
-        g1 = _geom(1, 1, Mp, 1, Mp, K, K, 1, 1, 1, 0)
-        gwp, gbp = conv_wgrad(xs, g1, dzs, Ns, nk=(sum(cs), C * 9), with_bias=True,
-                              step_scratch=all(grad_sink(p) is not None for p in list(ws) + list(bs)))
-        dx = None
-        if ctx.needs_input_grad[0]:
-            Wf = pack_head_weights(ws, nps, Cp, 0, dtype).view(1, 1, Ns, K)
-            dzt = dzs.view(Mp, Ns).t().contiguous().view(1, 1, Ns, Mp)
-            g3 = _geom(1, 1, Ns, 1, Ns, K, K, 1, 1, 1, 0)
-            D = conv_wgrad(Wf, g3, dzt, Mp, nk=(B * P, C * 9), step_scratch=True, ordered=True)
-            dx = torch.zeros((B, H, W, Cp), dtype=dtype, device=dev)
-            check(lib.vkas_points_scatter3x3(_p(D), _p(pix), _p(pmap), Mp, B, H, W, Cp, _p(dx), Cp, _dtc(dtype), _stream()),
-                  'points_scatter3x3')
-        grads = []
-        for h in range(n_heads):
-            gslice = gwp[offs[h] * K:offs[h + 1] * K]
-            sw = grad_sink(ws[h])
-            if sw is not None:
-                unpack_wgrad(gslice, (cs[h], C, 3, 3), nps[h], Cp, into=ws[h].grad)
-                sw[0].grad_delivered(sw[1])
-                gw = None
-            else:
-                gw = unpack_wgrad(gslice, (cs[h], C, 3, 3), nps[h], Cp)
-            d = dparams[h]
-            grads.extend([gw, gbp[offs[h]:offs[h] + cs[h]], d[:cs[h]], d[pw:pw + cs[h]],
-                          d[2 * pw:6 * pw].view(4, pw)[:ocs[h], :cs[h]], d[6 * pw:6 * pw + ocs[h]]])
+        dparams = torch.empty((n_heads, 6 * pw + 8), dtype=_FLOAT, device=dev)
+        dx = torch.zeros((B, H, W, Cp), dtype=dtype, device=dev) if ctx.needs_input_grad[0] else None
+        flat_sinks = all(grad_sink(p) is not None for p in list(heads.ws) + list(heads.bs))
+        gwp, gbp = _heads_points_grads(heads, 0, n_heads, pw, hp, xs, zs, stats_s, [d.data_ptr() for d in dproj_s], pix, pmap,
+                                       B * P, dparams, None, None, flat_sinks, dx)
+        gws = _deliver_head_weight_grads(heads, gwp, K)
+        # the small gradients go back to autograd as tensors
+        grads = [g for h in range(n_heads) for g in (gws[h], *heads.small_grad_views(h, pw, dparams[h], gbp))]
         return (dx, None, None, *grads)
 
 
