@@ -206,14 +206,37 @@ int vkas_mlp_chain_ln_fwd(const void* y, long ldy, const float* ln_gamma, const 
 /* dh = (dz W2) * gelu'(h) (stored, operand of the W1 weight gradient); dyn = dh W1.  img_t = the mode-1 image. */
 int vkas_mlp_chain_bwd(const void* dz, long lddz, const void* img_t, const void* h, long ldh, void* dh, long lddh,
                        void* dyn, long lddyn, long M, int C, int dtype, void* stream);
-/* profiling aid: tile configuration a bf16 call of these sizes runs.  fwd (wgrad == 0): 1 = 128x128 (4 waves), else the
- * N extent 128 / 192 / 224 of the 256-row 8-wave tile; wgrad: N extent 128 (4 waves), 192 / 224 (8 waves, 256 K columns) or 384 (8 waves, 128 K columns); 0 when the
- * plain fp32-FMA kernels are forced (VKAS_GEMM=simple). */
+/* The three reporters below read the launch plan the 16-bit launchers execute (csrc/gemm_plan.h).
+ * tile configuration a 16-bit call of these sizes runs.  fwd (wgrad == 0): 1 = 128x128 (4 waves), else the N extent 128 /
+ * 192 / 224 of the 256-row 8-wave tile; wgrad: N extent 128 (4 waves), 192 / 224 (8 waves, 256 K columns) or 384 (8 waves,
+ * 128 K columns); 0 when the plain fp32-FMA kernels are forced (VKAS_GEMM=simple). */
 int vkas_conv_gemm_tile(int wgrad, long M, int Np, int K);
-/* profiling aid: the kernel a bf16 call with this geometry runs.  0 = plain fp32-FMA kernels forced.  fwd: 1 / 128 / 192 /
- * 224 as above, 1000 + TN = the 3x3 row-slab kernel conv3x3_slab_mfma_kernel<TN, .> (TN = 4, 6, 7); wgrad: 128 / 192 /
- * 224, 2000 + TNn = conv3x3_wgrad_slab_kernel<TNn> (7, 8).  head_width > 0 for a fused-head launch (widest head). */
+/* the kernel a 16-bit call with this geometry runs (wgrad: a plain vkas_conv_gemm_wgrad call).  0 = plain fp32-FMA kernels
+ * forced.  fwd: 1 / 128 / 192 / 224 as above, 10 + depth = gemm_nt_ring_kernel<2 / 3 / 4>, 1000 + TN = the 3x3 row-slab kernel
+ * conv3x3_slab_mfma_kernel<TN, .> (TN = 4, 6, 7); wgrad: 128 / 192 / 224 / 384, 2000 + TNn = conv3x3_wgrad_slab_kernel<TNn>
+ * (6, 7, 8).  head_width > 0 for a fused-head launch (widest head). */
 int vkas_conv_gemm_kernel_id(int wgrad, const vkas_conv_geom* g, int Np, long lddy, int head_width);
+/* the A/B switches of the kernel choice, one per VKAS_* environment variable of INTEGRATION.md */
+typedef struct vkas_gemm_switches {
+  int nt_tile, tn_tile; /* VKAS_NT_TILE 1 / 128 / 192 / 224, VKAS_TN_TILE 128 / 192 / 224 / 384; any other value: unset */
+  int nt_ring;          /* VKAS_NT_RING: < 0 unset, 2 / 3 / 4 the ring depth, any other value the register-staged kernel */
+  int nt_noslab, nt_nobuf, tn_nobuf, tn_noslab, tn_no96; /* non-zero: set */
+} vkas_gemm_switches;
+/* the whole plan of a 16-bit call.  family: fwd 0 register-staged 128x128, 1 ring, 2 256-row tile, 3 row slab; wgrad 0
+ * generic, 1 slab.  grid = tiles * splits; fwd: tiles = grid_m * grid_n and splits = 1 (a fused-head launch runs grid_m *
+ * n_heads workgroups).  rows: rows per split (generic wgrad) or 64-row chunks per split (wgrad slab).  a_bytes / b_bytes:
+ * the spans of x and of Bw (fwd) or dy (wgrad).  name: the kernel as a profiler prints it, template arguments shortened. */
+typedef struct vkas_gemm_plan_info {
+  int kernel_id, family, bn, ring, buf, head, pw, nobias, xg; /* kernel_id: vkas_conv_gemm_kernel_id; bn: N extent of the tile */
+  long grid_m, grid_n, tiles, splits, rows, a_bytes, b_bytes;
+  unsigned grid;
+  char name[44];
+} vkas_gemm_plan_info;
+/* flags: 1 = vkas_conv_gemm_wgrad_gelu, 2 = vkas_conv_gemm_wgrad_ordered; has_gb: a bias gradient is asked for;
+ * sw == NULL: the switches of this process's environment (and VKAS_GEMM=simple: kernel_id 0, name gemm_nt_simple /
+ * gemm_tn_simple, nothing else filled). */
+int vkas_conv_gemm_plan(int wgrad, const vkas_conv_geom* g, int Np, long lddy, int head_width, int flags, int has_gb,
+                        const vkas_gemm_switches* sw, vkas_gemm_plan_info* out);
 /* column sums: out[n] (+)= sum_m y[m][n]   (bias gradients) */
 int vkas_colsum(const void* y, long ld, long M, int Np, float* out, int accumulate, float* ws, size_t ws_bytes,
                 int dtype, void* stream);

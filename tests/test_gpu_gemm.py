@@ -9,10 +9,10 @@ timed out or ended abnormally no further child is started and the remaining test
 cases of its setting in both 16-bit types (the default child also in fp32: gemm_simple.hip and epi_store4), records
 vkas_conv_gemm_kernel_id / vkas_conv_gemm_tile of every case (a retuned dispatch cannot silently move a case to another kernel),
 checks the guards on the device and saves the outputs; the parent computes fp64 references on the host and compares per case.
-The kernel id names the tile, the ring depth and the slab kernel; it does not tell a buffer from a non-buffer form, nor the
-NOBIAS / PW instantiations.  That those ran rests on the child asserting its own environment (the switches are read from it once)
-and on launch_nt / launch_tn, which read nothing else.  NOBIAS exists with buffer loads only: 'no gb' on a non-buffer tile is the
-plain non-buffer kernel with a null gb.
+The kernel id names the tile, the ring depth and the slab kernel; buffer against non-buffer and the NOBIAS / PW instantiations
+come from vkas_conv_gemm_plan, the plan the launchers execute (csrc/gemm_plan.h; tests/test_cpu_gemm_plan.py holds it to the
+previous launchers): the child records it per case and the parent asserts it against the setting.  NOBIAS exists with buffer
+loads only: 'no gb' on a non-buffer tile is the plain non-buffer kernel with a null gb.
   forward   register-staged 128x128, ring 2 / 3 / 4, 256x128 / 192 / 224 buffer and non-buffer, row-slab 4 / 6 / 7
   wgrad     tile 128 / 192 / 224 / 384 x buffer / non-buffer x plain (gb) / plain (no gb: NOBIAS at 192 / 384 pointwise) / GELU / ordered
 
@@ -177,6 +177,13 @@ def cid(c):
 
 def expected_kid(s, c):
     return 1000 + s.BN // 32 if (s.slab and c.geo == 's3') else s.kid
+
+
+def plan_record(_lib, wgrad, G, Np, lddy, flags, has_gb):
+    """[buf, pw, nobias, ring depth, kernel name] of the plan this process's launchers execute for the call."""
+    info = _lib.GemmPlanInfo()
+    rc = _lib.lib.vkas_conv_gemm_plan(wgrad, ctypes.byref(G), Np, lddy, 0, flags, int(has_gb), None, ctypes.byref(info))
+    return [info.buf, info.pw, info.nobias, info.ring, info.name.decode() if rc == 0 else 'rc %d' % rc]
 
 
 # ------------------------------------------------------------------------------------------------------------- operands
@@ -465,6 +472,7 @@ def child_nt(_lib, s, c, kind, dt):
         kid, tile = lib.vkas_conv_gemm_kernel_id(0, ctypes.byref(G), Np, 0, 0), lib.vkas_conv_gemm_tile(0, M, Np, K)
         if kid != expected_kid(s, c) or tile != (1 if s.BM == 128 else s.BN):
             msgs.append('kernel id %d / tile %d, expected %d / %d' % (kid, tile, expected_kid(s, c), 1 if s.BM == 128 else s.BN))
+        res['plan'] = plan_record(_lib, 0, G, Np, 0, 0, False)
     bias = _vec(o['bias']) if o['bias'] is not None else None
 
     def launch(tag, mode, out=None, out2=None, aux=None, cs=None, rs=None, rpi=0, patch=None):
@@ -518,6 +526,7 @@ def child_tn(_lib, s, c, kind, dt):
         kid, tile = lib.vkas_conv_gemm_kernel_id(1, ctypes.byref(G), Np, dy.ld, 0), lib.vkas_conv_gemm_tile(1, M, Np, K)
         if kid != s.tn or tile != s.tn:
             msgs.append('kernel id %d / tile %d, expected %d' % (kid, tile, s.tn))
+        res['plan'] = plan_record(_lib, 1, G, Np, dy.ld, {'gelu': 1, 'ordered': 2}.get(c.entry, 0), c.entry in ('gb', 'gelu'))
 
     def fresh(v0):
         t = torch.full((v0.numel() + 64,), SENTINEL, device='cuda')
@@ -674,6 +683,10 @@ def test_forward(name, c, dt):
         got = res['nt|%s|%s|%s' % (cid(c), kind, dt)]
         assert got['msg'] == '', '%s %s %s: %s' % (cid(c), kind, dt, got['msg'])
         compare_nt(c, kind, dt, got, form)
+        if dt != 'f32':  # the plan behind the launch: buffer loads unless VKAS_NT_NOBUF, the ring depth and the name of the kernel id
+            from tests.test_cpu_gemm_plan import nt_kernel_name
+            assert got['plan'] == [int('VKAS_NT_NOBUF' not in s.env), 0, 0, s.kid - 10 if 12 <= s.kid <= 14 else 0,
+                                   nt_kernel_name(expected_kid(s, c), False)], (cid(c), kind, dt, got['plan'])
 
 
 @pytest.mark.parametrize('name,c,dt', TN_PARAMS, ids=_ids(TN_PARAMS))
@@ -686,6 +699,12 @@ def test_wgrad(name, c, dt):
         got = res['tn|%s|%s|%s' % (cid(c), kind, dt)]
         assert got['msg'] == '', '%s %s %s: %s' % (cid(c), kind, dt, got['msg'])
         compare_tn(c, kind, dt, got, form)
+        if dt != 'f32':  # non-buffer in the ...nb settings and t224noslab; NOBIAS: no gb pointer ('nogb', and _ordered, which has
+            # none), pointwise, tile 192 / 384, buffer loads only
+            from tests.test_cpu_gemm_plan import tn_kernel_name
+            buf = int(TN_BUFFER[name])
+            nobias = int(c.entry in ('nogb', 'ordered') and c.geo == 'pw' and s.tn in (192, 384) and buf)
+            assert got['plan'] == [buf, int(buf and c.geo == 'pw'), nobias, 0, tn_kernel_name(s.tn)], (cid(c), kind, dt, got['plan'])
 
 
 def _same_bits(a, b):
@@ -694,7 +713,7 @@ def _same_bits(a, b):
 
 
 def _tensors(r):
-    return {k: v for k, v in r.items() if k != 'msg'}
+    return {k: v for k, v in r.items() if k not in ('msg', 'plan')}
 
 
 @pytest.mark.parametrize('other', ['ring2', 'ring3', 'ring4', 'default'])

@@ -6,7 +6,7 @@ or a symbol cannot be resolved, importing this module raises.
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int64, c_long, c_longlong, c_size_t, c_void_p
+from ctypes import POINTER, Structure, c_char, c_char_p, c_double, c_float, c_int, c_int64, c_long, c_longlong, c_size_t, c_uint, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # VKAS_LIB_PATH: profiling aid only (timing-only ablation builds from profiles/build_*_variants.sh)
@@ -34,6 +34,21 @@ class Epilogue(Structure):
                 ('ldo2', c_long), ('aux', c_void_p), ('ldaux', c_long), ('colscale', c_void_p),
                 ('rowscale', c_void_p), ('rows_per_image', c_int), ('patch', c_int), ('patch_Hs', c_int),
                 ('patch_Ws', c_int), ('patch_Cp', c_int), ('head', HeadDesc)]
+
+
+class GemmSwitches(Structure):
+    """vkas_gemm_switches; the defaults are 'nothing set'."""
+    _fields_ = [('nt_tile', c_int), ('tn_tile', c_int), ('nt_ring', c_int), ('nt_noslab', c_int), ('nt_nobuf', c_int),
+                ('tn_nobuf', c_int), ('tn_noslab', c_int), ('tn_no96', c_int)]
+
+    def __init__(self, nt_ring=-1, **kw):
+        super().__init__(nt_ring=nt_ring, **kw)
+
+
+class GemmPlanInfo(Structure):
+    _fields_ = [(n, c_int) for n in ('kernel_id', 'family', 'bn', 'ring', 'buf', 'head', 'pw', 'nobias', 'xg')] + \
+               [(n, c_long) for n in ('grid_m', 'grid_n', 'tiles', 'splits', 'rows', 'a_bytes', 'b_bytes')] + \
+               [('grid', c_uint), ('name', c_char * 44)]
 
 
 class PackDesc(Structure):
@@ -109,6 +124,8 @@ _SIGS = {
     'vkas_mlp_chain_bwd': (c_int, [_P, c_long, _P, _P, c_long, _P, c_long, _P, c_long, c_long, c_int, c_int, _P]),
     'vkas_conv_gemm_tile': (c_int, [c_int, c_long, c_int, c_int]),
     'vkas_conv_gemm_kernel_id': (c_int, [c_int, POINTER(ConvGeom), c_int, c_long, c_int]),
+    'vkas_conv_gemm_plan': (c_int, [c_int, POINTER(ConvGeom), c_int, c_long, c_int, c_int, c_int, POINTER(GemmSwitches),
+                                    POINTER(GemmPlanInfo)]),
     'vkas_colsum': (c_int, [_P, c_long, c_long, c_int, _P, c_int, _P, c_size_t, c_int, _P]),
     'vkas_colsum_ws_bytes': (c_size_t, [c_long, c_int]),
     'vkas_dwconv7x7_fwd': (c_int, [_P, c_long, _P, _P, _P, c_long, _P, c_long, c_int, c_int, c_int, c_int, c_int, _P]),

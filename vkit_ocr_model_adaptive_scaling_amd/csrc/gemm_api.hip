@@ -3,6 +3,7 @@
 #include <string.h>
 
 #include "gemm_parts.h"
+#include "gemm_plan.h"
 
 int vkas_gemm_nt_simple(const void*, const vkas_conv_geom*, const void*, int, const vkas_epilogue*, int, hipStream_t);
 int vkas_gemm_tn_simple(const void*, const vkas_conv_geom*, const void*, long, int, float*, float*, int, int, hipStream_t);
@@ -10,14 +11,6 @@ int vkas_gemm_nt_mfma_bf16(const void*, const vkas_conv_geom*, const void*, int,
 int vkas_gemm_tn_mfma_bf16(const void*, const vkas_conv_geom*, const void*, long, int, float*, float*, int, hipStream_t);
 int vkas_gemm_nt_mfma_f16(const void*, const vkas_conv_geom*, const void*, int, const vkas_epilogue*, hipStream_t);
 int vkas_gemm_tn_mfma_f16(const void*, const vkas_conv_geom*, const void*, long, int, float*, float*, int, hipStream_t);
-
-int vkas_gemm_nt_tile_choice(long M, int Np);
-int vkas_gemm_tn_tile_choice(long M, int Np, int K);
-bool vkas_nt_slab_eligible(const vkas_conv_geom* g, int Np);
-int vkas_gemm_nt_ring_stages(const vkas_conv_geom* g, int Np);
-bool vkas_tn_slab_eligible(const vkas_conv_geom* g, int Np, long lddy);
-bool vkas_tn_slab_n112(int Np);
-bool vkas_tn_slab_n96(int Np);
 
 static thread_local char g_err[512] = "";
 
@@ -107,30 +100,40 @@ extern "C" int vkas_conv_gemm_fwd(const void* x, const vkas_conv_geom* g, const 
   return vkas_gemm_nt_simple(x, g, Bw, Np, epi, dtype, vkas_stream(stream));
 }
 
-// Which kernel instantiation a bf16 call with these sizes runs (profiling aid; the names match rocprofv3's).
-extern "C" int vkas_conv_gemm_tile(int wgrad, long M, int Np, int K) {
-  if (force_simple()) return 0;
-  return wgrad ? vkas_gemm_tn_tile_choice(M, Np, K) : vkas_gemm_nt_tile_choice(M, Np);
+// The reporters of include/vkas.h: the plan the launchers of gemm_mfma.hip execute, and its kernel's name as rocprofv3 prints it.
+extern "C" int vkas_conv_gemm_plan(int wgrad, const vkas_conv_geom* g, int Np, long lddy, int head_width, int flags, int has_gb,
+                                   const vkas_gemm_switches* sw, vkas_gemm_plan_info* out) {
+  VKAS_CHECK(g && out, "vkas_conv_gemm_plan: null argument");
+  vkas_gemm_plan_info o = {};
+  if (!sw && force_simple()) {
+    snprintf(o.name, sizeof(o.name), wgrad ? "gemm_tn_simple" : "gemm_nt_simple");
+  } else if (wgrad) {
+    const vkas_tn_plan p = vkas_plan_tn(*g, Np, lddy, flags, has_gb != 0, sw ? *sw : *vkas_gemm_env_switches());
+    o = {vkas_tn_kernel_id(p), p.family, p.tile, 0, p.buf, 0, p.pw, p.nobias, p.xg, 0, 0, p.tiles, p.splits, p.rows, p.x_bytes, p.dy_bytes, p.grid, ""};
+    const char* t = p.tile == 128 ? "2,2,4" : (p.tile == 192 ? "2,4,6" : (p.tile == 224 ? "2,4,7" : "4,2,6"));
+    if (p.family == VKAS_TN_SLAB) snprintf(o.name, sizeof(o.name), "conv3x3_wgrad_slab_kernel<%d>", p.tile / 16);
+    else snprintf(o.name, sizeof(o.name), "gemm_tn_mfma_kernel<%s,4>", t);
+  } else {
+    const vkas_nt_plan p = vkas_plan_nt(*g, Np, head_width, sw ? *sw : *vkas_gemm_env_switches());
+    const long tiles = p.grid_m * p.grid_n;
+    o = {vkas_nt_kernel_id(p), p.family, p.bn, p.ring, p.buf, p.head, 0, 0, 0, p.grid_m, p.grid_n, tiles, 1, 0, p.a_bytes, p.b_bytes, (unsigned)tiles, ""};
+    if (p.family == VKAS_NT_SLAB) snprintf(o.name, sizeof(o.name), "conv3x3_slab_mfma_kernel<%d,%d>", p.bn / 32, (int)p.head);
+    else if (p.family == VKAS_NT_RING) snprintf(o.name, sizeof(o.name), "gemm_nt_ring_kernel<%d>", p.ring);
+    else snprintf(o.name, sizeof(o.name), "gemm_nt_mfma_kernel<%s,4,%d>", p.family == VKAS_NT_REG128 ? "2,2" : "4,2", p.bn / 32);
+  }
+  *out = o;
+  return VKAS_OK;
 }
 
-// Which kernel a bf16 call with this geometry runs: 0 plain fp32-FMA kernels forced; fwd: 1 = 128x128, 12 / 13 / 14 =
-// gemm_nt_ring_kernel<2 / 3 / 4>, 128 / 192 / 224 =
-// N extent of the generic 256-row tile, 1000 + TN = conv3x3_slab_mfma_kernel<TN, .> (TN = 4, 6, 7); wgrad: 128 / 192 /
-// 224 generic, 2000 + TNn = conv3x3_wgrad_slab_kernel<TNn>.  head_width > 0: a fused-head launch whose widest head has
-// that many columns.
+extern "C" int vkas_conv_gemm_tile(int wgrad, long M, int Np, int K) {
+  if (force_simple()) return 0;
+  const vkas_gemm_switches& sw = *vkas_gemm_env_switches();
+  return wgrad ? vkas_tn_tile_rule(M, Np, K, sw) : vkas_nt_tile_rule(M, Np, sw);
+}
+
 extern "C" int vkas_conv_gemm_kernel_id(int wgrad, const vkas_conv_geom* g, int Np, long lddy, int head_width) {
-  if (force_simple() || !g) return 0;
-  const long M = (long)g->B * g->Hout * g->Wout;
-  const int K = g->KH * g->KW * g->Cp;
-  if (wgrad) {
-    if (vkas_tn_slab_eligible(g, Np, lddy)) return 2000 + (vkas_tn_slab_n96(Np) ? 6 : (vkas_tn_slab_n112(Np) ? 7 : 8));
-    return vkas_gemm_tn_tile_choice(M, Np, K);
-  }
-  int choice = vkas_gemm_nt_tile_choice(M, Np);
-  if (head_width > 0) choice = head_width <= 128 ? 128 : (head_width <= 192 ? 192 : 224);
-  if (choice != 1 && vkas_nt_slab_eligible(g, Np)) return 1000 + choice / 32;
-  if (choice == 1 && head_width <= 0 && vkas_gemm_nt_ring_stages(g, Np) > 0) return 10 + vkas_gemm_nt_ring_stages(g, Np);
-  return choice;
+  vkas_gemm_plan_info o;
+  return g && vkas_conv_gemm_plan(wgrad, g, Np, lddy, head_width, 0, 0, nullptr, &o) == VKAS_OK ? o.kernel_id : 0;
 }
 
 static int conv_gemm_wgrad(const char* who, const void* x, const vkas_conv_geom* g, const void* dy, long lddy, int Np,

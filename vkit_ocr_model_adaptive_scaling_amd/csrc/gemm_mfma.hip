@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "gemm_parts.h"
+#include "gemm_plan.h"
 
 // This file is compiled twice (csrc/Makefile): for bf16 storage and, with -DVKAS_MFMA_F16, for fp16 storage (config #5 of
 // BASELINE.json).  The two differ in the element type of the operands and in the MFMA opcode (same rate, fp32 accumulate);
@@ -31,15 +32,6 @@ typedef bf16x4 elem4;
 #define VKAS_MFMA16(a, b, c, x, y, z) __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, x, y, z)
 #define VKAS_MFMA_FN(name) name##_bf16
 #endif
-
-// tile / kernel choices shared by both builds (defined once, in the bf16 build)
-int vkas_gemm_nt_tile_choice(long M, int Np);
-int vkas_gemm_tn_tile_choice(long M, int Np, int K);
-bool vkas_nt_slab_eligible(const vkas_conv_geom* g, int Np);
-int vkas_gemm_nt_ring_stages(const vkas_conv_geom* g, int Np);
-bool vkas_tn_slab_eligible(const vkas_conv_geom* g, int Np, long lddy);
-bool vkas_tn_slab_n112(int Np);
-bool vkas_tn_slab_n96(int Np);
 
 namespace {
 
@@ -964,7 +956,7 @@ __global__ __launch_bounds__(512) void conv3x3_slab_mfma_kernel(const elem_t* __
 }
 
 // ---------------------------------------------------------------------------------------------------
-constexpr int TN_ROWS = 64;  // reduction rows per iteration
+constexpr int TN_ROWS = VKAS_TN_ROWS;  // reduction rows per iteration
 
 // acc + lo + hi of a packed pair of 16-bit elements (one v_dot2c_f32_{bf16,f16} against (1, 1); products with 1 are exact)
 __device__ __forceinline__ float dot2_ones(unsigned pair, float acc) {
@@ -1610,287 +1602,81 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_slab_kernel(const elem_t* _
 
 }  // namespace
 
-template <int WM, int WN, int TM, int TN>
-static void launch_nt(const void* x, const vkas_conv_geom* g, const void* Bw, int Np, long M, int K,
-                      const vkas_epilogue* e, hipStream_t st) {
-  constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
-  const long ntn = e->mode == VKAS_EPI_HEAD ? e->head.n_heads : vkas_cdiv(Np, BN);
-  dim3 grid((unsigned)(vkas_cdiv(M, BM) * ntn));
-  // bytes spanned by the operands (x may be a channel slice: last pixel ends after Cp of its ld channels)
-  const long a_bytes = (((long)g->B * g->Hin * g->Win - 1) * g->ldx + g->Cp) * 2;
-  const long b_bytes = (long)Np * K * 2;
-  static const bool no_buf = getenv("VKAS_NT_NOBUF") != nullptr;
-  const bool buf = !no_buf && a_bytes < 0xFFFFFFF0L && b_bytes < 0xFFFFFFF0L;
-  const elem_t* xp = (const elem_t*)x;
-  const elem_t* bp = (const elem_t*)Bw;
-  const unsigned ab = buf ? (unsigned)a_bytes : 0u, bb = buf ? (unsigned)b_bytes : 0u;
-  if (e->mode == VKAS_EPI_HEAD) {
-    if constexpr (WM * WN == 8) {  // the fused head epilogue is instantiated for the 8-wave tiles only
-      if (buf) gemm_nt_mfma_kernel<WM, WN, TM, TN, true, true><<<grid, WM * WN * 64, 0, st>>>(xp, *g, bp, Np, M, K, *e, ab, bb);
-      else gemm_nt_mfma_kernel<WM, WN, TM, TN, false, true><<<grid, WM * WN * 64, 0, st>>>(xp, *g, bp, Np, M, K, *e, ab, bb);
-    }
-  } else if (buf) {
-    gemm_nt_mfma_kernel<WM, WN, TM, TN, true, false><<<grid, WM * WN * 64, 0, st>>>(xp, *g, bp, Np, M, K, *e, ab, bb);
-  } else {
-    gemm_nt_mfma_kernel<WM, WN, TM, TN, false, false><<<grid, WM * WN * 64, 0, st>>>(xp, *g, bp, Np, M, K, *e, ab, bb);
-  }
-}
-
-#ifndef VKAS_MFMA_F16
-// Tile choice of the NT kernel: returns 1 for the 4-wave 128x128 tile, else the N extent (128 / 192 / 224) of the
-// 8-wave 256-row tile.  256-row tiles once there is enough work to fill the chip with them; N extent = the candidate
-// with the least zero padding (ties -> wider tile, fewer re-reads of A).
-int vkas_gemm_nt_tile_choice(long M, int Np) {
-  static const int force = getenv("VKAS_NT_TILE") ? atoi(getenv("VKAS_NT_TILE")) : 0;
-  if (force) return force;
-  if (M < 16384) return 1;
-  long best = -1;
-  int bn = 128;
-  const int cand[3] = {224, 192, 128};
-  for (int c = 0; c < 3; ++c) {
-    const long padded = vkas_cdiv(Np, cand[c]) * cand[c];
-    if (best < 0 || padded < best) {
-      best = padded;
-      bn = cand[c];
-    }
-  }
-  return bn;
-}
-
-// Ring depth of gemm_nt_ring_kernel for a launch the tile choice above gives the 128 x 128 tile (0 = the register-staged
-// kernel).  At most one round of workgroups (<= 256 tiles): four stages (128 KB of LDS, one workgroup per CU, three K tiles in
-// flight) - the launch lasts as long as one workgroup's K loop; more tiles: two stages, so that two workgroups share a CU and
-// one's prologue / epilogue sits behind the other's K loop (profiles/sweep_small.py: 4 stages 26.6 / 37.1 us against 31.7 /
-// 52.1 at M = 7 168, N = 512, K = 2 048 / M = 1 792, N = 1 024, K = 4 096; 2 stages 34.2 against 44.3 at M = 7 168,
-// N = 2 048, K = 512; the register-staged kernel: 42.2, 70.2 and 40.0).  VKAS_NT_RING = 0 keeps the register-staged kernel,
-// 2 / 3 / 4 force a depth.
-int vkas_gemm_nt_ring_stages(const vkas_conv_geom* g, int Np) {
-  static const int ring_env = getenv("VKAS_NT_RING") ? atoi(getenv("VKAS_NT_RING")) : -1;
-  const long M = (long)g->B * g->Hout * g->Wout;
-  const long K = (long)g->KH * g->KW * g->Cp;
-  const long a_bytes = (((long)g->B * g->Hin * g->Win - 1) * g->ldx + g->Cp) * 2;
-  if (a_bytes >= 0xFFFFFFF0L || (long)Np * K * 2 >= 0xFFFFFFF0L) return 0;  // operands addressed with 32-bit buffer offsets
-  if (ring_env >= 0) return ring_env >= 2 && ring_env <= 4 ? ring_env : 0;
-  return vkas_cdiv(M, 128) * vkas_cdiv(Np, 128) <= 256 ? 4 : 2;
-}
-
-static bool row_aligned_3x3(const vkas_conv_geom* g, int wmod) {
-  return g->KH == 3 && g->KW == 3 && g->stride == 1 && g->pad == 1 && g->Hout == g->Hin && g->Wout == g->Win &&
-         g->Win % wmod == 0;
-}
-
-// conv3x3_slab_mfma_kernel: rows of whole 256-pixel tiles, operands addressable with 32-bit buffer offsets
-bool vkas_nt_slab_eligible(const vkas_conv_geom* g, int Np) {
-  static const bool no_slab = getenv("VKAS_NT_NOSLAB") != nullptr;
-  const long K = (long)g->KH * g->KW * g->Cp;
-  const long a_bytes = (((long)g->B * g->Hin * g->Win - 1) * g->ldx + g->Cp) * 2;
-  return !no_slab && row_aligned_3x3(g, 256) && a_bytes < 0xFFFFFFF0L && (long)Np * K * 2 < 0xFFFFFFF0L;
-}
-
-// conv3x3_wgrad_slab_kernel: rows of whole 64-pixel chunks, at least one full n tile and channel block
-bool vkas_tn_slab_eligible(const vkas_conv_geom* g, int Np, long lddy) {
-  static const bool no_slab = getenv("VKAS_TN_NOSLAB") != nullptr;
-  const long M = (long)g->B * g->Hout * g->Wout;
-  const long x_bytes = (((long)g->B * g->Hin * g->Win - 1) * g->ldx + g->Cp) * 2;
-  const long dy_bytes = ((M - 1) * lddy + Np) * 2;
-  return !no_slab && row_aligned_3x3(g, 64) && M >= 65536 && Np >= 112 && g->Cp >= 128 && x_bytes < 0xFFFFFFF0L &&
-         dy_bytes < 0xFFFFFFF0L;
-}
-#ifdef VKAS_TRACE
+#if defined(VKAS_TRACE) && !defined(VKAS_MFMA_F16)
 extern "C" int vkas_trace_read(void* dst, size_t bytes) {
   return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(vkas_trace_buf), bytes, 0, hipMemcpyDeviceToHost);
 }
 #endif
-bool vkas_tn_slab_n112(int Np) { return vkas_cdiv(Np, 112) * 112 < vkas_cdiv(Np, 128) * 128; }  // 112-wide tiles pad less
-// 96-wide tiles when they pad less than both wider ones (N = 192: no padding against 224 / 256 columns)
-bool vkas_tn_slab_n96(int Np) {
-  static const bool off = getenv("VKAS_TN_NO96") != nullptr;
-  const long p96 = vkas_cdiv(Np, 96) * 96;
-  return !off && p96 < vkas_cdiv(Np, 112) * 112 && p96 < vkas_cdiv(Np, 128) * 128;
-}
 
-#endif  // VKAS_MFMA_F16
+// The launchers execute the plan of gemm_plan.h: one case per kernel instantiation.
+static constexpr int nt_case(int family, int v, bool buf, bool head) { return ((family * 8 + v) * 2 + buf) * 2 + head; }
+static constexpr int tn_case(int family, int tile, bool xg, int form) { return ((family * 512 + tile) * 2 + xg) * 4 + form; }
 
 int VKAS_MFMA_FN(vkas_gemm_nt_mfma)(const void* x, const vkas_conv_geom* g, const void* Bw, int Np, const vkas_epilogue* e,
                            hipStream_t st) {
   const long M = (long)g->B * g->Hout * g->Wout;
   const int K = g->KH * g->KW * g->Cp;
   if (M == 0) return VKAS_OK;
-  int choice = vkas_gemm_nt_tile_choice(M, Np);
-  if (e->mode == VKAS_EPI_HEAD) {  // one 256-row tile per head: the narrowest N extent that holds the widest head
-    int wmax = 0;
-    for (int h = 0; h < e->head.n_heads; ++h) wmax = e->head.np[h] > wmax ? e->head.np[h] : wmax;
-    choice = wmax <= 128 ? 128 : (wmax <= 192 ? 192 : 224);
+  const bool head = e->mode == VKAS_EPI_HEAD;
+  int wmax = 0;
+  for (int h = 0; head && h < e->head.n_heads; ++h) wmax = e->head.np[h] > wmax ? e->head.np[h] : wmax;
+  const vkas_nt_plan p = vkas_plan_nt(*g, Np, wmax, *vkas_gemm_env_switches());
+  const dim3 grid((unsigned)(p.grid_m * (head ? e->head.n_heads : p.grid_n)));
+  const unsigned ab = p.buf ? (unsigned)p.a_bytes : 0u, bb = p.buf ? (unsigned)p.b_bytes : 0u;
+#define VKAS_GO(THREADS, ...) \
+  __VA_ARGS__<<<grid, THREADS, 0, st>>>((const elem_t*)x, *g, (const elem_t*)Bw, Np, M, K, *e, ab, bb); \
+  break;
+  // the 256-row tile of N extent 32 TNV, buffer / non-buffer x plain / fused head, and the row slab of that extent
+#define VKAS_TILE(TNV)                                                                                      \
+  case nt_case(VKAS_NT_TILE256, TNV, true, true): VKAS_GO(512, gemm_nt_mfma_kernel<4, 2, 4, TNV, true, true>)    \
+  case nt_case(VKAS_NT_TILE256, TNV, false, true): VKAS_GO(512, gemm_nt_mfma_kernel<4, 2, 4, TNV, false, true>)  \
+  case nt_case(VKAS_NT_TILE256, TNV, true, false): VKAS_GO(512, gemm_nt_mfma_kernel<4, 2, 4, TNV, true, false>)  \
+  case nt_case(VKAS_NT_TILE256, TNV, false, false): VKAS_GO(512, gemm_nt_mfma_kernel<4, 2, 4, TNV, false, false>) \
+  case nt_case(VKAS_NT_SLAB, TNV, true, true): VKAS_GO(512, conv3x3_slab_mfma_kernel<TNV, true>)                \
+  case nt_case(VKAS_NT_SLAB, TNV, true, false): VKAS_GO(512, conv3x3_slab_mfma_kernel<TNV, false>)
+  switch (nt_case(p.family, p.family == VKAS_NT_RING ? p.ring : p.bn / 32, p.buf, p.head)) {
+    VKAS_TILE(4) VKAS_TILE(6) VKAS_TILE(7)
+    case nt_case(VKAS_NT_REG128, 4, true, false): VKAS_GO(256, gemm_nt_mfma_kernel<2, 2, 4, 4, true, false>)
+    case nt_case(VKAS_NT_REG128, 4, false, false): VKAS_GO(256, gemm_nt_mfma_kernel<2, 2, 4, 4, false, false>)
+    case nt_case(VKAS_NT_RING, 2, true, false): VKAS_GO(512, gemm_nt_ring_kernel<2>)
+    case nt_case(VKAS_NT_RING, 3, true, false): VKAS_GO(512, gemm_nt_ring_kernel<3>)
+    case nt_case(VKAS_NT_RING, 4, true, false): VKAS_GO(512, gemm_nt_ring_kernel<4>)
+    default: VKAS_CHECK(false, "gemm_nt_mfma: no kernel for family %d, N extent %d", (int)p.family, p.bn);
   }
-  const bool big = choice != 1;
-  const int bn = big ? choice : 128;
-  // 3x3 / stride 1 / pad 1 with rows of whole 256-pixel tiles: the row-slab kernel
-  const long a_bytes = (((long)g->B * g->Hin * g->Win - 1) * g->ldx + g->Cp) * 2;
-  const long b_bytes = (long)Np * K * 2;
-  if (big && vkas_nt_slab_eligible(g, Np)) {
-    const bool head = e->mode == VKAS_EPI_HEAD;
-    const long ntn = head ? e->head.n_heads : vkas_cdiv(Np, bn);
-    dim3 grid((unsigned)((M / 256) * ntn));
-    const elem_t* xp = (const elem_t*)x;
-    const elem_t* bp = (const elem_t*)Bw;
-#define VKAS_SLAB(TNV)                                                                                                  \
-  if (head) conv3x3_slab_mfma_kernel<TNV, true><<<grid, 512, 0, st>>>(xp, *g, bp, Np, M, K, *e, (unsigned)a_bytes, (unsigned)b_bytes); \
-  else conv3x3_slab_mfma_kernel<TNV, false><<<grid, 512, 0, st>>>(xp, *g, bp, Np, M, K, *e, (unsigned)a_bytes, (unsigned)b_bytes);
-    if (bn == 224) { VKAS_SLAB(7) }
-    else if (bn == 192) { VKAS_SLAB(6) }
-    else { VKAS_SLAB(4) }
-#undef VKAS_SLAB
-    VKAS_LAUNCH_CHECK("conv3x3_slab_mfma");
-    return VKAS_OK;
-  }
-  if (!big) {
-    const int nst = e->mode == VKAS_EPI_HEAD ? 0 : vkas_gemm_nt_ring_stages(g, Np);
-    if (nst >= 2) {
-      dim3 grid((unsigned)(vkas_cdiv(M, 128) * vkas_cdiv(Np, 128)));
-      const elem_t* xp = (const elem_t*)x;
-      const elem_t* bp = (const elem_t*)Bw;
-      if (nst == 2) gemm_nt_ring_kernel<2><<<grid, 512, 0, st>>>(xp, *g, bp, Np, M, K, *e, (unsigned)a_bytes, (unsigned)b_bytes);
-      else if (nst == 3) gemm_nt_ring_kernel<3><<<grid, 512, 0, st>>>(xp, *g, bp, Np, M, K, *e, (unsigned)a_bytes, (unsigned)b_bytes);
-      else gemm_nt_ring_kernel<4><<<grid, 512, 0, st>>>(xp, *g, bp, Np, M, K, *e, (unsigned)a_bytes, (unsigned)b_bytes);
-      VKAS_LAUNCH_CHECK("gemm_nt_ring");
-      return VKAS_OK;
-    }
-    launch_nt<2, 2, 4, 4>(x, g, Bw, Np, M, K, e, st);
-  }
-  else if (bn == 224) launch_nt<4, 2, 4, 7>(x, g, Bw, Np, M, K, e, st);
-  else if (bn == 192) launch_nt<4, 2, 4, 6>(x, g, Bw, Np, M, K, e, st);
-  else launch_nt<4, 2, 4, 4>(x, g, Bw, Np, M, K, e, st);
-  VKAS_LAUNCH_CHECK("gemm_nt_mfma");
+#undef VKAS_TILE
+#undef VKAS_GO
+  static const char* const who[] = {"gemm_nt_mfma", "gemm_nt_ring", "gemm_nt_mfma", "conv3x3_slab_mfma"};
+  VKAS_LAUNCH_CHECK(who[p.family]);
   return VKAS_OK;
 }
-
-template <int WN, int WK, int TNn, int TK, bool XG>
-static void launch_tn(const void* x, const vkas_conv_geom* g, const void* dy, long lddy, int Np, long M, int K, float* gw,
-                      float* gb, bool one_split, hipStream_t st) {
-  constexpr int BNn = WN * TNn * 16, BKc = WK * TK * 16;
-  const long tiles = vkas_cdiv(Np, BNn) * vkas_cdiv(K, BKc);
-  // Splits over M: pick the count that minimises a two-term cost model.
-  //   main loop: rounds of resident workgroups (256 CUs x 1 block of 8 waves | 2 blocks of 4) x 64-row iterations of a
-  //     split x time per iteration (measured: ~1.2 us for the 8-wave tiles, ~0.5 us for the 4-wave tile);
-  //   reduction: every split adds a full copy of its tile with fp32 atomics, ~1.3 TB/s chip-wide (MI355X_MICROARCH.md).
-  // On the stage-3/4 weight gradients (M = 16-64 K rows) the atomic tail was half the launch with the old "3 rounds"
-  // rule.  Ties go to multiples of 8 (whole splits per XCD, see the kernel's work order).
-  const long resident = 256L * (WN * WK >= 8 ? 1 : 2);
-  const double t_iter = WN * WK >= 8 ? 1.2e-6 : 0.5e-6;
-  const double tile_bytes = (double)BNn * BKc * 4.0;
-  // one_split: every output tile is reduced over all M rows by one workgroup, in row order, and added once to the zeroed
-  // gw: the result does not depend on the order workgroups run in (vkas_conv_gemm_wgrad_ordered)
-  const long max_splits = one_split ? 1 : vkas_cdiv(M, 4 * TN_ROWS);
-  long splits = 1;
-  double best_t = 1e30;
-  for (long sp = 1; sp <= max_splits && sp * tiles <= 8 * resident; ++sp) {
-    const long blocks = sp * tiles;
-    const double t = (double)vkas_cdiv(blocks, resident) * (double)vkas_cdiv(vkas_cdiv(M, sp), TN_ROWS) * t_iter +
-                     (double)blocks * tile_bytes / 1.3e12;
-    if (t < best_t * (sp % 8 == 0 ? 1.02 : 0.999)) {
-      best_t = t;
-      splits = sp;
-    }
-  }
-  if (splits > 65535) splits = 65535;
-  long rows = vkas_cdiv(M, splits);
-  rows = vkas_cdiv(rows, TN_ROWS) * TN_ROWS;
-  splits = vkas_cdiv(M, rows);
-  dim3 grid((unsigned)(tiles * splits));
-  const long x_bytes = (((long)g->B * g->Hin * g->Win - 1) * g->ldx + g->Cp) * 2;
-  const long dy_bytes = ((M - 1) * lddy + Np) * 2;
-  static const bool no_buf = getenv("VKAS_TN_NOBUF") != nullptr;
-  const bool pointwise = g->KH == 1 && g->KW == 1 && g->stride == 1 && g->pad == 0 && g->Hin == g->Hout && g->Win == g->Wout;
-  if (!no_buf && x_bytes < 0xFFFFFFF0L && dy_bytes < 0xFFFFFFF0L && pointwise && gb == nullptr && !XG && TNn == 6)
-    gemm_tn_mfma_kernel<WN, WK, TNn, TK, true, XG, true, !XG && TNn == 6><<<grid, WN * WK * 64, 0, st>>>(
-        (const elem_t*)x, *g, (const elem_t*)dy, lddy, Np, M, K, rows, gw, gb, (unsigned)x_bytes, (unsigned)dy_bytes);
-  else if (!no_buf && x_bytes < 0xFFFFFFF0L && dy_bytes < 0xFFFFFFF0L && pointwise)
-    gemm_tn_mfma_kernel<WN, WK, TNn, TK, true, XG, true><<<grid, WN * WK * 64, 0, st>>>(
-        (const elem_t*)x, *g, (const elem_t*)dy, lddy, Np, M, K, rows, gw, gb, (unsigned)x_bytes, (unsigned)dy_bytes);
-  else if (!no_buf && x_bytes < 0xFFFFFFF0L && dy_bytes < 0xFFFFFFF0L)
-    gemm_tn_mfma_kernel<WN, WK, TNn, TK, true, XG><<<grid, WN * WK * 64, 0, st>>>((const elem_t*)x, *g, (const elem_t*)dy, lddy, Np,
-                                                                             M, K, rows, gw, gb, (unsigned)x_bytes,
-                                                                             (unsigned)dy_bytes);
-  else
-    gemm_tn_mfma_kernel<WN, WK, TNn, TK, false, XG><<<grid, WN * WK * 64, 0, st>>>((const elem_t*)x, *g, (const elem_t*)dy, lddy,
-                                                                              Np, M, K, rows, gw, gb, 0u, 0u);
-}
-
-#ifndef VKAS_MFMA_F16
-// Tile choice of the TN (wgrad) kernel: N extent 128 (4 waves, 128 K columns), 192 / 224 (8 waves, 256 K columns) or 384 (8 waves, 128 K columns):
-// 8-wave tiles when there is enough work and K is wide enough; N extent = least zero padding.
-int vkas_gemm_tn_tile_choice(long M, int Np, int K) {
-  static const int force = getenv("VKAS_TN_TILE") ? atoi(getenv("VKAS_TN_TILE")) : 0;
-  if (force) return force;
-  int bn = 128;
-  if (M >= 16384 && K >= 192) {
-    long best = vkas_cdiv(Np, 128) * 128;
-    const int cand[2] = {192, 224};
-    for (int c = 0; c < 2; ++c) {
-      const long padded = vkas_cdiv(Np, cand[c]) * cand[c];
-      if (padded <= best) {
-        best = padded;
-        bn = cand[c];
-      }
-    }
-    // 384 (N) x 128 (K) instead of 192 x 256 - the same 96 x 64 per wave - where the 256-wide K tiles would be padded and the
-    // 128-wide ones are not (K = 384: the W1 weight gradient of a C = 384 ConvNeXt MLP ran a quarter of its products on zeros)
-    if (bn == 192 && Np % 384 == 0 && vkas_cdiv(K, 128) * 128 < vkas_cdiv(K, 256) * 256) bn = 384;
-  }
-  return bn;
-}
-
-#endif  // VKAS_MFMA_F16
 
 int VKAS_MFMA_FN(vkas_gemm_tn_mfma)(const void* x, const vkas_conv_geom* g, const void* dy, long lddy, int Np, float* gw,
                            float* gb, int flags, hipStream_t st) {
   const long M = (long)g->B * g->Hout * g->Wout;
   const int K = g->KH * g->KW * g->Cp;
   if (M == 0) return VKAS_OK;
-  const bool x_gelu = (flags & 1) != 0, one_split = (flags & 2) != 0;
-  // row-aligned 3x3 / stride 1 / pad 1 with wide operands: the slab kernel
-  const long x_bytes = (((long)g->B * g->Hin * g->Win - 1) * g->ldx + g->Cp) * 2;
-  const long dy_bytes = ((M - 1) * lddy + Np) * 2;
-  if (!x_gelu && !one_split && vkas_tn_slab_eligible(g, Np, lddy)) {
-    const bool n96 = vkas_tn_slab_n96(Np);
-    const bool n112 = !n96 && vkas_tn_slab_n112(Np);
-    const long tiles = vkas_cdiv(Np, n96 ? 96 : (n112 ? 112 : 128)) * 3 * vkas_cdiv(g->Cp, 128);
-    const long chunks = M / 64;
-    // Pixel splits: whole splits per XCD (multiple of 8).  The tiles of one split walk the same dy / x chunks at the same
-    // time and share them through that XCD's L2 (every operand byte is used by 9 tiles): keeping a split's tiles
-    // together matters more than filling the last round of workgroups (a round-balanced, XCD-straddling split count
-    // measured 5% slower).  About 3 rounds of the 256 resident workgroups, at least 16 chunks per split.
-    long splits = vkas_cdiv(3 * 256, tiles);
-    splits = vkas_cdiv(splits, 8) * 8;
-    if (splits > chunks / 16) splits = chunks / 16 > 0 ? chunks / 16 : 1;
-    const long cps = vkas_cdiv(chunks, splits);
-    splits = vkas_cdiv(chunks, cps);
-    if (n96)
-      conv3x3_wgrad_slab_kernel<6><<<(unsigned)(tiles * splits), 512, 0, st>>>((const elem_t*)x, *g, (const elem_t*)dy, lddy, Np, M,
-                                                                               K, (int)cps, gw, gb, (unsigned)x_bytes,
-                                                                               (unsigned)dy_bytes);
-    else if (n112)
-      conv3x3_wgrad_slab_kernel<7><<<(unsigned)(tiles * splits), 512, 0, st>>>((const elem_t*)x, *g, (const elem_t*)dy, lddy, Np, M,
-                                                                               K, (int)cps, gw, gb, (unsigned)x_bytes,
-                                                                               (unsigned)dy_bytes);
-    else
-      conv3x3_wgrad_slab_kernel<8><<<(unsigned)(tiles * splits), 512, 0, st>>>((const elem_t*)x, *g, (const elem_t*)dy, lddy, Np, M,
-                                                                               K, (int)cps, gw, gb, (unsigned)x_bytes,
-                                                                               (unsigned)dy_bytes);
-    VKAS_LAUNCH_CHECK("conv3x3_wgrad_slab");
-    return VKAS_OK;
+  const vkas_tn_plan p = vkas_plan_tn(*g, Np, lddy, flags, gb != nullptr, *vkas_gemm_env_switches());
+  const unsigned xb = p.buf ? (unsigned)p.x_bytes : 0u, db = p.buf ? (unsigned)p.dy_bytes : 0u;
+#define VKAS_GO(THREADS, ROWS, ...) \
+  __VA_ARGS__<<<p.grid, THREADS, 0, st>>>((const elem_t*)x, *g, (const elem_t*)dy, lddy, Np, M, K, ROWS, gw, gb, xb, db); \
+  break;
+  // one generic tile: non-buffer, buffer, buffer + pointwise (form 0 / 1 / 2)
+#define VKAS_TILE(WN, WK, TNn, XG)                                                                                             \
+  case tn_case(VKAS_TN_GENERIC, WN * TNn * 16, XG, 0): VKAS_GO(WN * WK * 64, p.rows, gemm_tn_mfma_kernel<WN, WK, TNn, 4, false, XG>) \
+  case tn_case(VKAS_TN_GENERIC, WN * TNn * 16, XG, 1): VKAS_GO(WN * WK * 64, p.rows, gemm_tn_mfma_kernel<WN, WK, TNn, 4, true, XG>)  \
+  case tn_case(VKAS_TN_GENERIC, WN * TNn * 16, XG, 2): VKAS_GO(WN * WK * 64, p.rows, gemm_tn_mfma_kernel<WN, WK, TNn, 4, true, XG, true>)
+  switch (tn_case(p.family, p.tile, p.xg, p.nobias ? 3 : (p.pw ? 2 : p.buf))) {
+    VKAS_TILE(2, 2, 4, false) VKAS_TILE(2, 4, 6, false) VKAS_TILE(2, 4, 7, false) VKAS_TILE(4, 2, 6, false)
+    VKAS_TILE(2, 2, 4, true) VKAS_TILE(2, 4, 6, true) VKAS_TILE(2, 4, 7, true) VKAS_TILE(4, 2, 6, true)
+    case tn_case(VKAS_TN_GENERIC, 192, false, 3): VKAS_GO(512, p.rows, gemm_tn_mfma_kernel<2, 4, 6, 4, true, false, true, true>)
+    case tn_case(VKAS_TN_GENERIC, 384, false, 3): VKAS_GO(512, p.rows, gemm_tn_mfma_kernel<4, 2, 6, 4, true, false, true, true>)
+    case tn_case(VKAS_TN_SLAB, 96, false, 1): VKAS_GO(512, (int)p.rows, conv3x3_wgrad_slab_kernel<6>)
+    case tn_case(VKAS_TN_SLAB, 112, false, 1): VKAS_GO(512, (int)p.rows, conv3x3_wgrad_slab_kernel<7>)
+    case tn_case(VKAS_TN_SLAB, 128, false, 1): VKAS_GO(512, (int)p.rows, conv3x3_wgrad_slab_kernel<8>)
+    default: VKAS_CHECK(false, "gemm_tn_mfma: no kernel for family %d, tile %d", (int)p.family, p.tile);
   }
-  const int bn = vkas_gemm_tn_tile_choice(M, Np, K);
-  if (bn == 384) {
-    if (x_gelu) launch_tn<4, 2, 6, 4, true>(x, g, dy, lddy, Np, M, K, gw, gb, one_split, st);
-    else launch_tn<4, 2, 6, 4, false>(x, g, dy, lddy, Np, M, K, gw, gb, one_split, st);
-  } else if (x_gelu) {
-    if (bn == 224) launch_tn<2, 4, 7, 4, true>(x, g, dy, lddy, Np, M, K, gw, gb, one_split, st);
-    else if (bn == 192) launch_tn<2, 4, 6, 4, true>(x, g, dy, lddy, Np, M, K, gw, gb, one_split, st);
-    else launch_tn<2, 2, 4, 4, true>(x, g, dy, lddy, Np, M, K, gw, gb, one_split, st);
-  } else if (bn == 224) launch_tn<2, 4, 7, 4, false>(x, g, dy, lddy, Np, M, K, gw, gb, one_split, st);
-  else if (bn == 192) launch_tn<2, 4, 6, 4, false>(x, g, dy, lddy, Np, M, K, gw, gb, one_split, st);
-  else launch_tn<2, 2, 4, 4, false>(x, g, dy, lddy, Np, M, K, gw, gb, one_split, st);
-  VKAS_LAUNCH_CHECK("gemm_tn_mfma");
+#undef VKAS_TILE
+#undef VKAS_GO
+  VKAS_LAUNCH_CHECK(p.family == VKAS_TN_SLAB ? "conv3x3_wgrad_slab" : "gemm_tn_mfma");
   return VKAS_OK;
 }

@@ -360,23 +360,14 @@ class LaunchTimer:
 TIMER: Optional[LaunchTimer] = None
 
 
-def nt_kernel_name(kid: int, head: bool) -> str:
-    """rocprofv3-style short name (profiles/parse_pmc.py) of the kernel behind a vkas_conv_gemm_kernel_id() code."""
-    if kid == 0:
-        return 'gemm_nt_simple'
-    if kid >= 1000:
-        return 'conv3x3_slab_mfma_kernel<%d,%d>' % (kid - 1000, int(head))
-    if 12 <= kid <= 14:
-        return 'gemm_nt_ring_kernel<%d>' % (kid - 10)
-    return 'gemm_nt_mfma_kernel<%s>' % {1: '2,2,4,4', 128: '4,2,4,4', 192: '4,2,4,6', 224: '4,2,4,7'}[kid]
-
-
-def tn_kernel_name(kid: int) -> str:
-    if kid == 0:
-        return 'gemm_tn_simple'
-    if kid >= 2000:
-        return 'conv3x3_wgrad_slab_kernel<%d>' % (kid - 2000)
-    return 'gemm_tn_mfma_kernel<%s>' % {128: '2,2,4,4', 192: '2,4,6,4', 224: '2,4,7,4', 384: '4,2,6,4'}[kid]
+def gemm_kernel_name(x, wgrad, geom, Np, lddy=0, head_width=0, flags=0, has_gb=False) -> str:
+    """rocprofv3-style short name (profiles/parse_pmc.py) of the kernel this call reaches: the launchers' own plan."""
+    if x.dtype not in _MFMA_DTYPES:
+        return 'gemm_tn_simple' if wgrad else 'gemm_nt_simple'
+    info = _lib.GemmPlanInfo()
+    check(lib.vkas_conv_gemm_plan(wgrad, ctypes.byref(geom), Np, lddy, head_width, flags, int(has_gb), None, ctypes.byref(info)),
+          'conv_gemm_plan')
+    return info.name.decode()
 
 
 def _timed(kind, x, flops, M, N, K, fn, nbytes=0.0):
@@ -397,11 +388,7 @@ def conv_gemm(x: torch.Tensor, geom: ConvGeom, Bw: torch.Tensor, Np: int, out: t
         # algorithmic FLOPs use the logical (unpadded) N and K when the caller knows them
         M = geom.B * geom.Hout * geom.Wout
         N, K = nk if nk is not None else (Np, geom.KH * geom.KW * geom.Cp)
-        if x.dtype in _MFMA_DTYPES:
-            wmax = max(head.np[i] for i in range(head.n_heads)) if head is not None else 0
-            kind = nt_kernel_name(lib.vkas_conv_gemm_kernel_id(0, ctypes.byref(geom), Np, 0, wmax), head is not None)
-        else:
-            kind = 'gemm_nt_simple'
+        kind = gemm_kernel_name(x, 0, geom, Np, head_width=max(head.np[i] for i in range(head.n_heads)) if head is not None else 0)
         es = x.element_size()
         nbytes = (geom.B * geom.Hin * geom.Win * geom.Cp + M * Np * ((out is not None) + (out2 is not None) + (aux is not None))) * es
         return _timed(kind, x, 2.0 * M * N * K, M, N, K,
@@ -492,13 +479,9 @@ def conv_wgrad(x: torch.Tensor, geom: ConvGeom, dy: torch.Tensor, Np: int, nk=No
         fn = lib.vkas_conv_gemm_wgrad_gelu if x_gelu else lib.vkas_conv_gemm_wgrad
         check(fn(_p(x), ctypes.byref(geom), _p(dy), act_ld(dy), Np, _p(gw), _p(gb), _dt(x), _stream()), 'conv_gemm_wgrad')
         return (gw, gb) if with_bias else gw
-    if x.dtype in _MFMA_DTYPES:
-        kid = lib.vkas_conv_gemm_kernel_id(1, ctypes.byref(geom), Np, act_ld(dy), 0)
-        if x_gelu and kid >= 2000:  # the gelu-on-load variant exists for the generic kernel only
-            kid = lib.vkas_conv_gemm_tile(1, M, Np, K)
-        kind = tn_kernel_name(kid)
-    else:
-        kind = 'gemm_tn_simple'
+    if TIMER is None:
+        return run()
+    kind = gemm_kernel_name(x, 1, geom, Np, act_ld(dy), flags=int(x_gelu) + 2 * int(ordered), has_gb=gb is not None)
     N, Kl = nk if nk is not None else (Np, K)
     nbytes = (geom.B * geom.Hin * geom.Win * geom.Cp + M * Np) * x.element_size() + 4.0 * Np * K
     return _timed(kind, x, 2.0 * M * N * Kl, M, N, Kl, run, nbytes)
