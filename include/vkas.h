@@ -498,6 +498,26 @@ long long vkas_text_regions_workspace_bytes(int B, int H, int W, int max_regions
 int vkas_text_regions(const unsigned char* mask, const float* height, int B, int H, int W, int max_regions, void* workspace,
                       long long workspace_bytes, int* count, int* labels, int* boxes, int* areas, int* valid, float* medians,
                       void* stream);
+/* Crop, rescale and pack text regions into the page of the precise pass (:190-293 restated on pixels; the resampling rule
+ * in integers and the host oracles: inferencing/packing.py).  src (Hs,Ws,3) uint8; placements (n,8) int32 rows (sy, sx, sh,
+ * sw, dy, dx, dh, dw): source rectangle [sy,sy+sh) x [sx,sx+sw) inside src -> destination rectangle [dy,dy+dh) x
+ * [dx,dx+dw) inside page (Hp,Wp,3) uint8; sides 1..8192; destinations pairwise disjoint (the caller's check: the table
+ * lives in device memory).  Per axis, S -> D samples: D < S area coverage, D >= S two-tap bilinear with half-pixel centres
+ * and clamped taps; a channel = (sum wy*wx*p + den/2) / den, integers only.  EVERY page byte is written: resampled pixels
+ * inside the placements, 0 elsewhere; n = 0 gives a zero page.  A row whose sides or source rectangle are out of range is
+ * skipped, so no table content makes the kernel read outside src or write outside page.  One launch; capture-safe: no
+ * allocation, no synchronisation, no atomics.  Hs, Ws, Hp, Wp in 1..32768; table 16-byte aligned. */
+int vkas_resample_pack_u8(const unsigned char* src, int Hs, int Ws, const int* placements, int n, unsigned char* page,
+                          int Hp, int Wp, void* stream);
+/* The region-label page that goes with it: out (Hq,Wq) int32 at 1/fdf of the page.  A label pixel (v,u) whose centre
+ * (v*fdf + fdf/2, u*fdf + fdf/2) lies in the destination of placement k gets region_ids[k] - unless the rough label map
+ * (labels (Hl,Wl) int32, of which valid_h x valid_w cover the Hs x Ws image the sources refer to) holds the label of ANOTHER
+ * region (neither 0 nor region_ids[k]) at the pixel's source position; then, and outside every placement, it gets 0.  Source
+ * position: map row min(valid_h - 1, ((2*dh*sy + t*sh) * valid_h) / (2*dh*Hs)) with t = 2*v*fdf + fdf - 2*dy; columns
+ * likewise.  Every out element is written; same contract as above otherwise; fdf in 1..64. */
+int vkas_pack_region_labels(const int* labels, int Hl, int Wl, int valid_h, int valid_w, int Hs, int Ws,
+                            const int* placements, const int* region_ids, int n, int fdf, int* out, int Hq, int Wq,
+                            void* stream);
 
 /* ---- optimizer on the flat parameter / gradient buffers: train.py:468-478 ------------------------------ */
 /* sumsq (1 double, zeroed by the call) = sum g^2 */

@@ -185,6 +185,9 @@ _SIGS = {
                                    _P, _P, _P, _P, _P]),
     'vkas_text_regions_workspace_bytes': (c_longlong, [c_int, c_int, c_int, c_int]),
     'vkas_text_regions': (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, c_longlong, _P, _P, _P, _P, _P, _P, _P]),
+    'vkas_resample_pack_u8': (c_int, [_P, c_int, c_int, _P, c_int, _P, c_int, c_int, _P]),
+    'vkas_pack_region_labels': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, c_int, _P, c_int, c_int,
+                                        _P]),
     'vkas_l2norm_sq': (c_int, [_P, c_long, _P, _P]),
     'vkas_adamw_step': (c_int, [_P, _P, _P, _P, c_long, _P, c_float, c_float, c_float, c_float, c_float, c_float,
                                 c_float, c_int, _P]),

@@ -1,0 +1,296 @@
+// Crop, rescale and pack the text regions into the page of the precise pass (inferencing/adaptive_scaling.py:190-293 restated
+// on pixels; the rule and the host oracles: inferencing/packing.py): a variable-ratio gather / resample of 3-byte pixels from
+// one source image into the disjoint rectangles of a packed page, and the int32 region-label page that goes with it.
+//
+// Both kernels are driven from the output.  A workgroup owns a tile of TILE_H x TILE_W output cells (page pixels / label
+// pixels) and first searches the placement table for the rows that reach into its tile: every wave takes 64 rows at a time,
+// ballots the hits and appends (row index, hit rectangle clipped to the tile) to its own list in LDS - no atomics, and the
+// order is irrelevant because destinations are disjoint, which also bounds a list by the tile's cell count.  Then every
+// thread resolves the owner of its four adjacent cells from the lists (wave-uniform LDS reads) and produces them: 12 bytes
+// of page (three aligned dword stores when Wp % 4 == 0) or four labels (one 16-byte store when Wq % 4 == 0).  Every output
+// byte is written exactly once - zero where no placement reaches - so a call leaves nothing of the buffer's earlier contents.
+//
+// The source pixels are gathered directly (byte loads through the vector L1): see DESIGN.md for why this first version
+// does not stage source rows in LDS.  All arithmetic is integer: inner row sums in 32 bits, the outer sum in 64, one
+// rounding division by the product of the axis denominators.
+#include "vkas_common.h"
+
+namespace {
+
+constexpr int TILE_H = 16, TILE_W = 64, QUAD = 4;           // cells per tile; cells per thread along x
+constexpr int THREADS = TILE_H * TILE_W / QUAD;             // 256
+constexpr int WAVES = THREADS / 64;
+constexpr int LIST_CAP = TILE_H * TILE_W;                   // disjoint placements: at most one per cell of the tile
+constexpr int SIDE_MAX = 8192;
+constexpr int DIM_MAX = 32768;                              // source / page sides: pixel counts stay below 2^30
+
+struct Placement {
+  int sy, sx, sh, sw, dy, dx, dh, dw;
+};
+
+__device__ __forceinline__ Placement load_placement(const int* __restrict__ table, int i) {
+  const int4 a = *reinterpret_cast<const int4*>(table + (long)i * 8);
+  const int4 b = *reinterpret_cast<const int4*>(table + (long)i * 8 + 4);
+  return Placement{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+}
+
+// the kernels trust the host's disjointness check, but never a row's bounds: a row that fails here is treated as absent,
+// so no table content can make a kernel read outside the source (writes are bounded by the output tile in any case)
+__device__ __forceinline__ bool placement_ok(const Placement& p, int Hs, int Ws) {
+  return p.sh >= 1 && p.sw >= 1 && p.dh >= 1 && p.dw >= 1 && p.sh <= SIDE_MAX && p.sw <= SIDE_MAX && p.dh <= SIDE_MAX &&
+         p.dw <= SIDE_MAX && p.sy >= 0 && p.sx >= 0 && p.sy <= Hs - p.sh && p.sx <= Ws - p.sw && p.dy >= 0 && p.dx >= 0 &&
+         p.dy <= DIM_MAX && p.dx <= DIM_MAX;
+}
+
+// cells [lo, hi) of one axis whose centres c*f + f/2 lie in the page interval [d0, d0 + dlen); f == 1: the pixels themselves
+__device__ __forceinline__ void cell_range(int d0, int dlen, int f, int& lo, int& hi) {
+  const int a = 2 * d0 - f, b = 2 * (d0 + dlen) - f;
+  lo = a <= 0 ? 0 : (a + 2 * f - 1) / (2 * f);
+  hi = b <= 0 ? 0 : (b + 2 * f - 1) / (2 * f);
+}
+
+struct TileLists {
+  int2 entry[WAVES][LIST_CAP];  // (row index, y0 | y1 << 8 | x0 << 16 | x1 << 24: hit rectangle in tile cells, exclusive ends)
+  int count[WAVES];
+};
+
+// the rows of the table that own at least one cell of the tile at (ty0, tx0); f = page pixels per cell
+__device__ __forceinline__ void find_tile_placements(const int* __restrict__ table, int n, int Hs, int Ws, int f, int ty0,
+                                                     int tx0, TileLists& L) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int cnt = 0;
+  for (int base = wave * 64; base < n; base += THREADS) {
+    const int i = base + lane;
+    bool hit = false;
+    int packed = 0;
+    if (i < n) {
+      const Placement p = load_placement(table, i);
+      if (placement_ok(p, Hs, Ws)) {
+        int y0, y1, x0, x1;
+        cell_range(p.dy, p.dh, f, y0, y1);
+        cell_range(p.dx, p.dw, f, x0, x1);
+        y0 = max(y0 - ty0, 0); y1 = min(y1 - ty0, TILE_H);
+        x0 = max(x0 - tx0, 0); x1 = min(x1 - tx0, TILE_W);
+        hit = y0 < y1 && x0 < x1;
+        packed = y0 | (y1 << 8) | (x0 << 16) | (x1 << 24);
+      }
+    }
+    const unsigned long long mask = __ballot(hit);
+    if (hit) {
+      const int pos = cnt + __popcll(mask & ((1ull << lane) - 1ull));
+      if (pos < LIST_CAP) L.entry[wave][pos] = make_int2(i, packed);
+    }
+    cnt += __popcll(mask);
+  }
+  if (lane == 0) L.count[wave] = min(cnt, LIST_CAP);
+  __syncthreads();
+}
+
+// owner row of each of the thread's four cells (tile row r, tile columns c .. c + 3), -1 where there is none
+__device__ __forceinline__ void resolve_owners(const TileLists& L, int r, int c, int owner[QUAD]) {
+#pragma unroll
+  for (int q = 0; q < QUAD; ++q) owner[q] = -1;
+  for (int w = 0; w < WAVES; ++w) {
+    const int cnt = L.count[w];
+    for (int e = 0; e < cnt; ++e) {
+      const int2 en = L.entry[w][e];
+      const int y0 = en.y & 255, y1 = (en.y >> 8) & 255, x0 = (en.y >> 16) & 255, x1 = (en.y >> 24) & 255;
+      if (r >= y0 && r < y1) {
+#pragma unroll
+        for (int q = 0; q < QUAD; ++q)
+          if (c + q >= x0 && c + q < x1) owner[q] = en.x;
+      }
+    }
+  }
+}
+
+// One axis of the rule for destination sample o of D from S source samples: taps j(k), weights w(k), k < n; their sum is den.
+struct Axis {
+  int n, j0, a, b, D, S, f;
+  bool shrink;
+  __device__ __forceinline__ void init(int o, int S_, int D_) {
+    S = S_; D = D_;
+    shrink = D < S;
+    if (shrink) {
+      a = o * S; b = a + S;
+      j0 = a / D;
+      n = (b - 1) / D - j0 + 1;
+    } else {
+      const int num = (2 * o + 1) * S - D;                      // >= -D: floor division by hand below zero
+      j0 = num >= 0 ? num / (2 * D) : -1;
+      f = num - j0 * 2 * D;
+      n = f == 0 ? 1 : 2;
+    }
+  }
+  __device__ __forceinline__ int den() const { return shrink ? S : 2 * D; }
+  __device__ __forceinline__ int tap(int k) const { return shrink ? j0 + k : min(max(j0 + k, 0), S - 1); }
+  __device__ __forceinline__ int weight(int k) const {
+    if (shrink) {
+      const int j = j0 + k;
+      return min((j + 1) * D, b) - max(j * D, a);
+    }
+    return k == 0 ? 2 * D - f : f;
+  }
+};
+
+// (num + den / 2) / den for num <= 255 * den, den < 2^29: a float estimate (within 1 of the quotient) and an exact fix-up
+__device__ __forceinline__ unsigned round_div(unsigned long long num, unsigned den) {
+  const unsigned long long t = num + (den >> 1);
+  int q = (int)((float)t * (1.0f / (float)den));
+  long long rem = (long long)t - (long long)q * den;
+  if (rem < 0) { --q; rem += den; }
+  if (rem < 0) { --q; rem += den; }
+  if (rem >= (long long)den) { ++q; rem -= den; }
+  if (rem >= (long long)den) ++q;
+  return (unsigned)q;
+}
+
+__device__ __forceinline__ void resample_pixel(const unsigned char* __restrict__ src, int Ws, const Placement& p,
+                                               const Axis& ay, int ox, unsigned out[3]) {
+  Axis ax;
+  ax.init(ox, p.sw, p.dw);
+  unsigned long long acc0 = 0, acc1 = 0, acc2 = 0;
+  for (int ky = 0; ky < ay.n; ++ky) {
+    const unsigned char* row = src + ((long)(p.sy + ay.tap(ky)) * Ws + p.sx) * 3;
+    unsigned in0 = 0, in1 = 0, in2 = 0;
+    for (int kx = 0; kx < ax.n; ++kx) {
+      const unsigned char* px = row + ax.tap(kx) * 3;
+      const unsigned w = (unsigned)ax.weight(kx);
+      in0 += w * px[0]; in1 += w * px[1]; in2 += w * px[2];
+    }
+    const unsigned long long wy = (unsigned long long)ay.weight(ky);
+    acc0 += wy * in0; acc1 += wy * in1; acc2 += wy * in2;
+  }
+  const unsigned den = (unsigned)ay.den() * (unsigned)ax.den();
+  out[0] = round_div(acc0, den); out[1] = round_div(acc1, den); out[2] = round_div(acc2, den);
+}
+
+__global__ __launch_bounds__(THREADS) void resample_pack_kernel(const unsigned char* __restrict__ src, int Hs, int Ws,
+                                                                const int* __restrict__ table, int n,
+                                                                unsigned char* __restrict__ page, int Hp, int Wp,
+                                                                int dword_stores) {
+  __shared__ TileLists L;
+  const int ty0 = blockIdx.y * TILE_H, tx0 = blockIdx.x * TILE_W;
+  find_tile_placements(table, n, Hs, Ws, 1, ty0, tx0, L);
+  const int r = threadIdx.x / (TILE_W / QUAD), c = (threadIdx.x % (TILE_W / QUAD)) * QUAD;
+  const int y = ty0 + r, x = tx0 + c;
+  if (y >= Hp || x >= Wp) return;
+  int owner[QUAD];
+  resolve_owners(L, r, c, owner);
+  unsigned char bytes[QUAD * 3];
+  int cur = -1;
+  Placement p;
+  Axis ay;
+#pragma unroll
+  for (int q = 0; q < QUAD; ++q) {
+    unsigned v[3] = {0u, 0u, 0u};
+    if (owner[q] >= 0 && x + q < Wp) {
+      if (owner[q] != cur) {
+        cur = owner[q];
+        p = load_placement(table, cur);
+        ay.init(y - p.dy, p.sh, p.dh);
+      }
+      resample_pixel(src, Ws, p, ay, x + q - p.dx, v);
+    }
+    bytes[q * 3] = (unsigned char)v[0]; bytes[q * 3 + 1] = (unsigned char)v[1]; bytes[q * 3 + 2] = (unsigned char)v[2];
+  }
+  unsigned char* out = page + ((long)y * Wp + x) * 3;
+  if (dword_stores) {  // Wp % 4 == 0 and a 4-byte aligned page: the quad is whole and its 12 bytes are three aligned dwords
+    unsigned* o = reinterpret_cast<unsigned*>(out);
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+      o[d] = bytes[4 * d] | (bytes[4 * d + 1] << 8) | (bytes[4 * d + 2] << 16) | ((unsigned)bytes[4 * d + 3] << 24);
+  } else {
+    const int nb = min(QUAD, Wp - x) * 3;
+#pragma unroll
+    for (int k = 0; k < QUAD * 3; ++k)
+      if (k < nb) out[k] = bytes[k];
+  }
+}
+
+// rough map coordinate under the centre of label cell c of a placement axis: packing.py's centre mapping
+__device__ __forceinline__ int source_cell(int c, int f, int d0, int dlen, int s0, int slen, int valid, int full) {
+  const long long t2 = 2LL * c * f + f - 2LL * d0;
+  const long long num = (2LL * dlen * s0 + t2 * slen) * valid;
+  const long long m = num / (2LL * dlen * full);
+  return (int)(m < valid - 1 ? m : valid - 1);
+}
+
+__global__ __launch_bounds__(THREADS) void pack_labels_kernel(const int* __restrict__ labels, int Wl, int valid_h,
+                                                              int valid_w, int Hs, int Ws, const int* __restrict__ table,
+                                                              const int* __restrict__ region_ids, int n, int f,
+                                                              int* __restrict__ out, int Hq, int Wq, int vec_stores) {
+  __shared__ TileLists L;
+  const int ty0 = blockIdx.y * TILE_H, tx0 = blockIdx.x * TILE_W;
+  find_tile_placements(table, n, Hs, Ws, f, ty0, tx0, L);
+  const int r = threadIdx.x / (TILE_W / QUAD), c = (threadIdx.x % (TILE_W / QUAD)) * QUAD;
+  const int y = ty0 + r, x = tx0 + c;
+  if (y >= Hq || x >= Wq) return;
+  int owner[QUAD];
+  resolve_owners(L, r, c, owner);
+  int vals[QUAD];
+  int cur = -1, rid = 0, my = 0;
+  Placement p;
+#pragma unroll
+  for (int q = 0; q < QUAD; ++q) {
+    int v = 0;
+    if (owner[q] >= 0 && x + q < Wq) {
+      if (owner[q] != cur) {
+        cur = owner[q];
+        p = load_placement(table, cur);
+        rid = region_ids[cur];
+        my = source_cell(y, f, p.dy, p.dh, p.sy, p.sh, valid_h, Hs);
+      }
+      const int mx = source_cell(x + q, f, p.dx, p.dw, p.sx, p.sw, valid_w, Ws);
+      const int other = labels[(long)my * Wl + mx];
+      v = (other != 0 && other != rid) ? 0 : rid;
+    }
+    vals[q] = v;
+  }
+  int* o = out + (long)y * Wq + x;
+  if (vec_stores) {
+    *reinterpret_cast<int4*>(o) = make_int4(vals[0], vals[1], vals[2], vals[3]);
+  } else {
+#pragma unroll
+    for (int q = 0; q < QUAD; ++q)
+      if (x + q < Wq) o[q] = vals[q];
+  }
+}
+
+}  // namespace
+
+extern "C" int vkas_resample_pack_u8(const unsigned char* src, int Hs, int Ws, const int* placements, int n,
+                                     unsigned char* page, int Hp, int Wp, void* stream) {
+  VKAS_CHECK(src && page, "vkas_resample_pack_u8: null pointer");
+  VKAS_CHECK(n >= 0 && (n == 0 || placements), "vkas_resample_pack_u8: bad table (n %d)", n);
+  VKAS_CHECK(Hs >= 1 && Ws >= 1 && Hp >= 1 && Wp >= 1, "vkas_resample_pack_u8: bad dims");
+  VKAS_CHECK(Hs <= DIM_MAX && Ws <= DIM_MAX && Hp <= DIM_MAX && Wp <= DIM_MAX,
+             "vkas_resample_pack_u8: source and page sides must not exceed %d", DIM_MAX);
+  VKAS_CHECK(vkas_aligned16(placements), "vkas_resample_pack_u8: the placement table must be 16-byte aligned");
+  const int dword_stores = (Wp % 4 == 0) && ((((uintptr_t)page) & 3u) == 0);
+  const dim3 grid((unsigned)vkas_cdiv(Wp, TILE_W), (unsigned)vkas_cdiv(Hp, TILE_H));
+  resample_pack_kernel<<<grid, THREADS, 0, vkas_stream(stream)>>>(src, Hs, Ws, placements, n, page, Hp, Wp, dword_stores);
+  VKAS_LAUNCH_CHECK("resample_pack_u8");
+  return VKAS_OK;
+}
+
+extern "C" int vkas_pack_region_labels(const int* labels, int Hl, int Wl, int valid_h, int valid_w, int Hs, int Ws,
+                                       const int* placements, const int* region_ids, int n, int fdf, int* out, int Hq,
+                                       int Wq, void* stream) {
+  VKAS_CHECK(labels && out, "vkas_pack_region_labels: null pointer");
+  VKAS_CHECK(n >= 0 && (n == 0 || (placements && region_ids)), "vkas_pack_region_labels: bad table (n %d)", n);
+  VKAS_CHECK(Hl >= 1 && Wl >= 1 && Hs >= 1 && Ws >= 1 && Hq >= 1 && Wq >= 1, "vkas_pack_region_labels: bad dims");
+  VKAS_CHECK(valid_h >= 1 && valid_h <= Hl && valid_w >= 1 && valid_w <= Wl,
+             "vkas_pack_region_labels: the valid part %d x %d does not fit the %d x %d label map", valid_h, valid_w, Hl, Wl);
+  VKAS_CHECK(fdf >= 1 && fdf <= 64, "vkas_pack_region_labels: bad factor %d", fdf);
+  VKAS_CHECK(Hl <= DIM_MAX && Wl <= DIM_MAX && Hs <= DIM_MAX && Ws <= DIM_MAX && (long)Hq * fdf <= DIM_MAX &&
+                 (long)Wq * fdf <= DIM_MAX,
+             "vkas_pack_region_labels: map, source and page sides must not exceed %d", DIM_MAX);
+  VKAS_CHECK(vkas_aligned16(placements), "vkas_pack_region_labels: the placement table must be 16-byte aligned");
+  const int vec_stores = (Wq % 4 == 0) && vkas_aligned16(out);
+  const dim3 grid((unsigned)vkas_cdiv(Wq, TILE_W), (unsigned)vkas_cdiv(Hq, TILE_H));
+  pack_labels_kernel<<<grid, THREADS, 0, vkas_stream(stream)>>>(labels, Wl, valid_h, valid_w, Hs, Ws, placements,
+                                                                region_ids, n, fdf, out, Hq, Wq, vec_stores);
+  VKAS_LAUNCH_CHECK("pack_region_labels");
+  return VKAS_OK;
+}

@@ -5,8 +5,11 @@ from .adaptive_scaling import (
     AdaptiveScalingInferencingRoughTextRegions,
     AdaptiveScalingInferencingPresiceInferResult,
     AdaptiveScalingInferencingPreciseCharPolygons,
+    AdaptiveScalingInferencingResult,
     AdaptiveScalingInferencing,
     precise_group_char_polygons,
 )
 from .graphs import GraphCache, param_stamp
 from .regions import region_scales, text_regions_host
+from .packing import (SIDE_MAX, axis_weights, check_placements, pack_region_labels_host, region_crops, remap_polygons,
+                      resample_host, stack_regions)

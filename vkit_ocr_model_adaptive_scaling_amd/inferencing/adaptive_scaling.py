@@ -12,9 +12,15 @@ pass's HIP graph, restated on pixels: a region is an 8-connected component of th
 hole is not filled, a component inside a hole is a region of its own), and its axis-aligned box stands in for vkit's
 flattened region in the scale rule (inferencing/regions.py states the rule and holds the host oracle).
 
-Out of scope: the CPU geometry around it - polygons of the rough regions, text-region flattening /
-stacking, building the region label map from them and remapping polygons through the flattening (vkit, cv2; third-party
-code that is absent here).  Images are plain (H, W, 3) uint8 arrays instead of ``vkit.element.Image``; results carry
+The step the model is named after - cut every text region out of the page, rescale it so that its median character
+height becomes 35 px and stack the cuts into the page of the precise pass (:190-293) - runs on the device too
+(csrc/respack.hip, ``ops.resample_pack_u8`` / ``ops.pack_region_labels``), and ``infer`` chains all of it: image in,
+characters per region in image coordinates out.  It differs from the reference where vkit and cv2 (absent here) would be
+needed: a region's axis-aligned box stands in for the flattened region, so nothing is rotated or straightened; the
+interpolation rule is this project's own, in integers (inferencing/packing.py); stacking is a shelf packing; and a character
+of a neighbouring region inside an overlapping box is excluded through the rough label map instead of ``flattened_mask``.
+
+Out of scope: polygons of the rough regions and flattening proper (vkit, cv2).  Images are plain (H, W, 3) uint8 arrays instead of ``vkit.element.Image``; results carry
 numpy arrays instead of ``Mask`` / ``ScoreMap`` / ``Polygon``.  The reference loads a TorchScript file (``model_jit``,
 :85-90); so does this mirror (``torch.jit.save`` of ``torch.jit.script(model)``, see model/scripting.py), and it also takes
 the scripted or the eager ``AdaptiveScaling`` module itself, or a state-dict file in the reference's ``RestoreState`` schema.
@@ -30,6 +36,7 @@ import torch
 from .opt import pad_mat_to_make_divisible
 from .graphs import GraphCache, param_stamp
 from .regions import region_scales
+from .packing import SIDE_MAX, region_crops, remap_polygons, stack_regions
 from .. import ops
 from .._lib import lib, check
 from ..model import AdaptiveScaling, AdaptiveScalingConfig
@@ -65,6 +72,17 @@ class AdaptiveScalingInferencingConfig:
     precise_flattened_text_region_resized_ratio_min: float = 0.25
     # table rows of rough_infer_text_regions; a page with more regions reports its true count and the first rows
     rough_text_regions_max: int = 4096
+    # :55-56, read by infer: the margin around the stacked page and the gap between stacked regions, in pixels
+    precise_stack_flattened_text_regions_page_pad: int = 10
+    precise_stack_flattened_text_regions_pad: int = 2
+    # The stacked page (inferencing/packing.py::stack_regions; both multiples of 32).  Width: the long side of the
+    # reference's 2048 x 1536 page - text near 35 px (scale near 1) then stacks to no more area than the source held, so
+    # such a page becomes ONE page no taller than the source, and a line as wide as the source minus the two page pads
+    # still fits a row.  The height is not capped - one page always - and grows in steps: a 2048-wide page between 256
+    # and 1536 rows takes one of six shapes, so the HIP-graph cache (one graph per page shape) stays small, at the price
+    # of up to 255 rows of padding for the precise pass.
+    precise_page_width_max: int = 2048
+    precise_page_height_step: int = 256
 
 
 @attrs.define
@@ -112,6 +130,24 @@ class AdaptiveScalingInferencingPreciseCharPolygons:
     points: np.ndarray    # (N, 2) int32 (y, x) in map pixels
     probs: np.ndarray     # (N,) float32, the char probability at each point
     polygons: np.ndarray  # (N, 4, 2) float32 (y, x) in padded-image pixels: up-left, up-right, down-right, down-left
+
+
+@attrs.define
+class AdaptiveScalingInferencingResult:
+    """``infer``: the characters of one image, grouped by text region, in the coordinates of the image as given.  Lists
+    have one entry per row of ``regions`` (region r is entry r - 1; empty for a region that was not packed)."""
+    image_shape: Tuple[int, int]
+    regions: AdaptiveScalingInferencingRoughTextRegions  # the region table; padded_image / labels only on request
+    packed: np.ndarray          # (N,) bool: the region has a placement
+    too_large: np.ndarray       # (N,) bool: kept, but wider than the page or with a side above the resampling limit
+    placements: np.ndarray      # (M, 8) int32 (sy, sx, sh, sw, dy, dx, dh, dw): image rectangle -> page rectangle
+    placement_regions: np.ndarray  # (M,) int32: the region (1-based) of each placement
+    page_shape: Tuple[int, int]
+    page: Optional[np.ndarray]  # the stacked (Hp, Wp, 3) uint8 page, only on request
+    region_labels: Optional[np.ndarray]  # the (Hp/FDF, Wp/FDF) int32 label page, only on request
+    points: Sequence[np.ndarray]    # per region (k, 2) int32 (y, x) in the precise maps of the page
+    probs: Sequence[np.ndarray]     # per region (k,) float32
+    polygons: Sequence[np.ndarray]  # per region (k, 4, 2) float64 (y, x) in image pixels
 
 
 def rough_resized_shape(height: int, width: int, short_side: int) -> Tuple[int, int]:
@@ -182,35 +218,68 @@ class AdaptiveScalingInferencing:
         return vh, vw
 
     # ---- rough pass ----------------------------------------------------------------------------------------------
-    def rough_infer(self, image, resize_fn=None) -> AdaptiveScalingInferencingRoughInferResult:
-        """:92-188.  ``resize_fn(mat, height, width)`` performs the area-interpolation shrink of the 720 rule (cv2 in the
-        reference); without it an image that needs shrinking is rejected - resampling pixels is host-side image I/O."""
+    def _device_rough_page(self, src: torch.Tensor, h: int, w: int) -> torch.Tensor:
+        """The (H, W, 3) uint8 device image resampled to h x w (the area-coverage shrink of the 720 rule; the identity when
+        the sizes agree) inside a zero page padded to the backbone's factor: csrc/respack.hip with a single placement."""
+        f = self.config.backbone_downsampling_factor
+        H, W = int(src.shape[0]), int(src.shape[1])
+        if max(H, W) > SIDE_MAX:
+            raise ValueError(f'image {(H, W)}: the device resampler takes sides up to {SIDE_MAX}')
+        table = np.array([[0, 0, H, W, 0, 0, h, w]], np.int32)
+        return ops.resample_pack_u8(src, table, (-(-h // f) * f, -(-w // f) * f))
+
+    def _rough_input(self, image, resize_fn):
+        """-> the image as given, (h, w) after the 720 rule, the padded image (numpy) and the model input on the device.
+        ``resize_fn``: None (an image that needs shrinking is rejected), a callable ``(mat, height, width)`` on the host, or
+        'device': the shrink runs on the MI355X with this package's own integer area rule (inferencing/packing.py)."""
         c = self.config
         mat = _as_mat(image)
         h, w = rough_resized_shape(mat.shape[0], mat.shape[1], c.rough_downsample_short_side_legnth)
+        if isinstance(resize_fn, str) and resize_fn != 'device':
+            raise ValueError(f"resize_fn must be None, a callable or 'device', got {resize_fn!r}")
         if (h, w) != mat.shape[:2]:
             if resize_fn is None:
                 raise ValueError(f'image {mat.shape[:2]} exceeds the short-side limit {c.rough_downsample_short_side_legnth}: '
-                                 f'pass resize_fn or an image already resized to {(h, w)}')
-            mat = np.asarray(resize_fn(mat, h, w))
-            assert mat.shape[:2] == (h, w)
-        padded = pad_mat_to_make_divisible(mat, c.backbone_downsampling_factor)
+                                 f"pass resize_fn (a callable, or 'device') or an image already resized to {(h, w)}")
+            if isinstance(resize_fn, str):
+                if mat.dtype != np.uint8:
+                    raise ValueError(f"resize_fn='device' takes a uint8 image, got {mat.dtype}")
+                src = torch.from_numpy(np.ascontiguousarray(mat)).to(c.device, non_blocking=True)
+                page = self._device_rough_page(src, h, w)
+                return mat, (h, w), page.cpu().numpy(), page[None].permute(0, 3, 1, 2).float()
+            resized = np.asarray(resize_fn(mat, h, w))
+            assert resized.shape[:2] == (h, w)
+            padded = pad_mat_to_make_divisible(resized, c.backbone_downsampling_factor)
+        else:
+            padded = pad_mat_to_make_divisible(mat, c.backbone_downsampling_factor)
+        return mat, (h, w), padded, self._to_device([padded])
+
+    def _rough_maps(self, x, vh, vw, H: int, W: int):
+        """The rough model call + the device post-processing (:129-172): mask (B,H,W) uint8 and height (B,H,W) fp32."""
+        c = self.config
+        mask_feat, height_feat = self.model.forward_rough(x)
+        B = mask_feat.shape[0]
+        assert tuple(mask_feat.shape) == (B, 1, H, W) and height_feat.shape == mask_feat.shape
+        out_mask = torch.empty((B, H, W), dtype=torch.uint8, device=x.device)
+        out_height = torch.empty((B, H, W), dtype=torch.float32, device=x.device)
+        check(lib.vkas_rough_postprocess(_ptr(mask_feat.contiguous()), _ptr(height_feat.contiguous()), B, H, W, _ptr(vh),
+                                         _ptr(vw), float(c.rough_char_mask_positive_thr), float(c.rough_valid_char_height_min),
+                                         _ptr(out_mask), _ptr(out_height), ops._stream()), 'rough_postprocess')
+        return out_mask, out_height
+
+    def rough_infer(self, image, resize_fn=None) -> AdaptiveScalingInferencingRoughInferResult:
+        """:92-188.  ``resize_fn(mat, height, width)`` performs the area-interpolation shrink of the 720 rule (cv2 in the
+        reference); ``resize_fn='device'`` shrinks on the device with this package's own area rule; without either an image
+        that needs shrinking is rejected."""
+        c = self.config
+        _, (h, w), padded, x = self._rough_input(image, resize_fn)
         fdf = 4 // c.rough_head_upsampling_factor
-        x = self._to_device([padded])
         H, W = padded.shape[0] // fdf, padded.shape[1] // fdf
         vh, vw = self._valid([(h, w)], fdf, x.device)
         thr, hmin = float(c.rough_char_mask_positive_thr), float(c.rough_valid_char_height_min)
 
         def rough_pass(x, vh, vw):  # the model call + the device post-processing: one HIP graph per padded shape
-            mask_feat, height_feat = self.model.forward_rough(x)
-            B = mask_feat.shape[0]
-            assert tuple(mask_feat.shape) == (B, 1, H, W) and height_feat.shape == mask_feat.shape
-            out_mask = torch.empty((B, H, W), dtype=torch.uint8, device=x.device)
-            out_height = torch.empty((B, H, W), dtype=torch.float32, device=x.device)
-            check(lib.vkas_rough_postprocess(_ptr(mask_feat.contiguous()), _ptr(height_feat.contiguous()), B, H, W, _ptr(vh),
-                                             _ptr(vw), thr, hmin, _ptr(out_mask), _ptr(out_height), ops._stream()),
-                  'rough_postprocess')
-            return out_mask, out_height
+            return self._rough_maps(x, vh, vw, H, W)
 
         with torch.no_grad():
             out_mask, out_height = self.graphs.run(('rough', thr, hmin), rough_pass, [x, vh, vw], param_stamp(self.model))
@@ -218,41 +287,18 @@ class AdaptiveScalingInferencing:
             resized_shape=(math.ceil(h / fdf), math.ceil(w / fdf)), padded_image=padded,
             rough_char_mask=out_mask[0].cpu().numpy(), rough_char_height_score_map=out_height[0].cpu().numpy())
 
-    def rough_infer_text_regions(self, image, resize_fn=None,
-                                 return_labels: bool = True) -> AdaptiveScalingInferencingRoughTextRegions:
-        """The rough pass followed by the text regions of its mask, the exact median of the valid character heights of
-        each (csrc/regions.hip, in the same HIP graph) and the reference's scale rule on the host (:190-279 restated on
-        pixels, inferencing/regions.py): the region count, the table rows and - if ``return_labels`` - the int32 label map
-        cross PCIe, the mask and the height map do not.  ``image`` and ``resize_fn`` as in ``rough_infer``, whose maps this
-        labels: the result equals ``text_regions_host`` + ``region_scales`` on them."""
+    def _rough_text_regions(self, x, image_shape, h: int, w: int, padded, return_labels: bool):
+        """The rough-plus-regions graph on a device input and the table rows read back: the result, and the device label
+        map (a static output of the graph: consume it before the next graph of this cache runs)."""
         c = self.config
-        mat = _as_mat(image)
-        image_shape = mat.shape[:2]
-        h, w = rough_resized_shape(mat.shape[0], mat.shape[1], c.rough_downsample_short_side_legnth)
-        if (h, w) != mat.shape[:2]:
-            if resize_fn is None:
-                raise ValueError(f'image {mat.shape[:2]} exceeds the short-side limit {c.rough_downsample_short_side_legnth}: '
-                                 f'pass resize_fn or an image already resized to {(h, w)}')
-            mat = np.asarray(resize_fn(mat, h, w))
-            assert mat.shape[:2] == (h, w)
-        padded = pad_mat_to_make_divisible(mat, c.backbone_downsampling_factor)
         fdf = 4 // c.rough_head_upsampling_factor
-        x = self._to_device([padded])
-        H, W = padded.shape[0] // fdf, padded.shape[1] // fdf
+        H, W = x.shape[2] // fdf, x.shape[3] // fdf
         vh, vw = self._valid([(h, w)], fdf, x.device)
         thr, hmin = float(c.rough_char_mask_positive_thr), float(c.rough_valid_char_height_min)
         cap = int(c.rough_text_regions_max)
 
         def rough_regions_pass(x, vh, vw):  # model call, post-processing and region table: one HIP graph per padded shape
-            mask_feat, height_feat = self.model.forward_rough(x)
-            B = mask_feat.shape[0]
-            assert tuple(mask_feat.shape) == (B, 1, H, W) and height_feat.shape == mask_feat.shape
-            out_mask = torch.empty((B, H, W), dtype=torch.uint8, device=x.device)
-            out_height = torch.empty((B, H, W), dtype=torch.float32, device=x.device)
-            check(lib.vkas_rough_postprocess(_ptr(mask_feat.contiguous()), _ptr(height_feat.contiguous()), B, H, W, _ptr(vh),
-                                             _ptr(vw), thr, hmin, _ptr(out_mask), _ptr(out_height), ops._stream()),
-                  'rough_postprocess')
-            return ops.text_regions(out_mask, out_height, cap)
+            return ops.text_regions(*self._rough_maps(x, vh, vw, H, W), cap)
 
         with torch.no_grad():
             count, labels, boxes, areas, valid, medians = self.graphs.run(
@@ -267,7 +313,17 @@ class AdaptiveScalingInferencing:
         return AdaptiveScalingInferencingRoughTextRegions(
             resized_shape=resized_shape, padded_image=padded, num_regions=num,
             labels=labels[0].cpu().numpy() if return_labels else None, boxes=boxes, areas=areas, valid=valid,
-            char_height_medians=medians, scales=scales, resized_shapes=resized_shapes, keep=keep)
+            char_height_medians=medians, scales=scales, resized_shapes=resized_shapes, keep=keep), labels[0]
+
+    def rough_infer_text_regions(self, image, resize_fn=None,
+                                 return_labels: bool = True) -> AdaptiveScalingInferencingRoughTextRegions:
+        """The rough pass followed by the text regions of its mask, the exact median of the valid character heights of
+        each (csrc/regions.hip, in the same HIP graph) and the reference's scale rule on the host (:190-279 restated on
+        pixels, inferencing/regions.py): the region count, the table rows and - if ``return_labels`` - the int32 label map
+        cross PCIe, the mask and the height map do not.  ``image`` and ``resize_fn`` as in ``rough_infer``, whose maps this
+        labels: the result equals ``text_regions_host`` + ``region_scales`` on them."""
+        mat, (h, w), padded, x = self._rough_input(image, resize_fn)
+        return self._rough_text_regions(x, mat.shape[:2], h, w, padded, return_labels)[0]
 
     # ---- precise pass --------------------------------------------------------------------------------------------
     def _precise_groups(self, images: Sequence):
@@ -328,26 +384,11 @@ class AdaptiveScalingInferencing:
         the same HIP graph (csrc/charpoly.hip): only the peak count and the peak rows cross PCIe, not the maps.  Pages are
         grouped by padded size as in ``precise_infer_batch``.  A map point (y, x) sits at (y * Hp / H, x * Wp / W) of the
         Hp x Wp padded image (vkit's ``Point.to_conducted_resized_point``, restated as proportional scaling)."""
-        c = self.config
-        fdf = 4 // c.precise_head_upsampling_factor
-        thr, size = float(c.precise_build_polygons_positive_char_prob_thr), c.precise_build_polygons_maximum_filter_size
         groups, mats, padded = self._precise_groups(images)
         results = [None] * len(mats)
         for shape, idxs in groups:
             x = self._to_device([padded[i] for i in idxs])
-            H, W = shape[0] // fdf, shape[1] // fdf
-            scale_y, scale_x = shape[0] / H, shape[1] / W
-            vh, vw = self._valid([mats[i].shape[:2] for i in idxs], fdf, x.device)
-
-            def char_polygons_pass(x, vh, vw):
-                o_prob, o_off, o_ang, o_dist = self._precise_maps(x, vh, vw, H, W)
-                return ops.char_polygons(o_prob, o_off, o_ang, o_dist, thr, size, scale_y, scale_x)
-
-            with torch.no_grad():
-                count, points, probs, quads = self.graphs.run(('precise_char_polygons', thr, size), char_polygons_pass,
-                                                              [x, vh, vw], param_stamp(self.model))
-            n = int(count.item())
-            points, probs, quads = (t[:n].cpu().numpy() for t in (points, probs, quads))
+            points, probs, quads = self._char_polygons(x, [mats[i].shape[:2] for i in idxs])
             bounds = np.searchsorted(points[:, 0], np.arange(len(idxs) + 1))  # rows are sorted by page
             for k, i in enumerate(idxs):
                 lo, hi = bounds[k], bounds[k + 1]
@@ -356,8 +397,90 @@ class AdaptiveScalingInferencing:
                     polygons=quads[lo:hi])
         return results
 
+    def _char_polygons(self, x: torch.Tensor, sizes: Sequence[Tuple[int, int]], on_device: bool = False):
+        """The precise-plus-char-polygons graph on a device input (B, 3, Hp, Wp) whose pages are valid on ``sizes``: the
+        (n, 3) int32 (page, y, x) points, (n,) probs and (n, 4, 2) quadrilaterals, as numpy arrays - or, ``on_device``, as
+        device tensors (views of the graph's static outputs)."""
+        c = self.config
+        fdf = 4 // c.precise_head_upsampling_factor
+        thr, size = float(c.precise_build_polygons_positive_char_prob_thr), c.precise_build_polygons_maximum_filter_size
+        shape = (int(x.shape[2]), int(x.shape[3]))
+        H, W = shape[0] // fdf, shape[1] // fdf
+        scale_y, scale_x = shape[0] / H, shape[1] / W
+        vh, vw = self._valid(sizes, fdf, x.device)
+
+        def char_polygons_pass(x, vh, vw):
+            o_prob, o_off, o_ang, o_dist = self._precise_maps(x, vh, vw, H, W)
+            return ops.char_polygons(o_prob, o_off, o_ang, o_dist, thr, size, scale_y, scale_x)
+
+        with torch.no_grad():
+            count, points, probs, quads = self.graphs.run(('precise_char_polygons', thr, size), char_polygons_pass,
+                                                          [x, vh, vw], param_stamp(self.model))
+        n = int(count.item())
+        if on_device:
+            return points[:n], probs[:n], quads[:n]
+        return tuple(t[:n].cpu().numpy() for t in (points, probs, quads))
+
     def precise_infer_char_polygons(self, image) -> AdaptiveScalingInferencingPreciseCharPolygons:
         return self.precise_infer_char_polygons_batch([image])[0]
+
+    # ---- image in, characters out --------------------------------------------------------------------------------
+    def infer(self, image, return_page: bool = False, return_labels: bool = False) -> AdaptiveScalingInferencingResult:
+        """Both passes and the step between them (:92-525 on pixels): the uint8 image is uploaded once; the 720 rule's shrink
+        (if any) and the padding run on the device; the rough-plus-regions graph gives the region table, whose rows come
+        back; scales, crops and the shelf packing are host arithmetic on that table (inferencing/regions.py, packing.py);
+        the placements go up, the regions are resampled into the stacked page and the label page is written on the device
+        (csrc/respack.hip); the precise-plus-char-polygons graph runs on that device page; the characters are grouped by
+        the label under their point and their quadrilaterals mapped back into the image.  The image, the maps and the page
+        do not cross back over PCIe unless ``return_page`` / ``return_labels`` ask for them.  Equal, bit for bit, to
+        ``rough_infer_text_regions`` -> ``resample_host`` -> ``precise_infer_char_polygons`` ->
+        ``precise_group_char_polygons`` -> ``remap_polygons``."""
+        c = self.config
+        mat = _as_mat(image)
+        if mat.dtype != np.uint8:
+            raise ValueError(f'infer takes a uint8 image, got {mat.dtype}')
+        image_shape = (int(mat.shape[0]), int(mat.shape[1]))
+        h, w = rough_resized_shape(image_shape[0], image_shape[1], c.rough_downsample_short_side_legnth)
+        src = torch.from_numpy(np.ascontiguousarray(mat)).to(c.device, non_blocking=True)
+        rough_page = self._device_rough_page(src, h, w)
+        regions, d_labels = self._rough_text_regions(rough_page[None].permute(0, 3, 1, 2).float(), image_shape, h, w,
+                                                     rough_page.cpu().numpy() if return_page else None, return_labels)
+        n = len(regions.boxes)
+        crops = region_crops(regions.boxes, image_shape, regions.resized_shape)
+        source_fits = (crops[:, 2:] <= SIDE_MAX).all(axis=1)
+        page_shape, boxes, packed, too_large = stack_regions(
+            regions.resized_shapes, c.precise_stack_flattened_text_regions_page_pad, c.precise_stack_flattened_text_regions_pad,
+            c.precise_page_width_max, c.precise_page_height_step, keep=regions.keep & source_fits)
+        too_large |= regions.keep & ~source_fits
+        ids = (np.flatnonzero(packed) + 1).astype(np.int32)
+        placements = np.ascontiguousarray(np.concatenate([crops[packed], boxes[packed]], axis=1).astype(np.int32))
+        empty = lambda *shape, dtype: np.zeros(shape, dtype)
+        points = [empty(0, 2, dtype=np.int32) for _ in range(n)]
+        probs = [empty(0, dtype=np.float32) for _ in range(n)]
+        polygons = [empty(0, 4, 2, dtype=np.float64) for _ in range(n)]
+        page = region_labels = None
+        if len(ids):
+            fdf = 4 // c.precise_head_upsampling_factor
+            d_page = ops.resample_pack_u8(src, placements, page_shape)
+            d_region_labels = ops.pack_region_labels(d_labels, regions.resized_shape, image_shape, placements, ids,
+                                                     (page_shape[0] // fdf, page_shape[1] // fdf), fdf)
+            d_points, d_probs, d_quads = self._char_polygons(d_page[None].permute(0, 3, 1, 2).float(), [page_shape],
+                                                             on_device=True)
+            at = d_region_labels[d_points[:, 1].long(), d_points[:, 2].long()].cpu().numpy()
+            all_points, all_probs, all_quads = (t.cpu().numpy() for t in (d_points[:, 1:], d_probs, d_quads))
+            for k, rid in enumerate(ids.tolist()):
+                sel = at == rid
+                points[rid - 1] = np.ascontiguousarray(all_points[sel])
+                probs[rid - 1] = all_probs[sel]
+                polygons[rid - 1] = remap_polygons(all_quads[sel], placements[k])
+            if return_page:
+                page = d_page.cpu().numpy()
+            if return_labels:
+                region_labels = d_region_labels.cpu().numpy()
+        return AdaptiveScalingInferencingResult(
+            image_shape=image_shape, regions=regions, packed=packed, too_large=too_large, placements=placements,
+            placement_regions=ids, page_shape=page_shape, page=page, region_labels=region_labels, points=points, probs=probs,
+            polygons=polygons)
 
     @staticmethod
     def precise_group_char_polygons(result: AdaptiveScalingInferencingPreciseCharPolygons,

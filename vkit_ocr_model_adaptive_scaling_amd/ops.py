@@ -2329,3 +2329,116 @@ def text_regions(mask: torch.Tensor, height: torch.Tensor, max_regions: int):
     check(lib.vkas_text_regions(_p(mask), _p(height), B, H, W, R, _p(ws), ws.numel(), _p(count), _p(labels), _p(boxes),
                                 _p(areas), _p(valid), _p(medians), _stream()), 'text_regions')
     return count, labels, boxes, areas, valid, medians
+
+
+def _placement_table(who: str, placements, src_shape, page_shape, device, validate: bool) -> torch.Tensor:
+    """The (n, 8) int32 placement table on ``device``.  A host table (numpy array or CPU tensor) is always validated
+    (inferencing/packing.py::check_placements: sides, bounds, disjoint destinations) and uploaded; a device table is copied
+    to the host for the same check when ``validate`` - a synchronisation -, else trusted (a captured graph's static table:
+    the kernels skip a row that is out of range, but overlapping destinations give an unspecified winner)."""
+    import numpy as np
+    from .inferencing.packing import check_placements
+    if isinstance(placements, torch.Tensor):
+        if placements.dim() != 2 or placements.shape[1] != 8:
+            raise ValueError(f'{who}: placements must be (n, 8), got {tuple(placements.shape)}')
+        if placements.dtype != torch.int32:
+            raise ValueError(f'{who}: placements must be int32, got {placements.dtype}')
+        if placements.is_cuda:
+            if validate:
+                check_placements(placements.cpu().numpy(), src_shape, page_shape)
+            if placements.device != device:
+                raise ValueError(f'{who}: placements are on {placements.device}, the image on {device}')
+            return placements.contiguous()
+        placements = placements.numpy()
+    else:
+        placements = np.asarray(placements)
+        if placements.ndim != 2 or placements.shape[1] != 8:
+            raise ValueError(f'{who}: placements must be (n, 8), got {placements.shape}')
+        if placements.dtype != np.int32:
+            raise ValueError(f'{who}: placements must be int32, got {placements.dtype}')
+    table = check_placements(placements, src_shape, page_shape)
+    if device.type != 'cuda':
+        return torch.from_numpy(table)
+    return torch.from_numpy(table).to(device, non_blocking=True)
+
+
+_PACK_DIM_MAX = 32768
+
+
+def resample_pack_u8(src: torch.Tensor, placements, page_shape: Tuple[int, int], validate: bool = True,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Crops, rescales and packs rectangles of one image into a page (the step between the two passes,
+    inferencing/adaptive_scaling.py:190-293 restated on pixels, csrc/respack.hip).  src (Hs,Ws,3) uint8 on the device;
+    ``placements`` (n,8) int32 rows (sy, sx, sh, sw, dy, dx, dh, dw), host or device (see ``_placement_table``); returns the
+    (Hp,Wp,3) uint8 page (``out`` if given): the resampled pixels inside the placements - the integer rule of
+    inferencing/packing.py, equal to ``resample_host`` byte for byte - and zero elsewhere.  One launch; with a device table
+    and ``validate=False`` it never synchronises, so it can be captured into a HIP graph."""
+    if src.dim() != 3 or src.shape[2] != 3:
+        raise ValueError(f'resample_pack_u8: src must be (H, W, 3), got {tuple(src.shape)}')
+    if src.dtype != torch.uint8:
+        raise ValueError(f'resample_pack_u8: src must be uint8, got {src.dtype}')
+    Hs, Ws = int(src.shape[0]), int(src.shape[1])
+    try:
+        Hp, Wp = (int(v) for v in page_shape)
+    except (TypeError, ValueError):
+        raise ValueError(f'resample_pack_u8: page_shape must be (height, width), got {page_shape!r}') from None
+    if Hs < 1 or Ws < 1 or Hp < 1 or Wp < 1:
+        raise ValueError(f'resample_pack_u8: empty source {(Hs, Ws)} or page {(Hp, Wp)}')
+    if max(Hs, Ws, Hp, Wp) > _PACK_DIM_MAX:
+        raise ValueError(f'resample_pack_u8: source {(Hs, Ws)} and page {(Hp, Wp)} sides must not exceed {_PACK_DIM_MAX}')
+    if out is not None and (tuple(out.shape) != (Hp, Wp, 3) or out.dtype != torch.uint8 or not out.is_contiguous()):
+        raise ValueError(f'resample_pack_u8: out must be a contiguous {(Hp, Wp, 3)} uint8 tensor')
+    table = _placement_table('resample_pack_u8', placements, (Hs, Ws), (Hp, Wp), src.device, validate)
+    _require_cuda(src, out)
+    if out is not None and out.device != src.device:
+        raise ValueError(f'resample_pack_u8: out is on {out.device}, src on {src.device}')
+    src = src.contiguous()
+    page = out if out is not None else torch.empty((Hp, Wp, 3), dtype=torch.uint8, device=src.device)
+    check(lib.vkas_resample_pack_u8(_p(src), Hs, Ws, _p(table) if table.shape[0] else None, int(table.shape[0]), _p(page),
+                                    Hp, Wp, _stream()), 'resample_pack_u8')
+    return page
+
+
+def pack_region_labels(labels: torch.Tensor, valid_shape: Tuple[int, int], image_shape: Tuple[int, int], placements,
+                       region_ids, out_shape: Tuple[int, int], fdf: int, validate: bool = True) -> torch.Tensor:
+    """The int32 region-label page of a packed page at ``1/fdf`` of its resolution (csrc/respack.hip; the rule and the oracle:
+    inferencing/packing.py::pack_region_labels_host).  labels (Hl,Wl) int32 on the device - the rough label map, of which
+    ``valid_shape`` covers the ``image_shape`` image the placements' sources refer to; ``placements`` as in
+    ``resample_pack_u8`` with the page taken as ``out_shape * fdf``; ``region_ids`` (n,) int32 >= 1, host or device.  Returns
+    (Hq,Wq) int32: region_ids[k] where the pixel's centre lies in placement k and the rough map holds no other region's label
+    at its source position, else 0."""
+    if labels.dim() != 2:
+        raise ValueError(f'pack_region_labels: labels must be (H, W), got {tuple(labels.shape)}')
+    if labels.dtype != torch.int32:
+        raise ValueError(f'pack_region_labels: labels must be int32, got {labels.dtype}')
+    Hl, Wl = int(labels.shape[0]), int(labels.shape[1])
+    vh, vw = (int(v) for v in valid_shape)
+    Hs, Ws = (int(v) for v in image_shape)
+    Hq, Wq = (int(v) for v in out_shape)
+    if not (1 <= vh <= Hl and 1 <= vw <= Wl):
+        raise ValueError(f'pack_region_labels: valid_shape {(vh, vw)} does not fit the {(Hl, Wl)} label map')
+    if fdf != int(fdf) or not 1 <= int(fdf) <= 64:
+        raise ValueError(f'pack_region_labels: fdf must be an integer in [1, 64], got {fdf}')
+    fdf = int(fdf)
+    if Hs < 1 or Ws < 1 or Hq < 1 or Wq < 1:
+        raise ValueError(f'pack_region_labels: empty image {(Hs, Ws)} or label page {(Hq, Wq)}')
+    if max(Hl, Wl, Hs, Ws, Hq * fdf, Wq * fdf) > _PACK_DIM_MAX:
+        raise ValueError(f'pack_region_labels: map, image and page sides must not exceed {_PACK_DIM_MAX}')
+    table = _placement_table('pack_region_labels', placements, (Hs, Ws), (Hq * fdf, Wq * fdf), labels.device, validate)
+    n = int(table.shape[0])
+    if not isinstance(region_ids, torch.Tensor):
+        import numpy as np
+        region_ids = torch.from_numpy(np.ascontiguousarray(np.asarray(region_ids)))
+    if region_ids.dim() != 1 or region_ids.shape[0] != n:
+        raise ValueError(f'pack_region_labels: region_ids must be ({n},), got {tuple(region_ids.shape)}')
+    if region_ids.dtype != torch.int32:
+        raise ValueError(f'pack_region_labels: region_ids must be int32, got {region_ids.dtype}')
+    if not region_ids.is_cuda and n and int(region_ids.min()) < 1:
+        raise ValueError('pack_region_labels: region ids start at 1 (0 is "no region")')
+    _require_cuda(labels)
+    ids = region_ids.to(labels.device, non_blocking=True).contiguous()
+    labels = labels.contiguous()
+    out = torch.empty((Hq, Wq), dtype=torch.int32, device=labels.device)
+    check(lib.vkas_pack_region_labels(_p(labels), Hl, Wl, vh, vw, Hs, Ws, _p(table) if n else None, _p(ids) if n else None, n,
+                                      fdf, _p(out), Hq, Wq, _stream()), 'pack_region_labels')
+    return out
