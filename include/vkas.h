@@ -434,7 +434,8 @@ int vkas_points_gather_rows(const void* z, long ldz, int c0, int Ns, const float
 int vkas_points_gather_patches(const void* x, long ldx, int Cp, int B, int H, int W, const int* pix, long Mp, void* xs,
                                int dtype, void* stream);
 /* D (Mp, 3, 3, Cp) fp32: D[i][ky][kx] is the input-gradient contribution of point i to pixel p_i + (ky-1, kx-1).  Adds them onto
- * dx (B,H,W,Cp; ld lddx): every touched pixel is summed in fp32 by one workgroup and written once. */
+ * dx (B,H,W,Cp; ld lddx): every touched pixel is summed in fp32 by one workgroup and written once.  Only the owners' rows of D
+ * (pix[i] >= 0) are read: the rows of duplicates and of padding may hold anything. */
 int vkas_points_scatter3x3(const float* D, const int* pix, const int* map, long Mp, int B, int H, int W, int Cp, void* dx,
                            long lddx, int dtype, void* stream);
 
