@@ -303,6 +303,12 @@ int vkas_resize_bwd_ws(const void* dy, long lddy, void* dx, long lddx, float* ws
  * E_k[s, n] = sum_q U[q, s] * dz[q + (k - 1), n], k = (ky, kx) the tap of the dgrad convolution (the K order of the mode-1
  * weight image), zero where q + (k - 1) leaves the map.  Then dx = E . Bt^T and dW[n][c][8 - k] = sum_s E_k[s, n] x[s, c]. */
 int vkas_upconv_adj(const void* dz, long lddz, void* E, int B, int h, int w, int N, int dtype, void* stream);
+/* the same E (bit for bit), and out[n] (+)= the column sums of dz over all B * 2h * 2w rows - what vkas_colsum delivers - from
+ * the values the kernel loads anyway.  N <= 2048; ws: vkas_upconv_adj_colsum_ws_bytes of per-workgroup partial rows; fixed
+ * summation order. */
+size_t vkas_upconv_adj_colsum_ws_bytes(int B, int h, int w, int N);
+int vkas_upconv_adj_colsum(const void* dz, long lddz, void* E, int B, int h, int w, int N, float* out, int accumulate, float* ws,
+                           size_t ws_bytes, int dtype, void* stream);
 /* gE (9 N, Cp) fp32, row k * N + n [the weight-gradient GEMM of E against x] added onto the packed gradient of the forward
  * taps: gwp (N, 3, 3, Cp)[n][8 - k][c] += gE[k * N + n][c] */
 int vkas_upconv_adj_unpack_wgrad(const float* gE, float* gwp, int N, int Cp, void* stream);
@@ -438,6 +444,12 @@ int vkas_points_gather_patches(const void* x, long ldx, int Cp, int B, int H, in
  * (pix[i] >= 0) are read: the rows of duplicates and of padding may hold anything. */
 int vkas_points_scatter3x3(const float* D, const int* pix, const int* map, long Mp, int B, int H, int W, int Cp, void* dx,
                            long lddx, int dtype, void* stream);
+/* The same contributions through U^T (U: x2 bilinear, align_corners=False, clamped) onto the gradient of the source map:
+ * dx (B,h,w,Cp; ld lddx)[s] += sum U[q, s] * D[i][t] over the (point i, tap t) pairs that land on an upsampled pixel q reading
+ * s.  pix / map are those of the upsampled (2h x 2w) map (vkas_points_prepare with H = 2h, W = 2w).  Every touched source pixel
+ * is summed in fp32 in a fixed order by one workgroup and written once; no atomics. */
+int vkas_points_scatter3x3_low(const float* D, const int* pix, const int* map, long Mp, int B, int h, int w, int Cp, void* dx,
+                               long lddx, int dtype, void* stream);
 
 /* (Mp, 8) fp32 rows <-> the (M, 8) projected-channel map of a head at the label points (opt-in label-point forward of
  * the regression heads, ops.HeadsAtPoints): scatter writes the owner rows (pix[i] >= 0) to their pixels (duplicates

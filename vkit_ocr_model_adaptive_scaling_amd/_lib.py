@@ -148,6 +148,8 @@ _SIGS = {
     'vkas_resize_bwd_ws': (c_int, [_P, c_long, _P, c_long, _P, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                    c_int, _P]),
     'vkas_upconv_adj': (c_int, [_P, c_long, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    'vkas_upconv_adj_colsum_ws_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'vkas_upconv_adj_colsum': (c_int, [_P, c_long, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, c_size_t, c_int, _P]),
     'vkas_upconv_adj_unpack_wgrad': (c_int, [_P, _P, c_int, c_int, _P]),
     'vkas_adaptive_avgpool_fwd':(c_int, [_P, c_long, _P, c_long, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     'vkas_adaptive_avgpool_bwd': (c_int, [_P, c_long, _P, c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
@@ -174,6 +176,7 @@ _SIGS = {
     'vkas_points_gather_rows': (c_int, [_P, c_long, c_int, c_int, _P, _P, c_int, c_long, _P, c_long, _P, _P, _P, c_int, _P]),
     'vkas_points_gather_patches': (c_int, [_P, c_long, c_int, c_int, c_int, c_int, _P, c_long, _P, c_int, _P]),
     'vkas_points_scatter3x3': (c_int, [_P, _P, _P, c_long, c_int, c_int, c_int, c_int, _P, c_long, c_int, _P]),
+    'vkas_points_scatter3x3_low': (c_int, [_P, _P, _P, c_long, c_int, c_int, c_int, c_int, _P, c_long, c_int, _P]),
     'vkas_points_scatter_vec8': (c_int, [_P, _P, c_long, _P, _P]),
     'vkas_points_gather_vec8': (c_int, [_P, _P, c_long, _P, _P]),
     'vkas_pack_many': (c_int, [_P, _P, c_int, c_int, _P]),

@@ -15,6 +15,8 @@
 //   vkas_points_gather_patches 3x3 input patches at the points -> compact (rows, 9*Cp) operand of the weight-gradient GEMM
 //   vkas_points_scatter3x3     compact fp32 (rows, 9*Cp) input-gradient contributions -> added onto dx, every touched pixel summed
 //                              in fp32 by exactly one workgroup (no atomics, deterministic)
+//   vkas_points_scatter3x3_low the same contributions through U^T (x2 bilinear) straight onto the gradient of the map the heads'
+//                              input is the upsample of: no buffer at the upsampled resolution, no U^T pass over it
 #include "vkas_common.h"
 
 namespace {
@@ -145,6 +147,86 @@ __global__ __launch_bounds__(64) void points_scatter3x3_kernel(const float* __re
   }
 }
 
+// weights with which destinations 2i-1 .. 2i+2 read source i of n: ut_weights of upconv_adj.hip
+__device__ __forceinline__ void pt_ut_weights(int i, int n, float* w) {
+  w[0] = i == 0 ? 0.f : 0.25f;
+  w[1] = i == 0 ? 1.f : 0.75f;
+  w[2] = i == n - 1 ? 1.f : 0.75f;
+  w[3] = i == n - 1 ? 0.f : 0.25f;
+}
+
+// The same contributions, taken through U^T (U the x2 bilinear upsample, align_corners=False, clamped) straight onto the
+// gradient dx (B, h, w, Cp) of the neck feature: dx[s] += sum U[q, s] * D[i][t] over the (point i, tap t) pairs that land on an
+// upsampled pixel q which reads s.  pix / map are those of the upsampled (2h x 2w) map.  A point at (yy, xx) reaches the
+// 3 x 3 source pixels around (yy / 2, xx / 2): workgroup (i, t) stands for one of them, s.  s reads the 4 x 4 upsampled
+// pixels 2s-1 .. 2s+2, so its contributors are the owner points in the 6 x 6 window 2s-2 .. 2s+3: the first of them in
+// row-major order owns s, sums every term in fp32 in window order, then tap order, and adds the sum onto dx once.  The
+// window lookups are unconditional from clamped addresses (positions outside the map masked on use); a lane without a channel
+// vector of its own repeats the last one and does not store.
+template <typename T>
+__global__ __launch_bounds__(64) void points_scatter3x3_low_kernel(const float* __restrict__ D, const int* __restrict__ pix,
+                                                                   const int* __restrict__ map, int h, int w, int Cp,
+                                                                   T* __restrict__ dx, long lddx) {
+  const long i = blockIdx.x / 9;
+  const int t = (int)(blockIdx.x - i * 9);
+  const int p = pix[i];
+  if (p < 0) return;  // duplicates and padding rows carry zeros
+  const int H = 2 * h, W = 2 * w;
+  const long q = p;
+  const int xx = (int)(q % W), yy = (int)((q / W) % H);
+  const long img = q - ((long)yy * W + xx);  // first pixel of the image in the upsampled map
+  const int si = (yy >> 1) + t / 3 - 1, sj = (xx >> 1) + t % 3 - 1;
+  if ((unsigned)si >= (unsigned)h || (unsigned)sj >= (unsigned)w) return;
+  int src[36];
+  bool first = true, mine = false;
+#pragma unroll
+  for (int e = 0; e < 36; ++e) {
+    const int Y = 2 * si - 2 + e / 6, X = 2 * sj - 2 + e % 6;
+    const bool ok = (unsigned)Y < (unsigned)H && (unsigned)X < (unsigned)W;
+    const int yc = Y < 0 ? 0 : (Y > H - 1 ? H - 1 : Y), xc = X < 0 ? 0 : (X > W - 1 ? W - 1 : X);
+    int o = map[img + (long)yc * W + xc];
+    o = __builtin_amdgcn_readfirstlane(ok ? o : PT_EMPTY);  // the same value in every lane: branches on it are uniform
+    src[e] = o;
+    if (o != PT_EMPTY && first) {
+      first = false;
+      mine = o == (int)i;
+    }
+  }
+  if (!mine) return;
+  float wy[4], wx[4];
+  pt_ut_weights(si, h, wy);
+  pt_ut_weights(sj, w, wx);
+  const int nv = Cp >> 3;
+  T* out = dx + ((img >> 2) + (long)si * w + sj) * lddx;  // img is a multiple of 4 h w
+  for (int v0 = 0; v0 < nv; v0 += 64) {
+    const int v = v0 + (int)threadIdx.x;
+    const int vc = v < nv ? v : nv - 1;
+    float old[8], acc[8];
+    load8(out + vc * 8, old);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc[k] = 0.f;
+#pragma unroll
+    for (int e = 0; e < 36; ++e) {
+      if (src[e] == PT_EMPTY) continue;
+      const float* Dp = D + (long)src[e] * 9 * Cp + vc * 8;
+#pragma unroll
+      for (int u = 0; u < 9; ++u) {
+        const int a = e / 6 + u / 3 - 2, c = e % 6 + u % 3 - 2;  // tap u of this point lands on upsampled pixel (2si-1+a, 2sj-1+c)
+        if (a < 0 || a > 3 || c < 0 || c > 3) continue;
+        const float wq = wy[a] * wx[c];  // 0 where that pixel lies outside the map
+        const float4* r = reinterpret_cast<const float4*>(Dp + (long)u * Cp);
+        const float4 r0 = r[0], r1 = r[1];
+        acc[0] = fmaf(wq, r0.x, acc[0]); acc[1] = fmaf(wq, r0.y, acc[1]); acc[2] = fmaf(wq, r0.z, acc[2]);
+        acc[3] = fmaf(wq, r0.w, acc[3]); acc[4] = fmaf(wq, r1.x, acc[4]); acc[5] = fmaf(wq, r1.y, acc[5]);
+        acc[6] = fmaf(wq, r1.z, acc[6]); acc[7] = fmaf(wq, r1.w, acc[7]);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) old[k] += acc[k];
+    if (v < nv) store8(out + v * 8, old);
+  }
+}
+
 // (rows, 8) fp32 vectors <-> the (M, 8) projected-channel maps of a head, at the label points
 __global__ __launch_bounds__(256) void points_scatter_vec8_kernel(const float* __restrict__ src, const int* __restrict__ pix,
                                                                   long Mp, float* __restrict__ dst) {
@@ -248,5 +330,19 @@ extern "C" int vkas_points_scatter3x3(const float* D, const int* pix, const int*
     points_scatter3x3_kernel<T><<<(unsigned)(Mp * 9), 64, 0, st>>>(D, pix, map, H, W, Cp, (T*)dx, lddx);
   })
   VKAS_LAUNCH_CHECK("points_scatter3x3");
+  return VKAS_OK;
+}
+
+extern "C" int vkas_points_scatter3x3_low(const float* D, const int* pix, const int* map, long Mp, int B, int h, int w, int Cp,
+                                          void* dx, long lddx, int dtype, void* stream) {
+  VKAS_CHECK(D && pix && map && dx, "vkas_points_scatter3x3_low: null pointer");
+  VKAS_CHECK(Cp > 0 && Cp % 8 == 0 && lddx >= Cp && lddx % 8 == 0 && B > 0 && h > 0 && w > 0 && Mp > 0 && Mp * 9 < 0x7fffffffL &&
+                 4L * B * h * w < PT_EMPTY && vkas_aligned16(D) && vkas_aligned16(dx),
+             "vkas_points_scatter3x3_low: bad sizes Cp=%d lddx=%ld Mp=%ld", Cp, lddx, Mp);
+  hipStream_t st = vkas_stream(stream);
+  VKAS_DISPATCH_DTYPE(dtype, "vkas_points_scatter3x3_low", {
+    points_scatter3x3_low_kernel<T><<<(unsigned)(Mp * 9), 64, 0, st>>>(D, pix, map, h, w, Cp, (T*)dx, lddx);
+  })
+  VKAS_LAUNCH_CHECK("points_scatter3x3_low");
   return VKAS_OK;
 }

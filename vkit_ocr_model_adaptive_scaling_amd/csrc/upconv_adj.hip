@@ -16,6 +16,8 @@
 // rounding to the storage type.
 #include "vkas_common.h"
 
+int vkas_colreduce_finalize(const float* partial, long P, int n, int ldp, float* out, int accumulate, hipStream_t st);
+
 namespace {
 
 // as in resize.hip: workgroups are dealt round-robin over the 8 XCDs; give every XCD one contiguous run of image rows
@@ -34,17 +36,12 @@ __device__ __forceinline__ void ut_weights(int i, int n, float* w) {
   w[3] = i == n - 1 ? 0.f : 0.25f;
 }
 
-// grid.x = B*h source rows, grid.y = chunks of 256 (pixel, vector) pairs of one row
-template <typename T>
-__global__ __launch_bounds__(256) void upconv_adj_kernel(const T* __restrict__ dz, long lddz, T* __restrict__ E, int h,
-                                                         int w, int nvec) {
-  const int idx = blockIdx.y * 256 + threadIdx.x;
-  const int j = idx / nvec;
-  const int v = idx - j * nvec;
-  if (j >= w) return;
-  const int row = xcd_row(blockIdx.x, gridDim.x);
-  const int b = row / h;
-  const int i = row - b * h;
+// One (source pixel, 8-channel vector) pair: E's nine vectors from the 6 x 6 window of dz.  CS: also add the centre 2 x 2 block
+// (upsampled pixels 2i, 2i+1 x 2j, 2j+1: every upsampled pixel is in exactly one pair's centre block) onto the thread's own
+// sums cs[k * 256], row-major (in LDS: the kernel has no registers to spare).
+template <typename T, bool CS>
+__device__ __forceinline__ void upconv_adj_pair(const T* __restrict__ dz, long lddz, T* __restrict__ E, int h, int w, int nvec,
+                                                int b, int i, int j, int v, float* cs) {
   const int H2 = 2 * h, W2 = 2 * w;
   float wy[4], wx[4];
   ut_weights(i, h, wy);
@@ -70,10 +67,18 @@ __global__ __launch_bounds__(256) void upconv_adj_kernel(const T* __restrict__ d
     const int Y = 2 * i - 2 + r;
     const bool yok = Y >= 0 && Y < H2;
     const int yc = Y < 0 ? 0 : (Y >= H2 ? H2 - 1 : Y);
-    const T* rowp = db + (long)yc * W2 * lddz;
     Raw8<T> raw[6];  // the row's six requests first, conversions afterwards
+    if constexpr (CS) {
+      // a row base that is the same in every lane plus six 32-bit element offsets that serve all six rows (the host
+      // checks that a row of dz stays below 2^31 elements): fewer address registers than six 64-bit pointers per row
+      const T* rowb = dz + ((long)b * H2 + yc) * W2 * lddz;
 #pragma unroll
-    for (int c = 0; c < 6; ++c) raw[c].load(rowp + (long)xc[c] * lddz);
+      for (int c = 0; c < 6; ++c) raw[c].load(rowb + (unsigned)(xc[c] * (int)lddz + v * 8));
+    } else {
+      const T* rowp = db + (long)yc * W2 * lddz;
+#pragma unroll
+      for (int c = 0; c < 6; ++c) raw[c].load(rowp + (long)xc[c] * lddz);
+    }
     float hs[3][8];
 #pragma unroll
     for (int kx = 0; kx < 3; ++kx)
@@ -84,6 +89,10 @@ __global__ __launch_bounds__(256) void upconv_adj_kernel(const T* __restrict__ d
       raw[c].keep_if(yok && xok[c]);
       float t[8];
       raw[c].unpack(t);
+      if (CS && (r == 2 || r == 3) && (c == 2 || c == 3)) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) cs[k * 256] += t[k];
+      }
 #pragma unroll
       for (int kx = 0; kx < 3; ++kx) {
         const int a = c - kx;  // window column c is destination 2j-1+a moved by tap kx
@@ -108,6 +117,51 @@ __global__ __launch_bounds__(256) void upconv_adj_kernel(const T* __restrict__ d
   for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
     for (int kx = 0; kx < 3; ++kx) store8(dst + (ky * 3 + kx) * N, acc[ky][kx]);
+}
+
+// grid.x = B*h source rows, grid.y = chunks of 256 (pixel, vector) pairs of one row
+template <typename T>
+__global__ __launch_bounds__(256) void upconv_adj_kernel(const T* __restrict__ dz, long lddz, T* __restrict__ E, int h,
+                                                         int w, int nvec) {
+  const int idx = blockIdx.y * 256 + threadIdx.x;
+  const int j = idx / nvec;
+  const int v = idx - j * nvec;
+  if (j >= w) return;
+  const int row = xcd_row(blockIdx.x, gridDim.x);
+  const int b = row / h;
+  upconv_adj_pair<T, false>(dz, lddz, E, h, w, nvec, b, row - b * h, j, v, nullptr);
+}
+
+// The same E, and the column sums of dz on the way.  grid.x = B*h source rows; workgroup (x, y) takes the chunks y, y +
+// gridDim.y, ... of its row, a chunk being ppc = 256 / nvec whole pixels (nvec <= 256), so that a thread keeps its vector v
+// and adds its centre blocks onto its own eight sums in LDS (red[k * 256 + thread]), chunk after chunk.  The workgroup's threads of
+// one v are then summed in thread order by the first of them: partial[x * gridDim.y + y][v * 8 ..], a fixed order throughout.
+template <typename T>
+__global__ __launch_bounds__(256, 2) void upconv_adj_colsum_kernel(const T* __restrict__ dz, long lddz, T* __restrict__ E, int h,
+                                                                int w, int nvec, float* __restrict__ partial) {
+  const int ppc = 256 / nvec;
+  const int jl = threadIdx.x / nvec;
+  const int v = threadIdx.x - jl * nvec;
+  const int row = xcd_row(blockIdx.x, gridDim.x);
+  const int b = __builtin_amdgcn_readfirstlane(row / h);  // the same in every lane: row addresses stay in scalar registers
+  const int i = row - b * h;
+  __shared__ float red[8 * 256];  // [k][thread]
+#pragma unroll
+  for (int k = 0; k < 8; ++k) red[k * 256 + threadIdx.x] = 0.f;
+  if (jl < ppc) {
+    for (int j = blockIdx.y * ppc + jl; j < w; j += gridDim.y * ppc)
+      upconv_adj_pair<T, true>(dz, lddz, E, h, w, nvec, b, i, j, v, red + threadIdx.x);
+  }
+  __syncthreads();
+  if (jl == 0) {
+    float cs[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) cs[k] = red[k * 256 + v];
+    for (int r = 1; r < ppc; ++r)
+#pragma unroll
+      for (int k = 0; k < 8; ++k) cs[k] += red[k * 256 + r * nvec + v];
+    store8(partial + ((long)blockIdx.x * gridDim.y + blockIdx.y) * ((long)nvec * 8) + v * 8, cs);
+  }
 }
 
 // gE (9 N, Cp) fp32, row k * N + n [the weight-gradient GEMM of E against x] added onto the packed gradient
@@ -144,6 +198,45 @@ extern "C" int vkas_upconv_adj(const void* dz, long lddz, void* E, int B, int h,
     upconv_adj_kernel<f16_t><<<grid, 256, 0, vkas_stream(stream)>>>((const f16_t*)dz, lddz, (f16_t*)E, h, w, N / 8);
   VKAS_LAUNCH_CHECK("upconv_adj");
   return VKAS_OK;
+}
+
+namespace {
+// workgroups per source row of the column-sum variant: as many as keep the partial rows near 4096 (B*h = 2048 rows of the
+// benchmark's passes: 2), at most one per chunk
+static inline long cs_groups(int B, int h, int w, int N) {
+  const long chunks = vkas_cdiv(w, 256 / (N / 8));
+  long g = 4096 / ((long)B * h);
+  g = g < 1 ? 1 : g;
+  return g < chunks ? g : chunks;
+}
+}  // namespace
+
+extern "C" size_t vkas_upconv_adj_colsum_ws_bytes(int B, int h, int w, int N) {
+  if (B <= 0 || h <= 0 || w <= 0 || N <= 0 || N % 8 || N > 2048) return 0;
+  return (size_t)B * h * cs_groups(B, h, w, N) * N * sizeof(float);
+}
+
+// vkas_upconv_adj, and out[n] (+)= the column sums of dz (what vkas_colsum(dz, ...) delivers): per-workgroup partial rows in
+// ws, summed by the finalize kernel of vkas_colsum.  Fixed summation order: two launches give the same bits.
+extern "C" int vkas_upconv_adj_colsum(const void* dz, long lddz, void* E, int B, int h, int w, int N, float* out, int accumulate,
+                                      float* ws, size_t ws_bytes, int dtype, void* stream) {
+  VKAS_CHECK(dz && E && out && ws && vkas_aligned16(dz) && vkas_aligned16(E) && vkas_aligned16(ws),
+             "vkas_upconv_adj_colsum: null/misaligned pointer");
+  VKAS_CHECK(B > 0 && h > 0 && w > 0 && (long)B * h < (1L << 31) && 2L * w * lddz < (1L << 31),
+             "vkas_upconv_adj_colsum: bad spatial dims");
+  VKAS_CHECK(N > 0 && N % 8 == 0 && N <= 2048 && lddz >= N && lddz % 8 == 0,
+             "vkas_upconv_adj_colsum: bad channels/stride (N=%d lddz=%ld)", N, lddz);
+  VKAS_CHECK(dtype == VKAS_BF16 || dtype == VKAS_F16, "vkas_upconv_adj_colsum: 16-bit storage only");
+  VKAS_CHECK(ws_bytes >= vkas_upconv_adj_colsum_ws_bytes(B, h, w, N), "vkas_upconv_adj_colsum: workspace too small");
+  const long G = cs_groups(B, h, w, N);
+  dim3 grid((unsigned)((long)B * h), (unsigned)G);
+  hipStream_t st = vkas_stream(stream);
+  if (dtype == VKAS_BF16)
+    upconv_adj_colsum_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)dz, lddz, (bf16_t*)E, h, w, N / 8, ws);
+  else
+    upconv_adj_colsum_kernel<f16_t><<<grid, 256, 0, st>>>((const f16_t*)dz, lddz, (f16_t*)E, h, w, N / 8, ws);
+  VKAS_LAUNCH_CHECK("upconv_adj_colsum");
+  return vkas_colreduce_finalize(ws, (long)B * h * G, N, N, out, accumulate, st);
 }
 
 extern "C" int vkas_upconv_adj_unpack_wgrad(const float* gE, float* gwp, int N, int Cp, void* stream) {

@@ -1127,16 +1127,15 @@ def _heads_dense_lowres(heads, r0, r1, pw, hp, x, z, stats, dps, dparams, gwp, g
     Nd = offs[r1] - offs[r0]
     dz = _heads_dense_dz(heads, r0, r1, pw, hp, x, z, stats, dps, dparams)
     E = new_act(B, h_, w_, 9 * Nd, x)
-    _timed('upconv_adj_kernel', x, 0.0, M // 4, 9 * Nd, 0,
-           lambda: check(lib.vkas_upconv_adj(_p(dz), act_ld(dz), _p(E), B, h_, w_, Nd, _dt(x), _stream()), 'upconv_adj'),
-           float(M) * Nd * es * 3.25)
     # conv bias gradient: column sums of dz, as the convolution's weight-gradient kernel delivers them (the column sums
-    # of E's centre tap are the same sum, but of values rounded once more)
-    nbytes = lib.vkas_colsum_ws_bytes(M, Nd)
+    # of E's centre tap are the same sum, but of values rounded once more) - summed by the E kernel from the centre 2 x 2
+    # block every thread loads anyway, so dz is read once
+    nbytes = lib.vkas_upconv_adj_colsum_ws_bytes(B, h_, w_, Nd)
     ws_cs = _ws(nbytes, x.device)
-    _timed('colsum_partial_kernel', x, 0.0, M, Nd, 0,
-           lambda: check(lib.vkas_colsum(_p(dz), act_ld(dz), M, Nd, _p(gbp[offs[r0]:offs[r1]]), 1, _p(ws_cs), nbytes,
-                                         _dt(x), _stream()), 'colsum'), float(M) * Nd * es)
+    _timed('upconv_adj_colsum_kernel', x, 0.0, M // 4, 9 * Nd, 0,
+           lambda: check(lib.vkas_upconv_adj_colsum(_p(dz), act_ld(dz), _p(E), B, h_, w_, Nd, _p(gbp[offs[r0]:offs[r1]]), 1,
+                                                    _p(ws_cs), nbytes, _dt(x), _stream()), 'upconv_adj_colsum'),
+           float(M) * Nd * es * 3.25)
     del dz
     g1 = _geom(B, h_, w_, h_, w_, Cp, act_ld(x_low), 1, 1, 1, 0)
     gE = conv_wgrad(x_low, g1, E, 9 * Nd, nk=(9 * sum(heads.cs[r0:r1]), C), step_scratch=True)
@@ -1149,12 +1148,13 @@ def _heads_dense_lowres(heads, r0, r1, pw, hp, x, z, stats, dps, dparams, gwp, g
 
 
 def _heads_points_grads(heads, h0, h1, pw, hp, patches, zs, stats_s, dp_ptrs, pix, pmap, n_points, dparams, gw_into, gb_into,
-                        step_scratch, dx_into):
+                        step_scratch, dx_into, dx_low=False):
     """Backward of the heads [h0, h1) on compact label-point rows: zs (1,1,Mp,Ns) their z, stats_s their row statistics, dp_ptrs
     their gathered (Mp, 8) output gradients; patches (1,1,Mp,9 Cp) the 3x3 input patches at the points, or a function that
     gathers them (called after the tail backward).  Returns the packed (weight, bias) gradient - accumulated into gw_into /
     gb_into when given, else a fresh buffer (step_scratch: see conv_wgrad); dx_into (B,H,W,Cp) or None receives the input
-    gradient, summed per touched pixel on top of what it holds."""
+    gradient, summed per touched pixel on top of what it holds; with dx_low it is (B,h,w,Cp), the gradient of the map the
+    points' map is the x2 bilinear upsample of (pix / pmap stay those of the 2h x 2w map)."""
     Mp, Ns, K, C = zs.shape[2], zs.shape[3], 9 * heads.Cp, heads.C
     dzs = new_act(1, 1, Mp, Ns, zs)
     _head_tail_bwd(heads, h0, h1, pw, hp, zs.data_ptr(), Ns, stats_s.data_ptr(), dp_ptrs, Mp, dzs, dparams)
@@ -1172,8 +1172,12 @@ def _heads_points_grads(heads, h0, h1, pw, hp, patches, zs, stats_s, dp_ptrs, pi
         dzt = dzs.view(Mp, Ns).t().contiguous().view(1, 1, Ns, Mp)
         g3 = _geom(1, 1, Ns, 1, Ns, K, K, 1, 1, 1, 0)
         D = conv_wgrad(Wf, g3, dzt, Mp, nk=(n_points, C * 9), step_scratch=True, ordered=True)
-        check(lib.vkas_points_scatter3x3(_p(D), _p(pix), _p(pmap), Mp, B, H, W, Cp, _p(dx_into), act_ld(dx_into), _dt(zs),
-                                         _stream()), 'points_scatter3x3')
+        if dx_low:  # dx_into is the gradient of the map whose x2 upsample the heads read: U^T is applied on the way
+            check(lib.vkas_points_scatter3x3_low(_p(D), _p(pix), _p(pmap), Mp, B, H, W, Cp, _p(dx_into), act_ld(dx_into),
+                                                 _dt(zs), _stream()), 'points_scatter3x3_low')
+        else:
+            check(lib.vkas_points_scatter3x3(_p(D), _p(pix), _p(pmap), Mp, B, H, W, Cp, _p(dx_into), act_ld(dx_into), _dt(zs),
+                                             _stream()), 'points_scatter3x3')
     return gw, gb
 
 
@@ -1295,14 +1299,19 @@ class HeadsFused(Function):
         sp = _point_sparse_run(dprojs, B, H, W) if _POINT_SPARSE else None
         # low: x is the x2 bilinear upsample U of the neck feature x_low (UpHeadsFused).  The dense heads' gradients are then
         # matrix products over the h*w rows of E (csrc/upconv_adj.hip) and dx is the gradient of x_low itself; the label-point
-        # heads scatter into an upsampled-resolution buffer that U^T (resize2x_bwd) adds onto it.
+        # heads add their input gradient onto it through U^T point by point (vkas_points_scatter3x3_low); next to a marked
+        # dense head, or with _POINTS_LOW_SCATTER off, they scatter into an upsampled-resolution buffer that U^T (resize2x_bwd)
+        # adds onto it.
         low, h_, w_ = ctx.low, H // 2, W // 2
         x_low = saved[4 + 6 * n_heads] if low else None
         (s0, s1), (u0, u1), (e0, e1) = _head_bwd_plan(n_heads, sp and sp[:2], [point_mark(d) is not None for d in dprojs], low)
         need_dx = ctx.needs_input_grad[0]
         dx = (new_act(B, h_, w_, Cp, x) if low else new_act(B, H, W, Cp, x)) if need_dx else None
         dx_pts = dx  # where the convolution kernels write and the label-point heads add their input gradient, at x's resolution
-        if low and need_dx and u1 == u0:  # low: a buffer of its own; here only the label-point heads add to it, if any
+        pts_low = low and need_dx and u1 == u0 and sp is not None and _POINTS_LOW_SCATTER
+        if pts_low:  # no buffer at x's resolution at all
+            dx_pts = None
+        elif low and need_dx and u1 == u0:  # low: a buffer of its own; here only the label-point heads add to it, if any
             dx_pts = torch.zeros((B, H, W, Cp), dtype=x.dtype, device=dev) if sp is not None else None
         elif low:
             dx_pts = new_act(B, H, W, Cp, x) if need_dx else None
@@ -1322,10 +1331,12 @@ class HeadsFused(Function):
             check(lib.vkas_points_gather_rows(_p(z), Nt, offs[s0], Ns, ctypes.c_void_p(stats.data_ptr() + s0 * M * 8), ptrs,
                                               s1 - s0, M, _p(pix), Mp, _p(zs), _p(stats_s), _p(dproj_s), _dt(x), _stream()),
                   'points_gather_rows')
+            if pts_low and e1 == e0:
+                dx.zero_()
             _heads_points_grads(heads, s0, s1, pw, hp, lambda: _points_gather_patches(x, pix, Mp), zs, stats_s,
                                 [dproj_s.data_ptr() + j * Mp * 32 for j in range(s1 - s0)], pix, pmap, py.numel(), dparams,
-                                gwp[offs[s0] * K:offs[s1] * K], gbp[offs[s0]:offs[s1]], False, dx_pts)
-        if low and dx is not None:
+                                gwp[offs[s0] * K:offs[s1] * K], gbp[offs[s0]:offs[s1]], False, dx if pts_low else dx_pts, pts_low)
+        if low and dx is not None and not pts_low:
             if dx_pts is not None:  # dx (+)= U^T dx_pts
                 _timed('resize2x_bwd_kernel', x, 0.0, M, Cp, 0,
                        lambda: check(lib.vkas_resize_bwd(_p(dx_pts), act_ld(dx_pts), _p(dx), act_ld(dx), B, h_, w_, H, W, Cp, 0,
@@ -1458,6 +1469,9 @@ class HeadsAtPoints(Function):
 
 
 _POINT_SPARSE = os.environ.get('VKAS_POINT_SPARSE_BWD', '1') != '0'
+# label-point heads of UpHeadsFused: input gradient straight onto the neck-resolution dx (vkas_points_scatter3x3_low);
+# VKAS_POINTS_UPRES_SCATTER=1 keeps the zeroed 2h x 2w buffer + resize2x_bwd (A/B runs, tests)
+_POINTS_LOW_SCATTER = os.environ.get('VKAS_POINTS_UPRES_SCATTER', '0') != '1'
 
 
 def point_sparse(grad: torch.Tensor, py: torch.Tensor, px: torch.Tensor) -> torch.Tensor:
