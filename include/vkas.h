@@ -531,6 +531,34 @@ int vkas_resample_pack_u8(const unsigned char* src, int Hs, int Ws, const int* p
 int vkas_pack_region_labels(const int* labels, int Hl, int Wl, int valid_h, int valid_w, int Hs, int Ws,
                             const int* placements, const int* region_ids, int n, int fdf, int* out, int Hq, int Wq,
                             void* stream);
+/* Orientation of the text regions (inferencing/orient.py holds the rule and the host oracles).  labels (B,H,W) int32 as
+ * vkas_text_regions writes them; R = max_regions rows per image, row r-1 for region r; label 0 and labels above R are
+ * ignored.  moments (B,R,6) int64 = n, sum y, sum x, sum y^2, sum x^2, sum x*y over the region's pixels, exact (sides up to
+ * 32768 and B*H*W < 2^31 keep every sum below 2^61); a region without pixels gets zeros.  Capture-safe: no allocation, no
+ * synchronisation, every table row is (re)written by the call; 64-bit integer atomics only (deterministic).  B <= 65535. */
+int vkas_region_moments(const int* labels, int B, int H, int W, int max_regions, long long* moments, void* stream);
+/* dirs (B,R,2) int32 (c, s), |c|, |s| <= 2^14: extents (B,R,4) int32 = min u, max u, min v, max v over the region's pixels
+ * with u = c*x + s*y, v = -s*x + c*y; a region without pixels keeps (INT_MAX, INT_MIN, INT_MAX, INT_MIN).  Same contract;
+ * extents 16-byte aligned. */
+int vkas_region_extents(const int* labels, int B, int H, int W, int max_regions, const int* dirs, int* extents,
+                        void* stream);
+/* Affine warps into the page.  warps (n,12) int64 rows (dy, dx, dh, dw, ay, ax, myy, myx, mxy, mxx, log2n, 0): destination
+ * pixel (i, j) of [dy,dy+dh) x [dx,dx+dw) reads src at Y = ay + i*myy + j*myx, X = ax + i*mxy + j*mxx in Q16 (an integer
+ * coordinate is a pixel centre).  Bounds: sides 1..8192, |m| <= 2^22, |ay|, |ax| < 2^40, log2n in 0..3; a row outside them is
+ * skipped.  With N = 2^log2n a pixel is the mean of N x N sub-samples at Y + ((2a+1-N)*myy + (2b+1-N)*myx) >> (1+log2n) (X
+ * likewise; arithmetic shifts), each two-tap bilinear per axis (k = Y >> 16, f = Y & 65535, weights 65536 - f and f on k and
+ * k+1; a tap outside src reads 0); a channel = (sum + den/2) >> (32 + 2*log2n).  Writes ONLY the pixels inside the
+ * destinations (it runs after vkas_resample_pack_u8 on the same page); destinations are disjoint from each other and from
+ * the placements (the caller's check).  One launch (none for n = 0); capture-safe; table 8-byte aligned. */
+int vkas_warp_pack_u8(const unsigned char* src, int Hs, int Ws, const long long* warps, int n, unsigned char* page, int Hp,
+                      int Wp, void* stream);
+/* The label cells of the warps: a cell (v,u) whose centre lies in the destination of warp k (the test of
+ * vkas_pack_region_labels) has i2 = 2*v*fdf + fdf - 2*dy - 1, j2 likewise, Y = ay + ((i2*myy + j2*myx) >> 1), source pixel
+ * Yp = (Y + 32768) >> 16 (X likewise).  Outside the Hs x Ws source it gets 0; else region_ids[k] unless the rough map holds
+ * another region's label at row min(valid_h - 1, ((2*Yp+1)*valid_h) / (2*Hs)), column likewise.  Writes ONLY those cells. */
+int vkas_warp_region_labels(const int* labels, int Hl, int Wl, int valid_h, int valid_w, int Hs, int Ws,
+                            const long long* warps, const int* region_ids, int n, int fdf, int* out, int Hq, int Wq,
+                            void* stream);
 
 /* ---- optimizer on the flat parameter / gradient buffers: train.py:468-478 ------------------------------ */
 /* sumsq (1 double, zeroed by the call) = sum g^2 */

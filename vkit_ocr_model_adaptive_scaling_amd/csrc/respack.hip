@@ -26,6 +26,8 @@ constexpr int DIM_MAX = 32768;                              // source / page sid
 
 struct Placement {
   int sy, sx, sh, sw, dy, dx, dh, dw;
+  static __device__ __forceinline__ Placement load(const int* __restrict__ table, int i);
+  __device__ __forceinline__ bool ok(int Hs, int Ws) const;
 };
 
 __device__ __forceinline__ Placement load_placement(const int* __restrict__ table, int i) {
@@ -49,14 +51,19 @@ __device__ __forceinline__ void cell_range(int d0, int dlen, int f, int& lo, int
   hi = b <= 0 ? 0 : (b + 2 * f - 1) / (2 * f);
 }
 
+__device__ __forceinline__ Placement Placement::load(const int* __restrict__ table, int i) { return load_placement(table, i); }
+__device__ __forceinline__ bool Placement::ok(int Hs, int Ws) const { return placement_ok(*this, Hs, Ws); }
+
 struct TileLists {
   int2 entry[WAVES][LIST_CAP];  // (row index, y0 | y1 << 8 | x0 << 16 | x1 << 24: hit rectangle in tile cells, exclusive ends)
   int count[WAVES];
 };
 
-// the rows of the table that own at least one cell of the tile at (ty0, tx0); f = page pixels per cell
-__device__ __forceinline__ void find_tile_placements(const int* __restrict__ table, int n, int Hs, int Ws, int f, int ty0,
-                                                     int tx0, TileLists& L) {
+// the rows of the table that own at least one cell of the tile at (ty0, tx0); f = page pixels per cell.  Row: the table's
+// row type (Placement, WarpRow) - load(table, i), ok(Hs, Ws) and the destination rectangle dy, dx, dh, dw
+template <class Row, class Word>
+__device__ __forceinline__ void find_tile_rows(const Word* __restrict__ table, int n, int Hs, int Ws, int f, int ty0, int tx0,
+                                               TileLists& L) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int cnt = 0;
   for (int base = wave * 64; base < n; base += THREADS) {
@@ -64,11 +71,11 @@ __device__ __forceinline__ void find_tile_placements(const int* __restrict__ tab
     bool hit = false;
     int packed = 0;
     if (i < n) {
-      const Placement p = load_placement(table, i);
-      if (placement_ok(p, Hs, Ws)) {
+      const Row p = Row::load(table, i);
+      if (p.ok(Hs, Ws)) {
         int y0, y1, x0, x1;
-        cell_range(p.dy, p.dh, f, y0, y1);
-        cell_range(p.dx, p.dw, f, x0, x1);
+        cell_range((int)p.dy, (int)p.dh, f, y0, y1);
+        cell_range((int)p.dx, (int)p.dw, f, x0, x1);
         y0 = max(y0 - ty0, 0); y1 = min(y1 - ty0, TILE_H);
         x0 = max(x0 - tx0, 0); x1 = min(x1 - tx0, TILE_W);
         hit = y0 < y1 && x0 < x1;
@@ -84,6 +91,11 @@ __device__ __forceinline__ void find_tile_placements(const int* __restrict__ tab
   }
   if (lane == 0) L.count[wave] = min(cnt, LIST_CAP);
   __syncthreads();
+}
+
+__device__ __forceinline__ void find_tile_placements(const int* __restrict__ table, int n, int Hs, int Ws, int f, int ty0,
+                                                     int tx0, TileLists& L) {
+  find_tile_rows<Placement>(table, n, Hs, Ws, f, ty0, tx0, L);
 }
 
 // owner row of each of the thread's four cells (tile row r, tile columns c .. c + 3), -1 where there is none
@@ -257,6 +269,136 @@ __global__ __launch_bounds__(THREADS) void pack_labels_kernel(const int* __restr
   }
 }
 
+// ---- affine warps: a slanted region cut out along its own axis (inferencing/orient.py builds the rows) ----------------
+// A warp row is 12 int64 (dy, dx, dh, dw, ay, ax, myy, myx, mxy, mxx, log2n, 0): destination pixel (i, j) of the rectangle
+// reads the source at Y = ay + i*myy + j*myx, X = ax + i*mxy + j*mxx in Q16, an integer coordinate being a pixel centre.
+constexpr int WARP_WORDS = 12;
+constexpr long long WARP_M_MAX = 1LL << 22, WARP_A_MAX = 1LL << 40;
+
+struct WarpRow {
+  long long dy, dx, dh, dw, ay, ax, myy, myx, mxy, mxx, log2n;
+  static __device__ __forceinline__ WarpRow load(const long long* __restrict__ table, int i) {
+    const long long* t = table + (long)i * WARP_WORDS;
+    return WarpRow{t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7], t[8], t[9], t[10]};
+  }
+  // as placement_ok: a row outside the bounds is absent.  Within them no intermediate leaves 64 bits (|Y| < 2^40 + 2^36)
+  // and a tap outside the source reads 0, so no table content makes a kernel read outside the source.
+  __device__ __forceinline__ bool ok(int, int) const {
+    const auto m_ok = [](long long m) { return m >= -WARP_M_MAX && m <= WARP_M_MAX; };
+    return dh >= 1 && dw >= 1 && dh <= SIDE_MAX && dw <= SIDE_MAX && dy >= 0 && dx >= 0 && dy <= DIM_MAX && dx <= DIM_MAX &&
+           ay > -WARP_A_MAX && ay < WARP_A_MAX && ax > -WARP_A_MAX && ax < WARP_A_MAX && m_ok(myy) && m_ok(myx) &&
+           m_ok(mxy) && m_ok(mxx) && log2n >= 0 && log2n <= 3;
+  }
+};
+
+// two-tap bilinear in x on source row k (zero outside the source): sum over the taps of weight * pixel, below 2^24
+__device__ __forceinline__ void warp_row_taps(const unsigned char* __restrict__ src, int Hs, int Ws, long long k,
+                                              long long kx, unsigned fx, unsigned in[3]) {
+  in[0] = in[1] = in[2] = 0u;
+  if (k < 0 || k >= Hs) return;
+  const unsigned char* row = src + (long)k * Ws * 3;
+  if (kx >= 0 && kx < Ws) {
+    const unsigned char* px = row + kx * 3;
+    const unsigned w = 65536u - fx;
+    in[0] += w * px[0]; in[1] += w * px[1]; in[2] += w * px[2];
+  }
+  if (fx != 0u && kx + 1 >= 0 && kx + 1 < Ws) {
+    const unsigned char* px = row + (kx + 1) * 3;
+    in[0] += fx * px[0]; in[1] += fx * px[1]; in[2] += fx * px[2];
+  }
+}
+
+__device__ __forceinline__ void warp_pixel(const unsigned char* __restrict__ src, int Hs, int Ws, const WarpRow& p, int i,
+                                           int j, unsigned out[3]) {
+  const long long Y = p.ay + i * p.myy + j * p.myx, X = p.ax + i * p.mxy + j * p.mxx;
+  const int ln = (int)p.log2n, n = 1 << ln;
+  unsigned long long acc[3] = {0ull, 0ull, 0ull};
+  for (int a = 0; a < n; ++a) {
+    for (int b = 0; b < n; ++b) {
+      const long long ka = 2 * a + 1 - n, kb = 2 * b + 1 - n;
+      const long long Ys = Y + ((ka * p.myy + kb * p.myx) >> (1 + ln));  // arithmetic shifts: floors
+      const long long Xs = X + ((ka * p.mxy + kb * p.mxx) >> (1 + ln));
+      const long long ky = Ys >> 16, kx = Xs >> 16;
+      const unsigned fy = (unsigned)(Ys & 65535), fx = (unsigned)(Xs & 65535);
+      unsigned r0[3], r1[3] = {0u, 0u, 0u};
+      warp_row_taps(src, Hs, Ws, ky, kx, fx, r0);
+      if (fy != 0u) warp_row_taps(src, Hs, Ws, ky + 1, kx, fx, r1);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) acc[c] += (unsigned long long)(65536u - fy) * r0[c] + (unsigned long long)fy * r1[c];
+    }
+  }
+  const int shift = 32 + 2 * ln;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) out[c] = (unsigned)((acc[c] + (1ull << (shift - 1))) >> shift);
+}
+
+// writes ONLY the pixels inside the destinations: the page keeps every other byte (resample_pack_kernel ran before)
+__global__ __launch_bounds__(THREADS) void warp_pack_kernel(const unsigned char* __restrict__ src, int Hs, int Ws,
+                                                            const long long* __restrict__ table, int n,
+                                                            unsigned char* __restrict__ page, int Hp, int Wp) {
+  __shared__ TileLists L;
+  const int ty0 = blockIdx.y * TILE_H, tx0 = blockIdx.x * TILE_W;
+  find_tile_rows<WarpRow>(table, n, Hs, Ws, 1, ty0, tx0, L);
+  const int r = threadIdx.x / (TILE_W / QUAD), c = (threadIdx.x % (TILE_W / QUAD)) * QUAD;
+  const int y = ty0 + r, x = tx0 + c;
+  if (y >= Hp || x >= Wp) return;
+  int owner[QUAD];
+  resolve_owners(L, r, c, owner);
+  int cur = -1;
+  WarpRow p;
+  for (int q = 0; q < QUAD; ++q) {
+    if (owner[q] < 0 || x + q >= Wp) continue;
+    if (owner[q] != cur) {
+      cur = owner[q];
+      p = WarpRow::load(table, cur);
+    }
+    unsigned v[3];
+    warp_pixel(src, Hs, Ws, p, y - (int)p.dy, x + q - (int)p.dx, v);
+    unsigned char* out = page + ((long)y * Wp + x + q) * 3;
+    out[0] = (unsigned char)v[0]; out[1] = (unsigned char)v[1]; out[2] = (unsigned char)v[2];
+  }
+}
+
+// rough map coordinate under source pixel P of an axis of S image pixels: the pixel's centre, as region_crops' inverse
+__device__ __forceinline__ int map_cell(long long P, int S, int valid) {
+  const long long m = ((2 * P + 1) * valid) / (2LL * S);
+  return (int)(m < valid - 1 ? m : valid - 1);
+}
+
+// writes ONLY the cells whose centres lie inside the destinations (pack_labels_kernel ran before)
+__global__ __launch_bounds__(THREADS) void warp_labels_kernel(const int* __restrict__ labels, int Wl, int valid_h, int valid_w,
+                                                              int Hs, int Ws, const long long* __restrict__ table,
+                                                              const int* __restrict__ region_ids, int n, int f,
+                                                              int* __restrict__ out, int Hq, int Wq) {
+  __shared__ TileLists L;
+  const int ty0 = blockIdx.y * TILE_H, tx0 = blockIdx.x * TILE_W;
+  find_tile_rows<WarpRow>(table, n, Hs, Ws, f, ty0, tx0, L);
+  const int r = threadIdx.x / (TILE_W / QUAD), c = (threadIdx.x % (TILE_W / QUAD)) * QUAD;
+  const int y = ty0 + r, x = tx0 + c;
+  if (y >= Hq || x >= Wq) return;
+  int owner[QUAD];
+  resolve_owners(L, r, c, owner);
+  int cur = -1, rid = 0;
+  WarpRow p;
+  for (int q = 0; q < QUAD; ++q) {
+    if (owner[q] < 0 || x + q >= Wq) continue;
+    if (owner[q] != cur) {
+      cur = owner[q];
+      p = WarpRow::load(table, cur);
+      rid = region_ids[cur];
+    }
+    const long long i2 = 2LL * y * f + f - 2 * p.dy - 1, j2 = 2LL * (x + q) * f + f - 2 * p.dx - 1;
+    const long long Yp = (p.ay + ((i2 * p.myy + j2 * p.myx) >> 1) + 32768) >> 16;
+    const long long Xp = (p.ax + ((i2 * p.mxy + j2 * p.mxx) >> 1) + 32768) >> 16;
+    int v = 0;
+    if (Yp >= 0 && Yp < Hs && Xp >= 0 && Xp < Ws) {
+      const int other = labels[(long)map_cell(Yp, Hs, valid_h) * Wl + map_cell(Xp, Ws, valid_w)];
+      v = (other != 0 && other != rid) ? 0 : rid;
+    }
+    out[(long)y * Wq + x + q] = v;
+  }
+}
+
 }  // namespace
 
 extern "C" int vkas_resample_pack_u8(const unsigned char* src, int Hs, int Ws, const int* placements, int n,
@@ -292,5 +434,41 @@ extern "C" int vkas_pack_region_labels(const int* labels, int Hl, int Wl, int va
   pack_labels_kernel<<<grid, THREADS, 0, vkas_stream(stream)>>>(labels, Wl, valid_h, valid_w, Hs, Ws, placements,
                                                                 region_ids, n, fdf, out, Hq, Wq, vec_stores);
   VKAS_LAUNCH_CHECK("pack_region_labels");
+  return VKAS_OK;
+}
+
+extern "C" int vkas_warp_pack_u8(const unsigned char* src, int Hs, int Ws, const long long* warps, int n, unsigned char* page,
+                                 int Hp, int Wp, void* stream) {
+  VKAS_CHECK(src && page, "vkas_warp_pack_u8: null pointer");
+  VKAS_CHECK(n >= 0 && (n == 0 || warps), "vkas_warp_pack_u8: bad table (n %d)", n);
+  VKAS_CHECK(Hs >= 1 && Ws >= 1 && Hp >= 1 && Wp >= 1, "vkas_warp_pack_u8: bad dims");
+  VKAS_CHECK(Hs <= DIM_MAX && Ws <= DIM_MAX && Hp <= DIM_MAX && Wp <= DIM_MAX,
+             "vkas_warp_pack_u8: source and page sides must not exceed %d", DIM_MAX);
+  VKAS_CHECK((((uintptr_t)warps) & 7u) == 0, "vkas_warp_pack_u8: the warp table must be 8-byte aligned");
+  if (n == 0) return VKAS_OK;  // nothing to write: the page stays as it is
+  const dim3 grid((unsigned)vkas_cdiv(Wp, TILE_W), (unsigned)vkas_cdiv(Hp, TILE_H));
+  warp_pack_kernel<<<grid, THREADS, 0, vkas_stream(stream)>>>(src, Hs, Ws, warps, n, page, Hp, Wp);
+  VKAS_LAUNCH_CHECK("warp_pack_u8");
+  return VKAS_OK;
+}
+
+extern "C" int vkas_warp_region_labels(const int* labels, int Hl, int Wl, int valid_h, int valid_w, int Hs, int Ws,
+                                       const long long* warps, const int* region_ids, int n, int fdf, int* out, int Hq, int Wq,
+                                       void* stream) {
+  VKAS_CHECK(labels && out, "vkas_warp_region_labels: null pointer");
+  VKAS_CHECK(n >= 0 && (n == 0 || (warps && region_ids)), "vkas_warp_region_labels: bad table (n %d)", n);
+  VKAS_CHECK(Hl >= 1 && Wl >= 1 && Hs >= 1 && Ws >= 1 && Hq >= 1 && Wq >= 1, "vkas_warp_region_labels: bad dims");
+  VKAS_CHECK(valid_h >= 1 && valid_h <= Hl && valid_w >= 1 && valid_w <= Wl,
+             "vkas_warp_region_labels: the valid part %d x %d does not fit the %d x %d label map", valid_h, valid_w, Hl, Wl);
+  VKAS_CHECK(fdf >= 1 && fdf <= 64, "vkas_warp_region_labels: bad factor %d", fdf);
+  VKAS_CHECK(Hl <= DIM_MAX && Wl <= DIM_MAX && Hs <= DIM_MAX && Ws <= DIM_MAX && (long)Hq * fdf <= DIM_MAX &&
+                 (long)Wq * fdf <= DIM_MAX,
+             "vkas_warp_region_labels: map, source and page sides must not exceed %d", DIM_MAX);
+  VKAS_CHECK((((uintptr_t)warps) & 7u) == 0, "vkas_warp_region_labels: the warp table must be 8-byte aligned");
+  if (n == 0) return VKAS_OK;
+  const dim3 grid((unsigned)vkas_cdiv(Wq, TILE_W), (unsigned)vkas_cdiv(Hq, TILE_H));
+  warp_labels_kernel<<<grid, THREADS, 0, vkas_stream(stream)>>>(labels, Wl, valid_h, valid_w, Hs, Ws, warps, region_ids, n, fdf,
+                                                                out, Hq, Wq);
+  VKAS_LAUNCH_CHECK("warp_region_labels");
   return VKAS_OK;
 }

@@ -16,11 +16,13 @@ The step the model is named after - cut every text region out of the page, resca
 height becomes 35 px and stack the cuts into the page of the precise pass (:190-293) - runs on the device too
 (csrc/respack.hip, ``ops.resample_pack_u8`` / ``ops.pack_region_labels``), and ``infer`` chains all of it: image in,
 characters per region in image coordinates out.  It differs from the reference where vkit and cv2 (absent here) would be
-needed: a region's axis-aligned box stands in for the flattened region, so nothing is rotated or straightened; the
+needed: a region's axis-aligned box stands in for the flattened region - unless ``precise_text_region_orient`` is set: then
+an elongated, slanted region is cut out along its own axis and turned by the small angle that makes it axis-parallel
+(inferencing/orient.py, csrc/orient.hip; deskewing only: no perspective, no curved lines, no polygon dilation) -; the
 interpolation rule is this project's own, in integers (inferencing/packing.py); stacking is a shelf packing; and a character
 of a neighbouring region inside an overlapping box is excluded through the rough label map instead of ``flattened_mask``.
 
-Out of scope: polygons of the rough regions and flattening proper (vkit, cv2).  Images are plain (H, W, 3) uint8 arrays instead of ``vkit.element.Image``; results carry
+Out of scope: polygons of the rough regions and flattening beyond deskewing (vkit, cv2).  Images are plain (H, W, 3) uint8 arrays instead of ``vkit.element.Image``; results carry
 numpy arrays instead of ``Mask`` / ``ScoreMap`` / ``Polygon``.  The reference loads a TorchScript file (``model_jit``,
 :85-90); so does this mirror (``torch.jit.save`` of ``torch.jit.script(model)``, see model/scripting.py), and it also takes
 the scripted or the eager ``AdaptiveScaling`` module itself, or a state-dict file in the reference's ``RestoreState`` schema.
@@ -36,7 +38,8 @@ import torch
 from .opt import pad_mat_to_make_divisible
 from .graphs import GraphCache, param_stamp
 from .regions import region_scales
-from .packing import SIDE_MAX, region_crops, remap_polygons, stack_regions
+from .packing import SIDE_MAX, check_warps, region_crops, remap_polygons, remap_polygons_affine, stack_regions
+from .orient import orient_regions, region_directions, warp_row
 from .. import ops
 from .._lib import lib, check
 from ..model import AdaptiveScaling, AdaptiveScalingConfig
@@ -83,6 +86,12 @@ class AdaptiveScalingInferencingConfig:
     # of up to 255 rows of padding for the precise pass.
     precise_page_width_max: int = 2048
     precise_page_height_step: int = 256
+    # Oriented text regions (inferencing/orient.py; the reference's TextRegionFlattener, deskewing only), read by infer: a
+    # kept region that is slanted by at least 1 degree, whose oriented rectangle is at least this many times longer than
+    # wide (the reference's typical_long_side_ratio_min) and packs smaller than its box, is cut out along its own axis.
+    # Off: every result is bit for bit what it is without the feature.
+    precise_text_region_orient: bool = False
+    precise_text_region_flattener_typical_long_side_ratio_min: float = 3.0
 
 
 @attrs.define
@@ -148,6 +157,12 @@ class AdaptiveScalingInferencingResult:
     points: Sequence[np.ndarray]    # per region (k, 2) int32 (y, x) in the precise maps of the page
     probs: Sequence[np.ndarray]     # per region (k,) float32
     polygons: Sequence[np.ndarray]  # per region (k, 4, 2) float64 (y, x) in image pixels
+    # oriented regions (config.precise_text_region_orient; empty / all False without it): ``placements`` holds the
+    # axis-aligned rows only, an oriented region has a warp row instead (inferencing/packing.py), and ``regions.keep`` /
+    # ``regions.resized_shapes`` are the rule's after orientation
+    oriented: np.ndarray = attrs.field(factory=lambda: np.zeros((0,), bool))             # (N,) bool
+    warps: np.ndarray = attrs.field(factory=lambda: np.zeros((0, 12), np.int64))         # (K, 12) int64
+    warp_regions: np.ndarray = attrs.field(factory=lambda: np.zeros((0,), np.int32))     # (K,) int32, 1-based
 
 
 def rough_resized_shape(height: int, width: int, short_side: int) -> Tuple[int, int]:
@@ -287,9 +302,10 @@ class AdaptiveScalingInferencing:
             resized_shape=(math.ceil(h / fdf), math.ceil(w / fdf)), padded_image=padded,
             rough_char_mask=out_mask[0].cpu().numpy(), rough_char_height_score_map=out_height[0].cpu().numpy())
 
-    def _rough_text_regions(self, x, image_shape, h: int, w: int, padded, return_labels: bool):
+    def _rough_text_regions(self, x, image_shape, h: int, w: int, padded, return_labels: bool, with_moments: bool = False):
         """The rough-plus-regions graph on a device input and the table rows read back: the result, and the device label
-        map (a static output of the graph: consume it before the next graph of this cache runs)."""
+        map (a static output of the graph: consume it before the next graph of this cache runs).  ``with_moments``: the
+        graph - one of its own key - also takes the regions' moments (csrc/orient.hip); their rows come third."""
         c = self.config
         fdf = 4 // c.rough_head_upsampling_factor
         H, W = x.shape[2] // fdf, x.shape[3] // fdf
@@ -300,11 +316,23 @@ class AdaptiveScalingInferencing:
         def rough_regions_pass(x, vh, vw):  # model call, post-processing and region table: one HIP graph per padded shape
             return ops.text_regions(*self._rough_maps(x, vh, vw, H, W), cap)
 
+        def rough_regions_moments_pass(x, vh, vw):
+            out = rough_regions_pass(x, vh, vw)
+            return out + (ops.region_moments(out[1], cap),)
+
+        moments = None
         with torch.no_grad():
-            count, labels, boxes, areas, valid, medians = self.graphs.run(
-                ('rough_text_regions', thr, hmin, cap), rough_regions_pass, [x, vh, vw], param_stamp(self.model))
+            if with_moments:
+                count, labels, boxes, areas, valid, medians, moments = self.graphs.run(
+                    ('rough_text_regions_moments', thr, hmin, cap), rough_regions_moments_pass, [x, vh, vw],
+                    param_stamp(self.model))
+            else:
+                count, labels, boxes, areas, valid, medians = self.graphs.run(
+                    ('rough_text_regions', thr, hmin, cap), rough_regions_pass, [x, vh, vw], param_stamp(self.model))
         num = int(count[0].item())
         n = min(num, cap)
+        if with_moments:
+            moments = moments[0, :n].cpu().numpy()
         boxes, areas, valid, medians = (t[0, :n].cpu().numpy() for t in (boxes, areas, valid, medians))
         resized_shape = (math.ceil(h / fdf), math.ceil(w / fdf))
         scales, resized_shapes, keep = region_scales(
@@ -313,7 +341,7 @@ class AdaptiveScalingInferencing:
         return AdaptiveScalingInferencingRoughTextRegions(
             resized_shape=resized_shape, padded_image=padded, num_regions=num,
             labels=labels[0].cpu().numpy() if return_labels else None, boxes=boxes, areas=areas, valid=valid,
-            char_height_medians=medians, scales=scales, resized_shapes=resized_shapes, keep=keep), labels[0]
+            char_height_medians=medians, scales=scales, resized_shapes=resized_shapes, keep=keep), labels[0], moments
 
     def rough_infer_text_regions(self, image, resize_fn=None,
                                  return_labels: bool = True) -> AdaptiveScalingInferencingRoughTextRegions:
@@ -434,7 +462,13 @@ class AdaptiveScalingInferencing:
         the label under their point and their quadrilaterals mapped back into the image.  The image, the maps and the page
         do not cross back over PCIe unless ``return_page`` / ``return_labels`` ask for them.  Equal, bit for bit, to
         ``rough_infer_text_regions`` -> ``resample_host`` -> ``precise_infer_char_polygons`` ->
-        ``precise_group_char_polygons`` -> ``remap_polygons``."""
+        ``precise_group_char_polygons`` -> ``remap_polygons``.
+
+        With ``config.precise_text_region_orient`` the rough graph (one of its own key) also takes the regions' moments;
+        their directions go up and their extents come back - one extra small round trip -; the rule of
+        inferencing/orient.py decides which regions are oriented; ``stack_regions`` runs on the mixed shapes;
+        ``ops.warp_pack_u8`` / ``ops.warp_region_labels`` write the oriented regions into the page and the label page after
+        the axis-aligned ones; their characters go back through ``remap_polygons_affine``."""
         c = self.config
         mat = _as_mat(image)
         if mat.dtype != np.uint8:
@@ -443,44 +477,73 @@ class AdaptiveScalingInferencing:
         h, w = rough_resized_shape(image_shape[0], image_shape[1], c.rough_downsample_short_side_legnth)
         src = torch.from_numpy(np.ascontiguousarray(mat)).to(c.device, non_blocking=True)
         rough_page = self._device_rough_page(src, h, w)
-        regions, d_labels = self._rough_text_regions(rough_page[None].permute(0, 3, 1, 2).float(), image_shape, h, w,
-                                                     rough_page.cpu().numpy() if return_page else None, return_labels)
+        orient = bool(c.precise_text_region_orient)
+        regions, d_labels, moments = self._rough_text_regions(
+            rough_page[None].permute(0, 3, 1, 2).float(), image_shape, h, w, rough_page.cpu().numpy() if return_page else None,
+            return_labels, with_moments=orient)
         n = len(regions.boxes)
         crops = region_crops(regions.boxes, image_shape, regions.resized_shape)
         source_fits = (crops[:, 2:] <= SIDE_MAX).all(axis=1)
+        oriented = np.zeros((n,), bool)
+        if orient and n:
+            # the one extra round trip of the oriented path: directions up, extents back (both a few bytes per region)
+            _, dirs = region_directions(moments)
+            extents = ops.region_extents(d_labels[None], dirs[None])[0].cpu().numpy()
+            oriented, rects, shapes, keep = orient_regions(
+                dirs, extents, regions.scales, regions.resized_shapes, regions.keep, image_shape, regions.resized_shape,
+                c.precise_text_region_flattener_typical_long_side_ratio_min,
+                c.precise_flattened_text_region_resized_char_height_median, c.precise_flattened_text_region_resized_ratio_min)
+            regions = attrs.evolve(regions, resized_shapes=shapes, keep=keep)
+            source_fits = source_fits | oriented  # an oriented region has no crop: its warp row was checked by the rule
         page_shape, boxes, packed, too_large = stack_regions(
             regions.resized_shapes, c.precise_stack_flattened_text_regions_page_pad, c.precise_stack_flattened_text_regions_pad,
             c.precise_page_width_max, c.precise_page_height_step, keep=regions.keep & source_fits)
         too_large |= regions.keep & ~source_fits
-        ids = (np.flatnonzero(packed) + 1).astype(np.int32)
-        placements = np.ascontiguousarray(np.concatenate([crops[packed], boxes[packed]], axis=1).astype(np.int32))
+        straight = packed & ~oriented
+        ids = (np.flatnonzero(straight) + 1).astype(np.int32)
+        placements = np.ascontiguousarray(np.concatenate([crops[straight], boxes[straight]], axis=1).astype(np.int32))
+        warp_ids = (np.flatnonzero(packed & oriented) + 1).astype(np.int32)
+        warps = np.zeros((len(warp_ids), 12), np.int64)
+        for k, rid in enumerate(warp_ids.tolist()):
+            warps[k] = warp_row(dirs[rid - 1], rects[rid - 1], image_shape, regions.resized_shape, boxes[rid - 1],
+                                regions.scales[rid - 1])
         empty = lambda *shape, dtype: np.zeros(shape, dtype)
         points = [empty(0, 2, dtype=np.int32) for _ in range(n)]
         probs = [empty(0, dtype=np.float32) for _ in range(n)]
         polygons = [empty(0, 4, 2, dtype=np.float64) for _ in range(n)]
         page = region_labels = None
-        if len(ids):
+        if len(ids) or len(warp_ids):
             fdf = 4 // c.precise_head_upsampling_factor
             d_page = ops.resample_pack_u8(src, placements, page_shape)
             d_region_labels = ops.pack_region_labels(d_labels, regions.resized_shape, image_shape, placements, ids,
                                                      (page_shape[0] // fdf, page_shape[1] // fdf), fdf)
+            if len(warp_ids):
+                check_warps(warps, page_shape, placements)
+                d_warps = torch.from_numpy(warps).to(c.device, non_blocking=True)
+                ops.warp_pack_u8(src, d_warps, d_page, validate=False)
+                ops.warp_region_labels(d_labels, regions.resized_shape, image_shape, d_warps, warp_ids, d_region_labels, fdf,
+                                       validate=False)
             d_points, d_probs, d_quads = self._char_polygons(d_page[None].permute(0, 3, 1, 2).float(), [page_shape],
                                                              on_device=True)
             at = d_region_labels[d_points[:, 1].long(), d_points[:, 2].long()].cpu().numpy()
             all_points, all_probs, all_quads = (t.cpu().numpy() for t in (d_points[:, 1:], d_probs, d_quads))
-            for k, rid in enumerate(ids.tolist()):
-                sel = at == rid
-                points[rid - 1] = np.ascontiguousarray(all_points[sel])
-                probs[rid - 1] = all_probs[sel]
-                polygons[rid - 1] = remap_polygons(all_quads[sel], placements[k])
+            for table, table_ids, remap in ((placements, ids, remap_polygons), (warps, warp_ids, remap_polygons_affine)):
+                for k, rid in enumerate(table_ids.tolist()):
+                    sel = at == rid
+                    points[rid - 1] = np.ascontiguousarray(all_points[sel])
+                    probs[rid - 1] = all_probs[sel]
+                    polygons[rid - 1] = remap(all_quads[sel], table[k])
             if return_page:
                 page = d_page.cpu().numpy()
             if return_labels:
                 region_labels = d_region_labels.cpu().numpy()
-        return AdaptiveScalingInferencingResult(
+        result = AdaptiveScalingInferencingResult(
             image_shape=image_shape, regions=regions, packed=packed, too_large=too_large, placements=placements,
             placement_regions=ids, page_shape=page_shape, page=page, region_labels=region_labels, points=points, probs=probs,
             polygons=polygons)
+        if orient:
+            result.oriented, result.warps, result.warp_regions = oriented, warps, warp_ids
+        return result
 
     @staticmethod
     def precise_group_char_polygons(result: AdaptiveScalingInferencingPreciseCharPolygons,

@@ -5,7 +5,9 @@
 The reference flattens every text region (vkit, cv2), resizes it with cv2's interpolation and stacks the results with
 ``stack_flattened_text_regions``.  vkit and cv2 are absent here, so the step is restated on pixels:
 
-* a region's axis-aligned box stands in for the flattened region (no rotation, no perspective);
+* a region's axis-aligned box stands in for the flattened region (no rotation, no perspective) - or, for a region that
+  inferencing/orient.py finds elongated and slanted, its oriented rectangle: an affine **warp** (the last part of this
+  module; ``ops.warp_pack_u8`` / ``ops.warp_region_labels``);
 * the interpolation rule is this project's own, defined in integers so that host and device agree bit for bit;
 * stacking is a deterministic shelf packing.
 
@@ -220,4 +222,132 @@ def remap_polygons(polygons, placement) -> np.ndarray:
     out = np.empty(p.shape, np.float64)
     out[..., 0] = sy + (p[..., 0] - dy) * sh / dh
     out[..., 1] = sx + (p[..., 1] - dx) * sw / dw
+    return out
+
+
+# ---- affine warps: a slanted region cut out along its own axis (inferencing/orient.py builds the rows) ------------------
+# A **warp** is a row ``(dy, dx, dh, dw, ay, ax, myy, myx, mxy, mxx, log2n, 0)`` of int64: destination pixel ``(i, j)`` of the
+# page rectangle ``[dy, dy + dh) x [dx, dx + dw)`` reads the source at the sample coordinates ``Y = ay + i*myy + j*myx``,
+# ``X = ax + i*mxy + j*mxx`` in Q16; an integer coordinate is a pixel centre.  With ``n = 2^log2n`` a pixel is the mean of
+# ``n x n`` sub-samples at ``Y + ((2a+1-n)*myy + (2b+1-n)*myx) >> (1 + log2n)`` (floor; ``X`` likewise), each two-tap
+# bilinear per axis: ``k = Y >> 16``, ``f = Y & 65535``, weights ``(65536 - f, f)`` on ``k`` and ``k + 1``, a tap outside the
+# source reading 0.  A channel is ``(sum + den/2) >> (32 + 2*log2n)``: one rounding, 64-bit sums (below 2^46), shifts only.
+# ``n`` is the smallest power of two >= 1/scale, at most 8: a region shrunk by more than 8 aliases.
+WARP_M_MAX = 1 << 22   # |myy|, |myx|, |mxy|, |mxx|: a destination step of at most 64 source pixels
+WARP_A_MAX = 1 << 40   # |ay|, |ax| stay below
+
+
+def check_warps(warps, page_shape: Tuple[int, int], placements=None) -> np.ndarray:
+    """Validates a (K, 12) warp table against an (Hp, Wp) page - integer rows, sides in [1, SIDE_MAX], coefficients within
+    their bounds, destinations inside the page, pairwise disjoint and disjoint from the destinations of the (n, 8)
+    ``placements`` (if given) - and returns it as contiguous int64.  Raises ValueError."""
+    w = np.asarray(warps)
+    if w.ndim != 2 or w.shape[1] != 12 or not np.issubdtype(w.dtype, np.integer):
+        raise ValueError(f'warps must be a (K, 12) integer table, got {w.dtype} {w.shape}')
+    w = np.ascontiguousarray(w.astype(np.int64))
+    Hp, Wp = (int(v) for v in page_shape)
+    dy, dx, dh, dw = w[:, 0], w[:, 1], w[:, 2], w[:, 3]
+    if ((w[:, 2:4] < 1) | (w[:, 2:4] > SIDE_MAX)).any():
+        raise ValueError(f'warps: every side must be in [1, {SIDE_MAX}]')
+    if ((dy < 0) | (dx < 0) | (dy + dh > Hp) | (dx + dw > Wp)).any():
+        raise ValueError(f'warps: a destination rectangle leaves the {(Hp, Wp)} page')
+    if (np.abs(w[:, 6:10]) > WARP_M_MAX).any() or (np.abs(w[:, 4:6]) >= WARP_A_MAX).any():
+        raise ValueError(f'warps: a coefficient exceeds 2^22 or an anchor reaches 2^40')
+    if ((w[:, 10] < 0) | (w[:, 10] > 3)).any():
+        raise ValueError('warps: log2n must be in [0, 3]')
+    rects = w[:, :4]
+    if placements is not None:
+        rects = np.concatenate([rects, np.asarray(placements, dtype=np.int64).reshape(-1, 8)[:, 4:]])
+    ry, rx, rh, rw = rects.T
+    order = np.argsort(ry, kind='stable')  # the sweep of check_placements, over warps and placements together
+    live = []
+    for r in order:
+        live = [k for k in live if ry[k] + rh[k] > ry[r]]
+        for k in live:
+            if min(k, r) < len(w) and rx[k] < rx[r] + rw[r] and rx[r] < rx[k] + rw[k]:
+                raise ValueError(f'warps: destination {int(min(k, r))} overlaps another destination')
+        live.append(r)
+    return w
+
+
+def _warp_samples(src: np.ndarray, Y: np.ndarray, X: np.ndarray) -> np.ndarray:
+    """One bilinear sub-sample per element of the int64 Q16 coordinate arrays (Y, X): (..., 3) int64 channel sums, the
+    weights of a sample summing to 2^32 (so a sum stays below 2^40)."""
+    Hs, Ws = src.shape[:2]
+    ky, fy, kx, fx = Y >> 16, Y & 65535, X >> 16, X & 65535
+    total = np.zeros(Y.shape + (3,), np.int64)
+    for k, wy in ((ky, 65536 - fy), (ky + 1, fy)):
+        for m, wx in ((kx, 65536 - fx), (kx + 1, fx)):
+            inside = (k >= 0) & (k < Hs) & (m >= 0) & (m < Ws)
+            pixels = src[np.clip(k, 0, Hs - 1), np.clip(m, 0, Ws - 1)].astype(np.int64)
+            total += np.where(inside, wy * wx, 0)[..., None] * pixels
+    return total
+
+
+def warp_host(src: np.ndarray, warps, page: np.ndarray) -> np.ndarray:
+    """The definition: writes the pixels of the (K, 12) warps into a copy of the (Hp, Wp, 3) uint8 ``page`` and leaves
+    every other byte of it alone.  Plain: one int64 array expression per sub-sample and tap."""
+    src, page = np.asarray(src), np.array(page)
+    if src.ndim != 3 or src.shape[2] != 3 or src.dtype != np.uint8:
+        raise ValueError(f'src must be an (H, W, 3) uint8 image, got {src.dtype} {src.shape}')
+    if page.ndim != 3 or page.shape[2] != 3 or page.dtype != np.uint8:
+        raise ValueError(f'page must be an (H, W, 3) uint8 image, got {page.dtype} {page.shape}')
+    for dy, dx, dh, dw, ay, ax, myy, myx, mxy, mxx, log2n, _ in check_warps(warps, page.shape[:2]).tolist():
+        n, shift = 1 << log2n, 32 + 2 * log2n
+        i, j = np.arange(dh, dtype=np.int64)[:, None], np.arange(dw, dtype=np.int64)[None, :]
+        Y, X = ay + i * myy + j * myx, ax + i * mxy + j * mxx
+        total = np.zeros((dh, dw, 3), np.int64)
+        for a in range(n):
+            for b in range(n):
+                ka, kb = 2 * a + 1 - n, 2 * b + 1 - n
+                total += _warp_samples(src, Y + ((ka * myy + kb * myx) >> (1 + log2n)), X + ((ka * mxy + kb * mxx) >> (1 + log2n)))
+        page[dy:dy + dh, dx:dx + dw] = (total + (1 << (shift - 1))) >> shift
+    return page
+
+
+def warp_region_labels_host(labels: np.ndarray, valid_shape: Tuple[int, int], image_shape: Tuple[int, int], warps,
+                            region_ids, out: np.ndarray, fdf: int) -> np.ndarray:
+    """The label cells of the warps, written into a copy of the (Hq, Wq) int32 label page ``out`` (every other cell stays):
+    a cell ``(v, u)`` whose centre lies in the destination of warp k (``label_cells``) has ``i2 = 2*v*fdf + fdf - 2*dy - 1``
+    (twice its row in the destination, pixel centres being integers), ``j2`` likewise, ``Y = ay + ((i2*myy + j2*myx) >> 1)``
+    and the source pixel ``Yp = (Y + 32768) >> 16``.  Outside the image the cell gets 0; else ``region_ids[k]`` unless the
+    rough map holds another region's label at row ``min(vh - 1, ((2*Yp + 1) * vh) // (2*Hs))``, column likewise."""
+    labels, out = np.asarray(labels), np.array(out)
+    if labels.ndim != 2 or labels.dtype != np.int32 or out.ndim != 2 or out.dtype != np.int32:
+        raise ValueError('labels and out must be (H, W) int32 maps')
+    vh, vw = (int(v) for v in valid_shape)
+    Hs, Ws = (int(v) for v in image_shape)
+    Hq, Wq = out.shape
+    fdf = int(fdf)
+    table = check_warps(warps, (Hq * fdf, Wq * fdf))
+    ids = np.asarray(region_ids).reshape(-1)
+    if len(ids) != len(table):
+        raise ValueError(f'{len(ids)} region ids for {len(table)} warps')
+    for (dy, dx, dh, dw, ay, ax, myy, myx, mxy, mxx, _, _), rid in zip(table.tolist(), ids.tolist()):
+        v0, v1 = label_cells(dy, dh, fdf)
+        u0, u1 = label_cells(dx, dw, fdf)
+        for v in range(v0, min(v1, Hq)):
+            i2 = 2 * v * fdf + fdf - 2 * dy - 1
+            for u in range(u0, min(u1, Wq)):
+                j2 = 2 * u * fdf + fdf - 2 * dx - 1
+                Yp = (ay + ((i2 * myy + j2 * myx) >> 1) + 32768) >> 16
+                Xp = (ax + ((i2 * mxy + j2 * mxx) >> 1) + 32768) >> 16
+                if not (0 <= Yp < Hs and 0 <= Xp < Ws):
+                    out[v, u] = 0
+                    continue
+                other = int(labels[min(vh - 1, ((2 * Yp + 1) * vh) // (2 * Hs)), min(vw - 1, ((2 * Xp + 1) * vw) // (2 * Ws))])
+                out[v, u] = 0 if other not in (0, rid) else rid
+    return out
+
+
+def remap_polygons_affine(polygons, warp) -> np.ndarray:
+    """(..., 2) (y, x) page positions -> float64 positions in the image the warp's source refers to: ``(i, j) = (y - dy -
+    1/2, x - dx - 1/2)`` (destination pixel centres are integers), ``Y = (ay + i*myy + j*myx) / 65536 + 1/2``, ``X``
+    likewise - positions as ``remap_polygons`` gives them, pixel k covering ``[k, k + 1)``."""
+    dy, dx, _, _, ay, ax, myy, myx, mxy, mxx, _, _ = (int(v) for v in np.asarray(warp).reshape(12))
+    p = np.asarray(polygons, dtype=np.float64)
+    i, j = p[..., 0] - dy - 0.5, p[..., 1] - dx - 0.5
+    out = np.empty(p.shape, np.float64)
+    out[..., 0] = (ay + i * myy + j * myx) / 65536 + 0.5
+    out[..., 1] = (ax + i * mxy + j * mxx) / 65536 + 0.5
     return out

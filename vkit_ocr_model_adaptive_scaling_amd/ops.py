@@ -2456,3 +2456,166 @@ def pack_region_labels(labels: torch.Tensor, valid_shape: Tuple[int, int], image
     check(lib.vkas_pack_region_labels(_p(labels), Hl, Wl, vh, vw, Hs, Ws, _p(table) if n else None, _p(ids) if n else None, n,
                                       fdf, _p(out), Hq, Wq, _stream()), 'pack_region_labels')
     return out
+
+
+def _label_maps(who: str, labels: torch.Tensor, max_regions) -> Tuple[int, int, int, int]:
+    if labels.dim() != 3:
+        raise ValueError(f'{who}: labels must be (B, H, W), got {tuple(labels.shape)}')
+    if labels.dtype != torch.int32:
+        raise ValueError(f'{who}: labels must be int32, got {labels.dtype}')
+    B, H, W = (int(v) for v in labels.shape)
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError(f'{who}: empty maps {(B, H, W)}')
+    R = int(max_regions)
+    if R != max_regions or R < 1:
+        raise ValueError(f'{who}: max_regions must be an integer >= 1, got {max_regions}')
+    if max(H, W) > _PACK_DIM_MAX or B > 65535:
+        raise ValueError(f'{who}: map sides must not exceed {_PACK_DIM_MAX} and B 65535, got {(B, H, W)}')
+    if B * H * W >= 1 << 31 or B * R >= 1 << 31:
+        raise ValueError(f'{who}: B*H*W = {B * H * W} and B*R = {B * R} must stay below 2^31')
+    return B, H, W, R
+
+
+def region_moments(labels: torch.Tensor, max_regions: int) -> torch.Tensor:
+    """The raw moments of the text regions (csrc/orient.hip; the oracle: inferencing/orient.py::region_moments_host).  labels
+    (B,H,W) int32 on the device, as ``text_regions`` returns them.  Returns (B,R,6) int64 with R = ``max_regions``: row r-1 =
+    ``n, sum y, sum x, sum y^2, sum x^2, sum x*y`` over the pixels of region r, exact; label 0 and labels above R are ignored,
+    a region without pixels gets zeros.  Never synchronises, so it can be captured into a HIP graph."""
+    B, H, W, R = _label_maps('region_moments', labels, max_regions)
+    _require_cuda(labels)
+    labels = labels.contiguous()
+    out = torch.empty((B, R, 6), dtype=torch.int64, device=labels.device)
+    check(lib.vkas_region_moments(_p(labels), B, H, W, R, _p(out), _stream()), 'region_moments')
+    return out
+
+
+_DIR_MAX = 1 << 14
+
+
+def region_extents(labels: torch.Tensor, dirs, validate: bool = True) -> torch.Tensor:
+    """The extents of the text regions along their own directions (csrc/orient.hip; the oracle: inferencing/orient.py::
+    region_extents_host).  labels (B,H,W) int32 on the device; ``dirs`` (B,R,2) int32 ``(c, s)`` with ``|c|, |s| <= 2^14``,
+    host (numpy / CPU tensor: always checked, then uploaded) or device (checked when ``validate`` - a synchronisation -, else
+    trusted).  Returns (B,R,4) int32 ``min u, max u, min v, max v`` with ``u = c*x + s*y``, ``v = -s*x + c*y``; a region
+    without pixels keeps ``(INT_MAX, INT_MIN, INT_MAX, INT_MIN)``."""
+    import numpy as np
+    if not isinstance(dirs, torch.Tensor):
+        dirs = torch.from_numpy(np.ascontiguousarray(np.asarray(dirs)))
+    if dirs.dim() != 3 or dirs.shape[2] != 2:
+        raise ValueError(f'region_extents: dirs must be (B, R, 2), got {tuple(dirs.shape)}')
+    if dirs.dtype != torch.int32:
+        raise ValueError(f'region_extents: dirs must be int32, got {dirs.dtype}')
+    B, H, W, R = _label_maps('region_extents', labels, int(dirs.shape[1]))
+    if dirs.shape[0] != B:
+        raise ValueError(f'region_extents: dirs must be ({B}, R, 2), got {tuple(dirs.shape)}')
+    if (validate or not dirs.is_cuda) and int(dirs.abs().max()) > _DIR_MAX:
+        raise ValueError(f'region_extents: |c| and |s| must not exceed {_DIR_MAX}')
+    _require_cuda(labels)
+    if dirs.is_cuda and dirs.device != labels.device:
+        raise ValueError(f'region_extents: dirs are on {dirs.device}, labels on {labels.device}')
+    dirs = dirs.to(labels.device, non_blocking=True).contiguous()
+    labels = labels.contiguous()
+    out = torch.empty((B, R, 4), dtype=torch.int32, device=labels.device)
+    check(lib.vkas_region_extents(_p(labels), B, H, W, R, _p(dirs), _p(out), _stream()), 'region_extents')
+    return out
+
+
+def _warp_table(who: str, warps, page_shape, device, validate: bool) -> torch.Tensor:
+    """The (K, 12) int64 warp table on ``device``, checked as ``_placement_table`` checks placements
+    (inferencing/packing.py::check_warps: bounds, destinations inside the page and pairwise disjoint)."""
+    import numpy as np
+    from .inferencing.packing import check_warps
+    if isinstance(warps, torch.Tensor):
+        if warps.dim() != 2 or warps.shape[1] != 12:
+            raise ValueError(f'{who}: warps must be (K, 12), got {tuple(warps.shape)}')
+        if warps.dtype != torch.int64:
+            raise ValueError(f'{who}: warps must be int64, got {warps.dtype}')
+        if warps.is_cuda:
+            if validate:
+                check_warps(warps.cpu().numpy(), page_shape)
+            if warps.device != device:
+                raise ValueError(f'{who}: warps are on {warps.device}, the image on {device}')
+            return warps.contiguous()
+        warps = warps.numpy()
+    else:
+        warps = np.asarray(warps)
+        if warps.ndim != 2 or warps.shape[1] != 12:
+            raise ValueError(f'{who}: warps must be (K, 12), got {warps.shape}')
+        if warps.dtype != np.int64:
+            raise ValueError(f'{who}: warps must be int64, got {warps.dtype}')
+    table = torch.from_numpy(check_warps(warps, page_shape))
+    return table if device.type != 'cuda' else table.to(device, non_blocking=True)
+
+
+def warp_pack_u8(src: torch.Tensor, warps, page: torch.Tensor, validate: bool = True) -> torch.Tensor:
+    """Cuts slanted rectangles out of one image along their own axes into a page (csrc/respack.hip; the rule and the oracle:
+    inferencing/packing.py::warp_host).  src (Hs,Ws,3) uint8 and ``page`` (Hp,Wp,3) uint8, contiguous, on the device;
+    ``warps`` (K,12) int64 rows, host or device (as ``resample_pack_u8`` takes placements).  Writes ONLY the pixels inside
+    the warps' destinations - it runs after ``resample_pack_u8`` has written the page and its zeros - and returns ``page``.
+    The destinations must also be disjoint from that call's placements (``check_warps(..., placements)``: the caller's
+    check).  One launch; with a device table and ``validate=False`` it never synchronises."""
+    if src.dim() != 3 or src.shape[2] != 3 or page.dim() != 3 or page.shape[2] != 3:
+        raise ValueError(f'warp_pack_u8: src and page must be (H, W, 3), got {tuple(src.shape)} and {tuple(page.shape)}')
+    if src.dtype != torch.uint8 or page.dtype != torch.uint8:
+        raise ValueError(f'warp_pack_u8: src and page must be uint8, got {src.dtype} and {page.dtype}')
+    Hs, Ws, Hp, Wp = int(src.shape[0]), int(src.shape[1]), int(page.shape[0]), int(page.shape[1])
+    if Hs < 1 or Ws < 1 or Hp < 1 or Wp < 1:
+        raise ValueError(f'warp_pack_u8: empty source {(Hs, Ws)} or page {(Hp, Wp)}')
+    if max(Hs, Ws, Hp, Wp) > _PACK_DIM_MAX:
+        raise ValueError(f'warp_pack_u8: source {(Hs, Ws)} and page {(Hp, Wp)} sides must not exceed {_PACK_DIM_MAX}')
+    if not page.is_contiguous():
+        raise ValueError('warp_pack_u8: page must be contiguous (it is written in place)')
+    table = _warp_table('warp_pack_u8', warps, (Hp, Wp), src.device, validate)
+    _require_cuda(src, page)
+    if page.device != src.device:
+        raise ValueError(f'warp_pack_u8: page is on {page.device}, src on {src.device}')
+    src = src.contiguous()
+    K = int(table.shape[0])
+    check(lib.vkas_warp_pack_u8(_p(src), Hs, Ws, _p(table) if K else None, K, _p(page), Hp, Wp, _stream()), 'warp_pack_u8')
+    return page
+
+
+def warp_region_labels(labels: torch.Tensor, valid_shape: Tuple[int, int], image_shape: Tuple[int, int], warps, region_ids,
+                       out: torch.Tensor, fdf: int, validate: bool = True) -> torch.Tensor:
+    """The label cells of the warps, written into the (Hq,Wq) int32 label page ``out`` of ``pack_region_labels`` (csrc/
+    respack.hip; the rule and the oracle: inferencing/packing.py::warp_region_labels_host).  Arguments as
+    ``pack_region_labels`` with ``warps`` as in ``warp_pack_u8``; writes ONLY the cells whose centres lie inside the warps'
+    destinations and returns ``out``."""
+    if labels.dim() != 2 or out.dim() != 2:
+        raise ValueError(f'warp_region_labels: labels and out must be (H, W), got {tuple(labels.shape)} and {tuple(out.shape)}')
+    if labels.dtype != torch.int32 or out.dtype != torch.int32:
+        raise ValueError(f'warp_region_labels: labels and out must be int32, got {labels.dtype} and {out.dtype}')
+    Hl, Wl = int(labels.shape[0]), int(labels.shape[1])
+    vh, vw = (int(v) for v in valid_shape)
+    Hs, Ws = (int(v) for v in image_shape)
+    Hq, Wq = int(out.shape[0]), int(out.shape[1])
+    if not (1 <= vh <= Hl and 1 <= vw <= Wl):
+        raise ValueError(f'warp_region_labels: valid_shape {(vh, vw)} does not fit the {(Hl, Wl)} label map')
+    if fdf != int(fdf) or not 1 <= int(fdf) <= 64:
+        raise ValueError(f'warp_region_labels: fdf must be an integer in [1, 64], got {fdf}')
+    fdf = int(fdf)
+    if Hs < 1 or Ws < 1 or Hq < 1 or Wq < 1:
+        raise ValueError(f'warp_region_labels: empty image {(Hs, Ws)} or label page {(Hq, Wq)}')
+    if max(Hl, Wl, Hs, Ws, Hq * fdf, Wq * fdf) > _PACK_DIM_MAX:
+        raise ValueError(f'warp_region_labels: map, image and page sides must not exceed {_PACK_DIM_MAX}')
+    if not out.is_contiguous():
+        raise ValueError('warp_region_labels: out must be contiguous (it is written in place)')
+    table = _warp_table('warp_region_labels', warps, (Hq * fdf, Wq * fdf), labels.device, validate)
+    K = int(table.shape[0])
+    if not isinstance(region_ids, torch.Tensor):
+        import numpy as np
+        region_ids = torch.from_numpy(np.ascontiguousarray(np.asarray(region_ids)))
+    if region_ids.dim() != 1 or region_ids.shape[0] != K:
+        raise ValueError(f'warp_region_labels: region_ids must be ({K},), got {tuple(region_ids.shape)}')
+    if region_ids.dtype != torch.int32:
+        raise ValueError(f'warp_region_labels: region_ids must be int32, got {region_ids.dtype}')
+    if not region_ids.is_cuda and K and int(region_ids.min()) < 1:
+        raise ValueError('warp_region_labels: region ids start at 1 (0 is "no region")')
+    _require_cuda(labels, out)
+    if out.device != labels.device:
+        raise ValueError(f'warp_region_labels: out is on {out.device}, labels on {labels.device}')
+    ids = region_ids.to(labels.device, non_blocking=True).contiguous()
+    labels = labels.contiguous()
+    check(lib.vkas_warp_region_labels(_p(labels), Hl, Wl, vh, vw, Hs, Ws, _p(table) if K else None, _p(ids) if K else None, K,
+                                      fdf, _p(out), Hq, Wq, _stream()), 'warp_region_labels')
+    return out
