@@ -531,6 +531,28 @@ int vkas_resample_pack_u8(const unsigned char* src, int Hs, int Ws, const int* p
 int vkas_pack_region_labels(const int* labels, int Hl, int Wl, int valid_h, int valid_w, int Hs, int Ws,
                             const int* placements, const int* region_ids, int n, int fdf, int* out, int Hq, int Wq,
                             void* stream);
+/* The same step for a batch (infer_batch): several sources, several pages, one launch.  The sources lie in one byte arena;
+ * sources (S,4) int64 rows (byte offset, Hs, Ws, 0): image s is (Hs,Ws,3) uint8 at arena + offset.  rows (n,12) int32 (src,
+ * page, sy, sx, sh, sw, dy, dx, dh, dw, local_id, global_id), sorted by page; page_start (Q+1) int32: page q owns
+ * rows[page_start[q] .. page_start[q+1]) (clamped to 0..n).  pages (Q,Hp,Wp,3) uint8; grid (ceil(Wp/64), ceil(Hp/16), Q).
+ * The resampling rule is vkas_resample_pack_u8's; EVERY byte of every page is written, 0 where no row reaches.  A row is
+ * skipped when src is outside 0..S-1, page != q, its sides or rectangles are out of range, or its source entry is (sides
+ * outside 1..32768, offset < 0, offset + 3*Hs*Ws > arena_bytes): every address is arena + offset and is checked against
+ * arena_bytes per row, so no table content makes the kernel touch memory outside its buffers.  Destinations are disjoint
+ * per page (the caller's check).  One launch; capture-safe: no allocation, no synchronisation, no atomics.  Q in 1..65535,
+ * Hp, Wp in 1..32768; rows 16-byte, sources 8-byte aligned. */
+int vkas_resample_pack_u8_multi(const unsigned char* arena, long long arena_bytes, const long long* sources, int S,
+                                const int* rows, int n, const int* page_start, unsigned char* pages, int Q, int Hp, int Wp,
+                                void* stream);
+/* The label pages that go with them: out (Q,Hq,Wq) int32 at 1/fdf of the pages.  The rough label maps of the batch (local
+ * ids 1..N_i per image) lie in one int32 arena; label_sources (S,8) int64 rows (word offset, Hl, Wl, valid_h, valid_w, Hs,
+ * Ws, 0).  A label cell whose centre lies in a row's destination gets the row's global_id - unless the rough label under
+ * it (the source position of vkas_pack_region_labels) is neither 0 nor the row's local_id; then, and outside every row, 0.
+ * A row is skipped as above (entry: map and image sides outside 1..32768, valid part outside the map, offset < 0, offset +
+ * Hl*Wl > label_words).  Every out element is written; same contract otherwise; fdf in 1..64. */
+int vkas_pack_region_labels_multi(const int* label_arena, long long label_words, const long long* label_sources, int S,
+                                  const int* rows, int n, const int* page_start, int fdf, int* out, int Q, int Hq, int Wq,
+                                  void* stream);
 /* Orientation of the text regions (inferencing/orient.py holds the rule and the host oracles).  labels (B,H,W) int32 as
  * vkas_text_regions writes them; R = max_regions rows per image, row r-1 for region r; label 0 and labels above R are
  * ignored.  moments (B,R,6) int64 = n, sum y, sum x, sum y^2, sum x^2, sum x*y over the region's pixels, exact (sides up to

@@ -191,6 +191,8 @@ _SIGS = {
     'vkas_resample_pack_u8': (c_int, [_P, c_int, c_int, _P, c_int, _P, c_int, c_int, _P]),
     'vkas_pack_region_labels': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, c_int, _P, c_int, c_int,
                                         _P]),
+    'vkas_resample_pack_u8_multi': (c_int, [_P, c_longlong, _P, c_int, _P, c_int, _P, _P, c_int, c_int, c_int, _P]),
+    'vkas_pack_region_labels_multi': (c_int, [_P, c_longlong, _P, c_int, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, _P]),
     'vkas_region_moments': (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
     'vkas_region_extents': (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P]),
     'vkas_warp_pack_u8': (c_int, [_P, c_int, c_int, _P, c_int, _P, c_int, c_int, _P]),

@@ -24,10 +24,15 @@ constexpr int LIST_CAP = TILE_H * TILE_W;                   // disjoint placemen
 constexpr int SIDE_MAX = 8192;
 constexpr int DIM_MAX = 32768;                              // source / page sides: pixel counts stay below 2^30
 
+// what a row is checked against: the one source of the single-image kernels; the multi kernels look theirs up per row
+struct SourceDims {
+  int Hs, Ws;
+};
+
 struct Placement {
   int sy, sx, sh, sw, dy, dx, dh, dw;
   static __device__ __forceinline__ Placement load(const int* __restrict__ table, int i);
-  __device__ __forceinline__ bool ok(int Hs, int Ws) const;
+  __device__ __forceinline__ bool ok(const SourceDims& d) const;
 };
 
 __device__ __forceinline__ Placement load_placement(const int* __restrict__ table, int i) {
@@ -52,27 +57,28 @@ __device__ __forceinline__ void cell_range(int d0, int dlen, int f, int& lo, int
 }
 
 __device__ __forceinline__ Placement Placement::load(const int* __restrict__ table, int i) { return load_placement(table, i); }
-__device__ __forceinline__ bool Placement::ok(int Hs, int Ws) const { return placement_ok(*this, Hs, Ws); }
 
 struct TileLists {
   int2 entry[WAVES][LIST_CAP];  // (row index, y0 | y1 << 8 | x0 << 16 | x1 << 24: hit rectangle in tile cells, exclusive ends)
   int count[WAVES];
 };
 
-// the rows of the table that own at least one cell of the tile at (ty0, tx0); f = page pixels per cell.  Row: the table's
-// row type (Placement, WarpRow) - load(table, i), ok(Hs, Ws) and the destination rectangle dy, dx, dh, dw
-template <class Row, class Word>
-__device__ __forceinline__ void find_tile_rows(const Word* __restrict__ table, int n, int Hs, int Ws, int f, int ty0, int tx0,
-                                               TileLists& L) {
+__device__ __forceinline__ bool Placement::ok(const SourceDims& d) const { return placement_ok(*this, d.Hs, d.Ws); }
+
+// the rows [begin, end) of the table that own at least one cell of the tile at (ty0, tx0); f = page pixels per cell.  Row:
+// the table's row type (Placement, WarpRow, MultiRow) - load(table, i), ok(ctx) and the destination rectangle dy, dx, dh, dw
+template <class Row, class Word, class Ctx>
+__device__ __forceinline__ void find_tile_rows(const Word* __restrict__ table, int begin, int end, const Ctx& ctx, int f,
+                                               int ty0, int tx0, TileLists& L) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int cnt = 0;
-  for (int base = wave * 64; base < n; base += THREADS) {
+  for (int base = begin + wave * 64; base < end; base += THREADS) {
     const int i = base + lane;
     bool hit = false;
     int packed = 0;
-    if (i < n) {
+    if (i < end) {
       const Row p = Row::load(table, i);
-      if (p.ok(Hs, Ws)) {
+      if (p.ok(ctx)) {
         int y0, y1, x0, x1;
         cell_range((int)p.dy, (int)p.dh, f, y0, y1);
         cell_range((int)p.dx, (int)p.dw, f, x0, x1);
@@ -95,7 +101,7 @@ __device__ __forceinline__ void find_tile_rows(const Word* __restrict__ table, i
 
 __device__ __forceinline__ void find_tile_placements(const int* __restrict__ table, int n, int Hs, int Ws, int f, int ty0,
                                                      int tx0, TileLists& L) {
-  find_tile_rows<Placement>(table, n, Hs, Ws, f, ty0, tx0, L);
+  find_tile_rows<Placement>(table, 0, n, SourceDims{Hs, Ws}, f, ty0, tx0, L);
 }
 
 // owner row of each of the thread's four cells (tile row r, tile columns c .. c + 3), -1 where there is none
@@ -177,6 +183,32 @@ __device__ __forceinline__ void resample_pixel(const unsigned char* __restrict__
   out[0] = round_div(acc0, den); out[1] = round_div(acc1, den); out[2] = round_div(acc2, den);
 }
 
+// the thread's quad of page pixels: cells of them lie inside the page
+__device__ __forceinline__ void store_pixels(unsigned char* __restrict__ out, const unsigned char bytes[QUAD * 3], int cells,
+                                             int dword_stores) {
+  if (dword_stores) {  // Wp % 4 == 0 and a 4-byte aligned page: the quad is whole and its 12 bytes are three aligned dwords
+    unsigned* o = reinterpret_cast<unsigned*>(out);
+#pragma unroll
+    for (int d = 0; d < 3; ++d)
+      o[d] = bytes[4 * d] | (bytes[4 * d + 1] << 8) | (bytes[4 * d + 2] << 16) | ((unsigned)bytes[4 * d + 3] << 24);
+  } else {
+    const int nb = cells * 3;
+#pragma unroll
+    for (int k = 0; k < QUAD * 3; ++k)
+      if (k < nb) out[k] = bytes[k];
+  }
+}
+
+__device__ __forceinline__ void store_labels(int* __restrict__ o, const int vals[QUAD], int cells, int vec_stores) {
+  if (vec_stores) {
+    *reinterpret_cast<int4*>(o) = make_int4(vals[0], vals[1], vals[2], vals[3]);
+  } else {
+#pragma unroll
+    for (int q = 0; q < QUAD; ++q)
+      if (q < cells) o[q] = vals[q];
+  }
+}
+
 __global__ __launch_bounds__(THREADS) void resample_pack_kernel(const unsigned char* __restrict__ src, int Hs, int Ws,
                                                                 const int* __restrict__ table, int n,
                                                                 unsigned char* __restrict__ page, int Hp, int Wp,
@@ -206,18 +238,7 @@ __global__ __launch_bounds__(THREADS) void resample_pack_kernel(const unsigned c
     }
     bytes[q * 3] = (unsigned char)v[0]; bytes[q * 3 + 1] = (unsigned char)v[1]; bytes[q * 3 + 2] = (unsigned char)v[2];
   }
-  unsigned char* out = page + ((long)y * Wp + x) * 3;
-  if (dword_stores) {  // Wp % 4 == 0 and a 4-byte aligned page: the quad is whole and its 12 bytes are three aligned dwords
-    unsigned* o = reinterpret_cast<unsigned*>(out);
-#pragma unroll
-    for (int d = 0; d < 3; ++d)
-      o[d] = bytes[4 * d] | (bytes[4 * d + 1] << 8) | (bytes[4 * d + 2] << 16) | ((unsigned)bytes[4 * d + 3] << 24);
-  } else {
-    const int nb = min(QUAD, Wp - x) * 3;
-#pragma unroll
-    for (int k = 0; k < QUAD * 3; ++k)
-      if (k < nb) out[k] = bytes[k];
-  }
+  store_pixels(page + ((long)y * Wp + x) * 3, bytes, min(QUAD, Wp - x), dword_stores);
 }
 
 // rough map coordinate under the centre of label cell c of a placement axis: packing.py's centre mapping
@@ -259,14 +280,149 @@ __global__ __launch_bounds__(THREADS) void pack_labels_kernel(const int* __restr
     }
     vals[q] = v;
   }
-  int* o = out + (long)y * Wq + x;
-  if (vec_stores) {
-    *reinterpret_cast<int4*>(o) = make_int4(vals[0], vals[1], vals[2], vals[3]);
-  } else {
-#pragma unroll
-    for (int q = 0; q < QUAD; ++q)
-      if (x + q < Wq) o[q] = vals[q];
+  store_labels(out + (long)y * Wq + x, vals, Wq - x, vec_stores);
+}
+
+// ---- several sources, several pages (infer_batch): one launch cuts the regions of many images into shared pages ---------
+// A multi row is 12 int32 (src, page, sy, sx, sh, sw, dy, dx, dh, dw, local_id, global_id), 48 bytes; the rows are sorted by
+// page and page_start (Q + 1) gives page q its slice.  The sources lie in ONE arena: a table of int64 rows per source gives
+// its offset and sides, every address is arena + offset, and the offset is checked against the arena's size per row - a
+// row whose source, page, sides, rectangles or table entry is out of range is absent, as a bad placement is.
+struct MultiRow {
+  int src, page, sy, sx, sh, sw, dy, dx, dh, dw, local_id, global_id;
+  static __device__ __forceinline__ MultiRow load(const int* __restrict__ table, int i) {
+    const int4* t = reinterpret_cast<const int4*>(table + (long)i * 12);
+    const int4 a = t[0], b = t[1], c = t[2];
+    return MultiRow{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w};
   }
+  __device__ __forceinline__ Placement placement() const { return Placement{sy, sx, sh, sw, dy, dx, dh, dw}; }
+  template <class Arena>
+  __device__ __forceinline__ bool ok(const Arena& A) const {
+    if (src < 0 || src >= A.S || page != A.q) return false;
+    int Hs, Ws;
+    return A.source_ok(src, Hs, Ws) && placement_ok(placement(), Hs, Ws);
+  }
+};
+
+__device__ __forceinline__ bool side_ok(long long v) { return v >= 1 && v <= DIM_MAX; }
+
+// image arena: bytes; a source row is (byte offset, Hs, Ws, 0) and the image takes 3*Hs*Ws bytes from its offset
+struct ImageArena {
+  const long long* __restrict__ sources;
+  long long size;
+  int S, q;
+  static constexpr int WORDS = 4;
+  __device__ __forceinline__ bool source_ok(int s, int& Hs, int& Ws) const {
+    const long long* t = sources + (long)s * WORDS;
+    const long long off = t[0], h = t[1], w = t[2];
+    if (!side_ok(h) || !side_ok(w)) return false;
+    Hs = (int)h; Ws = (int)w;
+    return off >= 0 && off <= size && 3 * h * w <= size - off;
+  }
+};
+
+// label arena: int32 words; a source row is (word offset, Hl, Wl, valid_h, valid_w, Hs, Ws, 0): the Hl x Wl map takes Hl*Wl
+// words from its offset, valid_h x valid_w of it cover the Hs x Ws image the row's source rectangle refers to
+struct LabelArena {
+  const long long* __restrict__ sources;
+  long long size;
+  int S, q;
+  static constexpr int WORDS = 8;
+  __device__ __forceinline__ bool source_ok(int s, int& Hs, int& Ws) const {
+    const long long* t = sources + (long)s * WORDS;
+    const long long off = t[0], hl = t[1], wl = t[2], vh = t[3], vw = t[4], h = t[5], w = t[6];
+    if (!side_ok(hl) || !side_ok(wl) || !side_ok(h) || !side_ok(w)) return false;
+    Hs = (int)h; Ws = (int)w;
+    return vh >= 1 && vh <= hl && vw >= 1 && vw <= wl && off >= 0 && off <= size && hl * wl <= size - off;
+  }
+};
+
+// page q's slice of the rows, whatever page_start holds
+__device__ __forceinline__ void page_slice(const int* __restrict__ page_start, int q, int n, int& lo, int& hi) {
+  lo = min(max(page_start[q], 0), n);
+  hi = min(max(page_start[q + 1], lo), n);
+}
+
+__global__ __launch_bounds__(THREADS) void resample_pack_multi_kernel(const unsigned char* __restrict__ arena,
+                                                                      long long arena_bytes,
+                                                                      const long long* __restrict__ sources, int S,
+                                                                      const int* __restrict__ rows, int n,
+                                                                      const int* __restrict__ page_start,
+                                                                      unsigned char* __restrict__ pages, int Hp, int Wp,
+                                                                      int dword_stores) {
+  __shared__ TileLists L;
+  const int q = blockIdx.z, ty0 = blockIdx.y * TILE_H, tx0 = blockIdx.x * TILE_W;
+  int lo, hi;
+  page_slice(page_start, q, n, lo, hi);
+  find_tile_rows<MultiRow>(rows, lo, hi, ImageArena{sources, arena_bytes, S, q}, 1, ty0, tx0, L);
+  const int r = threadIdx.x / (TILE_W / QUAD), c = (threadIdx.x % (TILE_W / QUAD)) * QUAD;
+  const int y = ty0 + r, x = tx0 + c;
+  if (y >= Hp || x >= Wp) return;
+  int owner[QUAD];
+  resolve_owners(L, r, c, owner);
+  unsigned char bytes[QUAD * 3];
+  int cur = -1, Ws = 0;
+  const unsigned char* src = arena;
+  Placement p;
+  Axis ay;
+#pragma unroll
+  for (int k = 0; k < QUAD; ++k) {
+    unsigned v[3] = {0u, 0u, 0u};
+    if (owner[k] >= 0 && x + k < Wp) {
+      if (owner[k] != cur) {  // a row of the lists passed ok(): its source entry lies inside the arena
+        cur = owner[k];
+        const MultiRow m = MultiRow::load(rows, cur);
+        const long long* t = sources + (long)m.src * ImageArena::WORDS;
+        src = arena + t[0];
+        Ws = (int)t[2];
+        p = m.placement();
+        ay.init(y - p.dy, p.sh, p.dh);
+      }
+      resample_pixel(src, Ws, p, ay, x + k - p.dx, v);
+    }
+    bytes[k * 3] = (unsigned char)v[0]; bytes[k * 3 + 1] = (unsigned char)v[1]; bytes[k * 3 + 2] = (unsigned char)v[2];
+  }
+  store_pixels(pages + (((long)q * Hp + y) * Wp + x) * 3, bytes, min(QUAD, Wp - x), dword_stores);
+}
+
+__global__ __launch_bounds__(THREADS) void pack_labels_multi_kernel(const int* __restrict__ arena, long long arena_words,
+                                                                    const long long* __restrict__ sources, int S,
+                                                                    const int* __restrict__ rows, int n,
+                                                                    const int* __restrict__ page_start, int f,
+                                                                    int* __restrict__ out, int Hq, int Wq, int vec_stores) {
+  __shared__ TileLists L;
+  const int q = blockIdx.z, ty0 = blockIdx.y * TILE_H, tx0 = blockIdx.x * TILE_W;
+  int lo, hi;
+  page_slice(page_start, q, n, lo, hi);
+  find_tile_rows<MultiRow>(rows, lo, hi, LabelArena{sources, arena_words, S, q}, f, ty0, tx0, L);
+  const int r = threadIdx.x / (TILE_W / QUAD), c = (threadIdx.x % (TILE_W / QUAD)) * QUAD;
+  const int y = ty0 + r, x = tx0 + c;
+  if (y >= Hq || x >= Wq) return;
+  int owner[QUAD];
+  resolve_owners(L, r, c, owner);
+  int vals[QUAD];
+  int cur = -1, my = 0, Wl = 0, valid_w = 0, Ws = 0;
+  const int* labels = arena;
+  MultiRow m;
+#pragma unroll
+  for (int k = 0; k < QUAD; ++k) {
+    int v = 0;
+    if (owner[k] >= 0 && x + k < Wq) {
+      if (owner[k] != cur) {
+        cur = owner[k];
+        m = MultiRow::load(rows, cur);
+        const long long* t = sources + (long)m.src * LabelArena::WORDS;
+        labels = arena + t[0];
+        Wl = (int)t[2]; valid_w = (int)t[4]; Ws = (int)t[6];
+        my = source_cell(y, f, m.dy, m.dh, m.sy, m.sh, (int)t[3], (int)t[5]);
+      }
+      const int mx = source_cell(x + k, f, m.dx, m.dw, m.sx, m.sw, valid_w, Ws);
+      const int other = labels[(long)my * Wl + mx];
+      v = (other != 0 && other != m.local_id) ? 0 : m.global_id;
+    }
+    vals[k] = v;
+  }
+  store_labels(out + ((long)q * Hq + y) * Wq + x, vals, Wq - x, vec_stores);
 }
 
 // ---- affine warps: a slanted region cut out along its own axis (inferencing/orient.py builds the rows) ----------------
@@ -283,7 +439,7 @@ struct WarpRow {
   }
   // as placement_ok: a row outside the bounds is absent.  Within them no intermediate leaves 64 bits (|Y| < 2^40 + 2^36)
   // and a tap outside the source reads 0, so no table content makes a kernel read outside the source.
-  __device__ __forceinline__ bool ok(int, int) const {
+  __device__ __forceinline__ bool ok(const SourceDims&) const {
     const auto m_ok = [](long long m) { return m >= -WARP_M_MAX && m <= WARP_M_MAX; };
     return dh >= 1 && dw >= 1 && dh <= SIDE_MAX && dw <= SIDE_MAX && dy >= 0 && dx >= 0 && dy <= DIM_MAX && dx <= DIM_MAX &&
            ay > -WARP_A_MAX && ay < WARP_A_MAX && ax > -WARP_A_MAX && ax < WARP_A_MAX && m_ok(myy) && m_ok(myx) &&
@@ -338,7 +494,7 @@ __global__ __launch_bounds__(THREADS) void warp_pack_kernel(const unsigned char*
                                                             unsigned char* __restrict__ page, int Hp, int Wp) {
   __shared__ TileLists L;
   const int ty0 = blockIdx.y * TILE_H, tx0 = blockIdx.x * TILE_W;
-  find_tile_rows<WarpRow>(table, n, Hs, Ws, 1, ty0, tx0, L);
+  find_tile_rows<WarpRow>(table, 0, n, SourceDims{Hs, Ws}, 1, ty0, tx0, L);
   const int r = threadIdx.x / (TILE_W / QUAD), c = (threadIdx.x % (TILE_W / QUAD)) * QUAD;
   const int y = ty0 + r, x = tx0 + c;
   if (y >= Hp || x >= Wp) return;
@@ -372,7 +528,7 @@ __global__ __launch_bounds__(THREADS) void warp_labels_kernel(const int* __restr
                                                               int* __restrict__ out, int Hq, int Wq) {
   __shared__ TileLists L;
   const int ty0 = blockIdx.y * TILE_H, tx0 = blockIdx.x * TILE_W;
-  find_tile_rows<WarpRow>(table, n, Hs, Ws, f, ty0, tx0, L);
+  find_tile_rows<WarpRow>(table, 0, n, SourceDims{Hs, Ws}, f, ty0, tx0, L);
   const int r = threadIdx.x / (TILE_W / QUAD), c = (threadIdx.x % (TILE_W / QUAD)) * QUAD;
   const int y = ty0 + r, x = tx0 + c;
   if (y >= Hq || x >= Wq) return;
@@ -434,6 +590,49 @@ extern "C" int vkas_pack_region_labels(const int* labels, int Hl, int Wl, int va
   pack_labels_kernel<<<grid, THREADS, 0, vkas_stream(stream)>>>(labels, Wl, valid_h, valid_w, Hs, Ws, placements,
                                                                 region_ids, n, fdf, out, Hq, Wq, vec_stores);
   VKAS_LAUNCH_CHECK("pack_region_labels");
+  return VKAS_OK;
+}
+
+extern "C" int vkas_resample_pack_u8_multi(const unsigned char* arena, long long arena_bytes, const long long* sources, int S,
+                                           const int* rows, int n, const int* page_start, unsigned char* pages, int Q, int Hp,
+                                           int Wp, void* stream) {
+  VKAS_CHECK(arena && sources && page_start && pages, "vkas_resample_pack_u8_multi: null pointer");
+  VKAS_CHECK(n >= 0 && (n == 0 || rows), "vkas_resample_pack_u8_multi: bad table (n %d)", n);
+  VKAS_CHECK(arena_bytes >= 1 && S >= 1, "vkas_resample_pack_u8_multi: empty arena (%lld bytes, %d sources)", arena_bytes, S);
+  VKAS_CHECK(Q >= 1 && Q <= 65535 && Hp >= 1 && Wp >= 1 && Hp <= DIM_MAX && Wp <= DIM_MAX,
+             "vkas_resample_pack_u8_multi: %d pages of %d x %d: 1..65535 pages, sides 1..%d", Q, Hp, Wp, DIM_MAX);
+  VKAS_CHECK(vkas_aligned16(rows), "vkas_resample_pack_u8_multi: the row table must be 16-byte aligned");
+  VKAS_CHECK((((uintptr_t)sources) & 7u) == 0 && (((uintptr_t)page_start) & 3u) == 0,
+             "vkas_resample_pack_u8_multi: the source table must be 8-byte aligned, page_start 4-byte aligned");
+  // a page starts at a multiple of Hp*Wp*3 bytes: 4-byte aligned whenever Wp % 4 == 0 and the first one is
+  const int dword_stores = (Wp % 4 == 0) && ((((uintptr_t)pages) & 3u) == 0);
+  const dim3 grid((unsigned)vkas_cdiv(Wp, TILE_W), (unsigned)vkas_cdiv(Hp, TILE_H), (unsigned)Q);
+  resample_pack_multi_kernel<<<grid, THREADS, 0, vkas_stream(stream)>>>(arena, arena_bytes, sources, S, rows, n, page_start,
+                                                                        pages, Hp, Wp, dword_stores);
+  VKAS_LAUNCH_CHECK("resample_pack_u8_multi");
+  return VKAS_OK;
+}
+
+extern "C" int vkas_pack_region_labels_multi(const int* label_arena, long long label_words, const long long* label_sources,
+                                             int S, const int* rows, int n, const int* page_start, int fdf, int* out, int Q,
+                                             int Hq, int Wq, void* stream) {
+  VKAS_CHECK(label_arena && label_sources && page_start && out, "vkas_pack_region_labels_multi: null pointer");
+  VKAS_CHECK(n >= 0 && (n == 0 || rows), "vkas_pack_region_labels_multi: bad table (n %d)", n);
+  VKAS_CHECK(label_words >= 1 && S >= 1, "vkas_pack_region_labels_multi: empty arena (%lld words, %d sources)", label_words, S);
+  VKAS_CHECK(fdf >= 1 && fdf <= 64, "vkas_pack_region_labels_multi: bad factor %d", fdf);
+  VKAS_CHECK(Q >= 1 && Q <= 65535 && Hq >= 1 && Wq >= 1 && (long)Hq * fdf <= DIM_MAX && (long)Wq * fdf <= DIM_MAX,
+             "vkas_pack_region_labels_multi: %d label pages of %d x %d at factor %d: 1..65535 pages, page sides up to %d", Q,
+             Hq, Wq, fdf, DIM_MAX);
+  VKAS_CHECK(vkas_aligned16(rows), "vkas_pack_region_labels_multi: the row table must be 16-byte aligned");
+  VKAS_CHECK((((uintptr_t)label_sources) & 7u) == 0 && (((uintptr_t)page_start) & 3u) == 0 &&
+                 (((uintptr_t)label_arena) & 3u) == 0,
+             "vkas_pack_region_labels_multi: the source table must be 8-byte aligned, page_start and the arena 4-byte aligned");
+  // a label page starts at a multiple of Hq*Wq words: 16-byte aligned whenever Wq % 4 == 0 and the first one is
+  const int vec_stores = (Wq % 4 == 0) && vkas_aligned16(out);
+  const dim3 grid((unsigned)vkas_cdiv(Wq, TILE_W), (unsigned)vkas_cdiv(Hq, TILE_H), (unsigned)Q);
+  pack_labels_multi_kernel<<<grid, THREADS, 0, vkas_stream(stream)>>>(label_arena, label_words, label_sources, S, rows, n,
+                                                                      page_start, fdf, out, Hq, Wq, vec_stores);
+  VKAS_LAUNCH_CHECK("pack_region_labels_multi");
   return VKAS_OK;
 }
 

@@ -21,6 +21,9 @@ an elongated, slanted region is cut out along its own axis and turned by the sma
 (inferencing/orient.py, csrc/orient.hip; deskewing only: no perspective, no curved lines, no polygon dilation) -; the
 interpolation rule is this project's own, in integers (inferencing/packing.py); stacking is a shelf packing; and a character
 of a neighbouring region inside an overlapping box is excluded through the rough label map instead of ``flattened_mask``.
+``infer_batch`` does the same for a list of images at once: the rough pass runs on batches of one padded shape, and the
+regions of ALL images are cut in one launch into shared pages of at most 2048 x 1536 (the multi kernels of
+csrc/respack.hip; ``stack_regions_pages``), so N small images cost a few full precise passes instead of N padded ones.
 
 Out of scope: polygons of the rough regions and flattening beyond deskewing (vkit, cv2).  Images are plain (H, W, 3) uint8 arrays instead of ``vkit.element.Image``; results carry
 numpy arrays instead of ``Mask`` / ``ScoreMap`` / ``Polygon``.  The reference loads a TorchScript file (``model_jit``,
@@ -38,7 +41,8 @@ import torch
 from .opt import pad_mat_to_make_divisible
 from .graphs import GraphCache, param_stamp
 from .regions import region_scales
-from .packing import SIDE_MAX, check_warps, region_crops, remap_polygons, remap_polygons_affine, stack_regions
+from .packing import (SIDE_MAX, check_multi_rows, check_warps, region_crops, remap_polygons, remap_polygons_affine,
+                      stack_regions, stack_regions_pages)
 from .orient import orient_regions, region_directions, warp_row
 from .. import ops
 from .._lib import lib, check
@@ -86,6 +90,13 @@ class AdaptiveScalingInferencingConfig:
     # of up to 255 rows of padding for the precise pass.
     precise_page_width_max: int = 2048
     precise_page_height_step: int = 256
+    # Read by infer_batch only (infer stays uncapped): the height of a shared page, the short side of the reference's
+    # 2048 x 1536 page and a multiple of precise_page_height_step - the regions of a batch spill onto further pages of this
+    # height (inferencing/packing.py::stack_regions_pages) -, and the largest batch of one rough graph: a group of images of
+    # one padded rough shape is split into chunks of at most this many, so the graph cache holds one graph per (shape,
+    # chunk size) and not one per arbitrary B.
+    precise_page_height_max: int = 1536
+    rough_batch_max: int = 8
     # Oriented text regions (inferencing/orient.py; the reference's TextRegionFlattener, deskewing only), read by infer: a
     # kept region that is slanted by at least 1 degree, whose oriented rectangle is at least this many times longer than
     # wide (the reference's typical_long_side_ratio_min) and packs smaller than its box, is cut out along its own axis.
@@ -163,6 +174,20 @@ class AdaptiveScalingInferencingResult:
     oriented: np.ndarray = attrs.field(factory=lambda: np.zeros((0,), bool))             # (N,) bool
     warps: np.ndarray = attrs.field(factory=lambda: np.zeros((0, 12), np.int64))         # (K, 12) int64
     warp_regions: np.ndarray = attrs.field(factory=lambda: np.zeros((0,), np.int32))     # (K,) int32, 1-based
+    # infer_batch: the shared page each placement lies on (empty from infer, which has one page).  There ``page_shape`` /
+    # ``page`` / ``region_labels`` are those of the image's first placement's page, which other images share
+    placement_pages: np.ndarray = attrs.field(factory=lambda: np.zeros((0,), np.int32))  # (M,) int32
+
+
+@attrs.define
+class AdaptiveScalingInferencingBatchResult:
+    """``infer_batch``: one result per image, in input order, and the shared pages their regions were packed into."""
+    results: Sequence[AdaptiveScalingInferencingResult]
+    page_shapes: Sequence[Tuple[int, int]]  # per page: all of one width, all but the last of config.precise_page_height_max
+    rows: np.ndarray                        # (M, 12) int32 multi rows (inferencing/packing.py), sorted by page
+    # only on request, per page (none when no region was packed): (Hp, Wp, 3) uint8; (Hp/FDF, Wp/FDF) int32 global region ids
+    pages: Optional[Sequence[np.ndarray]] = None
+    region_labels: Optional[Sequence[np.ndarray]] = None
 
 
 def rough_resized_shape(height: int, width: int, short_side: int) -> Tuple[int, int]:
@@ -302,14 +327,14 @@ class AdaptiveScalingInferencing:
             resized_shape=(math.ceil(h / fdf), math.ceil(w / fdf)), padded_image=padded,
             rough_char_mask=out_mask[0].cpu().numpy(), rough_char_height_score_map=out_height[0].cpu().numpy())
 
-    def _rough_text_regions(self, x, image_shape, h: int, w: int, padded, return_labels: bool, with_moments: bool = False):
-        """The rough-plus-regions graph on a device input and the table rows read back: the result, and the device label
-        map (a static output of the graph: consume it before the next graph of this cache runs).  ``with_moments``: the
-        graph - one of its own key - also takes the regions' moments (csrc/orient.hip); their rows come third."""
+    def _rough_regions_graph(self, x, sizes: Sequence[Tuple[int, int]], with_moments: bool = False):
+        """The rough-plus-regions graph on a device input (B, 3, Hp, Wp) whose images are valid on ``sizes``: the device
+        tensors ``ops.text_regions`` returns (static outputs of the graph: consume them before the next graph of this cache
+        runs).  ``with_moments``: the graph - one of its own key - also takes the regions' moments (csrc/orient.hip)."""
         c = self.config
         fdf = 4 // c.rough_head_upsampling_factor
         H, W = x.shape[2] // fdf, x.shape[3] // fdf
-        vh, vw = self._valid([(h, w)], fdf, x.device)
+        vh, vw = self._valid(sizes, fdf, x.device)
         thr, hmin = float(c.rough_char_mask_positive_thr), float(c.rough_valid_char_height_min)
         cap = int(c.rough_text_regions_max)
 
@@ -320,28 +345,37 @@ class AdaptiveScalingInferencing:
             out = rough_regions_pass(x, vh, vw)
             return out + (ops.region_moments(out[1], cap),)
 
-        moments = None
         with torch.no_grad():
             if with_moments:
-                count, labels, boxes, areas, valid, medians, moments = self.graphs.run(
-                    ('rough_text_regions_moments', thr, hmin, cap), rough_regions_moments_pass, [x, vh, vw],
-                    param_stamp(self.model))
-            else:
-                count, labels, boxes, areas, valid, medians = self.graphs.run(
-                    ('rough_text_regions', thr, hmin, cap), rough_regions_pass, [x, vh, vw], param_stamp(self.model))
-        num = int(count[0].item())
-        n = min(num, cap)
-        if with_moments:
-            moments = moments[0, :n].cpu().numpy()
-        boxes, areas, valid, medians = (t[0, :n].cpu().numpy() for t in (boxes, areas, valid, medians))
+                return self.graphs.run(('rough_text_regions_moments', thr, hmin, cap), rough_regions_moments_pass, [x, vh, vw],
+                                       param_stamp(self.model))
+            return self.graphs.run(('rough_text_regions', thr, hmin, cap), rough_regions_pass, [x, vh, vw],
+                                   param_stamp(self.model))
+
+    def _rough_regions_result(self, image_shape, h: int, w: int, padded, num: int, labels, boxes, areas, valid, medians):
+        """The region table of one image from its rows as read back, with the reference's scale rule on the host."""
+        c = self.config
+        fdf = 4 // c.rough_head_upsampling_factor
         resized_shape = (math.ceil(h / fdf), math.ceil(w / fdf))
         scales, resized_shapes, keep = region_scales(
             boxes, medians, image_shape, resized_shape, c.precise_flattened_text_region_resized_char_height_median,
             c.precise_flattened_text_region_resized_ratio_min)
         return AdaptiveScalingInferencingRoughTextRegions(
-            resized_shape=resized_shape, padded_image=padded, num_regions=num,
-            labels=labels[0].cpu().numpy() if return_labels else None, boxes=boxes, areas=areas, valid=valid,
-            char_height_medians=medians, scales=scales, resized_shapes=resized_shapes, keep=keep), labels[0], moments
+            resized_shape=resized_shape, padded_image=padded, num_regions=num, labels=labels, boxes=boxes, areas=areas,
+            valid=valid, char_height_medians=medians, scales=scales, resized_shapes=resized_shapes, keep=keep)
+
+    def _rough_text_regions(self, x, image_shape, h: int, w: int, padded, return_labels: bool, with_moments: bool = False):
+        """The rough-plus-regions graph on a device input and the table rows read back: the result, and the device label
+        map (a static output of the graph: consume it before the next graph of this cache runs).  ``with_moments``: the
+        regions' moments come third."""
+        out = self._rough_regions_graph(x, [(h, w)], with_moments)
+        count, labels, boxes, areas, valid, medians = out[:6]
+        num = int(count[0].item())
+        n = min(num, int(self.config.rough_text_regions_max))
+        moments = out[6][0, :n].cpu().numpy() if with_moments else None
+        boxes, areas, valid, medians = (t[0, :n].cpu().numpy() for t in (boxes, areas, valid, medians))
+        return self._rough_regions_result(image_shape, h, w, padded, num, labels[0].cpu().numpy() if return_labels else None,
+                                          boxes, areas, valid, medians), labels[0], moments
 
     def rough_infer_text_regions(self, image, resize_fn=None,
                                  return_labels: bool = True) -> AdaptiveScalingInferencingRoughTextRegions:
@@ -352,6 +386,98 @@ class AdaptiveScalingInferencing:
         labels: the result equals ``text_regions_host`` + ``region_scales`` on them."""
         mat, (h, w), padded, x = self._rough_input(image, resize_fn)
         return self._rough_text_regions(x, mat.shape[:2], h, w, padded, return_labels)[0]
+
+    # ---- a batch of images: one arena, rough graphs per padded shape --------------------------------------------------
+    def _image_arena(self, images: Sequence):
+        """The uint8 images of a batch in ONE device byte arena: copied once into one pinned host buffer, every image start
+        16-byte aligned, and uploaded in one transfer.  -> the mats, the arena, and its (S, 4) int64 source table (byte
+        offset, Hs, Ws, 0) on the host and on the device."""
+        mats = [_as_mat(im) for im in images]
+        table = np.zeros((len(mats), 4), np.int64)
+        total = 0
+        for i, m in enumerate(mats):
+            if m.dtype != np.uint8:
+                raise ValueError(f'image {i}: a batch takes uint8 images, got {m.dtype}')
+            if min(m.shape[:2]) < 1 or max(m.shape[:2]) > SIDE_MAX:
+                raise ValueError(f'image {i} {m.shape[:2]}: the device resampler takes sides from 1 to {SIDE_MAX}')
+            table[i] = (total, m.shape[0], m.shape[1], 0)
+            total += -(-m.size // 16) * 16
+        host = torch.empty((total,), dtype=torch.uint8, pin_memory=True)
+        flat = host.numpy()
+        for m, (offset, _, _, _) in zip(mats, table.tolist()):
+            flat[offset:offset + m.size] = m.reshape(-1)
+        device = self.config.device
+        return mats, host.to(device, non_blocking=True), table, torch.from_numpy(table).to(device, non_blocking=True)
+
+    def _multi_tables(self, rows: np.ndarray, source_shapes, page_shape, num_pages: int):
+        """A multi-row table checked on the host (so the launches need no copy back) and uploaded with its page_start."""
+        rows = check_multi_rows(rows, source_shapes, page_shape, num_pages)
+        start = np.searchsorted(rows[:, 1], np.arange(num_pages + 1)).astype(np.int32)
+        device = self.config.device
+        return torch.from_numpy(rows).to(device, non_blocking=True), torch.from_numpy(start).to(device, non_blocking=True)
+
+    def _rough_text_regions_batch(self, mats, arena, sources, d_sources, return_padded: bool, return_labels: bool,
+                                  keep_labels: bool):
+        """The rough pass of a batch: images grouped by padded rough shape, a group split into chunks of at most
+        ``config.rough_batch_max``; per chunk ONE launch shrinks (the 720 rule) and pads its images out of the arena into a
+        (B, Hp, Wp, 3) batch - one multi row per image, source i -> page k - and one ``graphs.run`` of the rough-plus-regions
+        pass follows.  -> the region tables in input order and, ``keep_labels``, the int32 device arena of the rough label
+        maps with its (S, 8) int64 source table (word offset, Hl, Wl, valid_h, valid_w, Hs, Ws, 0): the label tensor of a graph
+        is a static output that the next replay overwrites, so each chunk's labels are copied there, device to device."""
+        c = self.config
+        f, fdf, cap = c.backbone_downsampling_factor, 4 // c.rough_head_upsampling_factor, int(c.rough_text_regions_max)
+        step = int(c.rough_batch_max)
+        if step < 1:
+            raise ValueError(f'rough_batch_max must be at least 1, got {c.rough_batch_max}')
+        shapes = [(int(m.shape[0]), int(m.shape[1])) for m in mats]
+        sizes = [rough_resized_shape(H, W, c.rough_downsample_short_side_legnth) for H, W in shapes]
+        groups = {}
+        for i, (h, w) in enumerate(sizes):
+            groups.setdefault((-(-h // f) * f, -(-w // f) * f), []).append(i)
+        chunks = [(shape, idxs[k:k + step]) for shape, idxs in groups.items() for k in range(0, len(idxs), step)]
+        label_sources = np.zeros((len(mats), 8), np.int64)
+        words = 0
+        for (Hp, Wp), idxs in chunks:  # the maps of a chunk lie side by side: one copy per chunk
+            for i in idxs:
+                label_sources[i] = (words, Hp // fdf, Wp // fdf, math.ceil(sizes[i][0] / fdf), math.ceil(sizes[i][1] / fdf),
+                                    shapes[i][0], shapes[i][1], 0)
+                words += (Hp // fdf) * (Wp // fdf)
+        label_arena = torch.empty((words,), dtype=torch.int32, device=arena.device) if keep_labels else None
+        results = [None] * len(mats)
+        for (Hp, Wp), idxs in chunks:
+            B = len(idxs)
+            rows = np.array([[i, k, 0, 0, shapes[i][0], shapes[i][1], 0, 0, sizes[i][0], sizes[i][1], 1, 1]
+                             for k, i in enumerate(idxs)], np.int32)
+            d_rows, d_start = self._multi_tables(rows, shapes, (Hp, Wp), B)
+            pages = ops.resample_pack_u8_multi(arena, d_sources, d_rows, B, (Hp, Wp), page_start=d_start, validate=False)
+            count, labels, boxes, areas, valid, medians = self._rough_regions_graph(
+                pages.permute(0, 3, 1, 2).float(), [sizes[i] for i in idxs])
+            if keep_labels:
+                first = int(label_sources[idxs[0], 0])
+                label_arena[first:first + labels.numel()].view(labels.shape).copy_(labels)
+            nums = count.cpu().numpy()
+            most = min(int(nums.max()), cap)
+            boxes, areas, valid, medians = (t[:, :most].cpu().numpy() for t in (boxes, areas, valid, medians))
+            labels = labels.cpu().numpy() if return_labels else None
+            pages = pages.cpu().numpy() if return_padded else None
+            for k, i in enumerate(idxs):
+                n = min(int(nums[k]), cap)
+                results[i] = self._rough_regions_result(
+                    shapes[i], sizes[i][0], sizes[i][1], pages[k] if return_padded else None, int(nums[k]),
+                    labels[k] if return_labels else None,
+                    *(np.ascontiguousarray(t[k, :n]) for t in (boxes, areas, valid, medians)))
+        return results, label_arena, label_sources
+
+    def rough_infer_text_regions_batch(self, images: Sequence,
+                                       return_labels: bool = True) -> Sequence[AdaptiveScalingInferencingRoughTextRegions]:
+        """``rough_infer_text_regions(image, resize_fn='device')`` for a list of uint8 (H, W, 3) images, in input order: the
+        images go up in one transfer, the 720 rule's shrink and the padding run on the device (one launch per chunk), and
+        images of one padded rough shape share a model call, at most ``config.rough_batch_max`` at a time.  A chunk of one
+        image runs the very graph ``infer`` and ``rough_infer_text_regions`` run: its result equals theirs bit for bit."""
+        if not len(images):
+            return []
+        mats, arena, sources, d_sources = self._image_arena(images)
+        return self._rough_text_regions_batch(mats, arena, sources, d_sources, True, return_labels, False)[0]
 
     # ---- precise pass --------------------------------------------------------------------------------------------
     def _precise_groups(self, images: Sequence):
@@ -544,6 +670,110 @@ class AdaptiveScalingInferencing:
         if orient:
             result.oriented, result.warps, result.warp_regions = oriented, warps, warp_ids
         return result
+
+    def infer_batch(self, images: Sequence, return_pages: bool = False,
+                    return_labels: bool = False) -> AdaptiveScalingInferencingBatchResult:
+        """``infer`` for a list of uint8 (H, W, 3) images whose text regions share the pages of the precise pass: N small
+        images cost a few full precise passes instead of N padded ones.  The images are copied into one pinned buffer and go
+        up in one transfer (``_image_arena``); the rough pass runs per chunk of one padded rough shape
+        (``_rough_text_regions_batch``); scales and crops are host arithmetic per image; ONE ``stack_regions_pages`` over the
+        kept regions of all images, in input order, fills pages of at most ``precise_page_width_max`` x
+        ``precise_page_height_max`` - a region's global id is 1 + its position in that concatenation -; the multi rows go
+        up, one launch cuts every region out of the arena into the full-height pages and one writes their label pages
+        (csrc/respack.hip), and once more for the last page if its height differs; the precise-plus-char-polygons graph
+        runs on the page batch, and again on the last page; one label per character is gathered on the device; the
+        characters are split by global id, then image, and mapped back through ``remap_polygons``.
+
+        Host round trips per batch: three uploads (arena, image table, label table); per rough chunk two small uploads
+        (rows, page_start) and five read-backs (counts, then four table slices); per page group - at most two - two small
+        uploads and five read-backs (count, labels under the points, points, probabilities, quadrilaterals).  Images,
+        maps and pages do not cross back over PCIe unless ``return_pages`` / ``return_labels`` ask for them.
+
+        ``infer_batch([image]).results[0]`` equals ``infer(image)`` bit for bit whenever the regions fit one page of
+        ``precise_page_height_max`` rows.  Oriented regions (``config.precise_text_region_orient``) on shared pages are not
+        built yet: with the flag set this raises ValueError."""
+        c = self.config
+        if c.precise_text_region_orient:
+            raise ValueError('infer_batch does not take oriented text regions yet: unset precise_text_region_orient or use infer')
+        if not len(images):
+            return AdaptiveScalingInferencingBatchResult(results=[], page_shapes=[], rows=np.zeros((0, 12), np.int32),
+                                                         pages=[] if return_pages else None,
+                                                         region_labels=[] if return_labels else None)
+        mats, arena, sources, d_sources = self._image_arena(images)
+        all_regions, label_arena, label_sources = self._rough_text_regions_batch(mats, arena, sources, d_sources, return_pages,
+                                                                                 return_labels, True)
+        shapes = [(int(m.shape[0]), int(m.shape[1])) for m in mats]
+        counts = np.array([len(r.boxes) for r in all_regions], np.int64)
+        first = np.concatenate([[0], np.cumsum(counts)])
+        image_of = np.repeat(np.arange(len(mats)), counts)
+        crops = np.concatenate([region_crops(r.boxes, shape, r.resized_shape) for r, shape in zip(all_regions, shapes)])
+        source_fits = (crops[:, 2:] <= SIDE_MAX).all(axis=1)
+        keep = np.concatenate([r.keep for r in all_regions])
+        page_shapes, boxes, page_of, packed, too_large = stack_regions_pages(
+            np.concatenate([r.resized_shapes for r in all_regions]), c.precise_stack_flattened_text_regions_page_pad,
+            c.precise_stack_flattened_text_regions_pad, c.precise_page_width_max, c.precise_page_height_step,
+            c.precise_page_height_max, keep=keep & source_fits)
+        too_large |= keep & ~source_fits
+        g = np.flatnonzero(packed)  # global region id - 1, ascending: image after image, region after region
+        by_region = np.concatenate([image_of[g, None], page_of[g, None], crops[g], boxes[g], (g - first[image_of[g]])[:, None] + 1,
+                                    g[:, None] + 1], axis=1).astype(np.int32)
+        rows = np.ascontiguousarray(by_region[np.argsort(by_region[:, 1], kind='stable')])
+        Q = len(page_shapes)
+        fdf = 4 // c.precise_head_upsampling_factor
+        d_label_sources = torch.from_numpy(label_sources).to(c.device, non_blocking=True)
+        # the pages of full height are one batch of the precise graph; the last page joins them only if it is as high
+        if Q == 1 or page_shapes[-1] == page_shapes[0]:
+            groups = [(0, Q)]
+        else:
+            groups = [(0, Q - 1), (Q - 1, Q)]
+        at, all_points, all_probs, all_quads, pages, region_labels = [], [], [], [], [], []
+        for q0, q1 in groups if len(rows) else []:
+            shape = page_shapes[q0]
+            sub = rows[(rows[:, 1] >= q0) & (rows[:, 1] < q1)] - np.array([0, q0] + [0] * 10, np.int32)
+            d_rows, d_start = self._multi_tables(sub, shapes, shape, q1 - q0)
+            d_pages = ops.resample_pack_u8_multi(arena, d_sources, d_rows, q1 - q0, shape, page_start=d_start, validate=False)
+            d_region_labels = ops.pack_region_labels_multi(label_arena, d_label_sources, d_rows, q1 - q0,
+                                                           (shape[0] // fdf, shape[1] // fdf), fdf, page_start=d_start,
+                                                           validate=False)
+            d_points, d_probs, d_quads = self._char_polygons(d_pages.permute(0, 3, 1, 2).float(), [shape] * (q1 - q0),
+                                                             on_device=True)
+            # static outputs of the graph: on the host before the graph of the last page runs
+            at.append(d_region_labels[d_points[:, 0].long(), d_points[:, 1].long(), d_points[:, 2].long()].cpu().numpy())
+            for store, t in ((all_points, d_points[:, 1:]), (all_probs, d_probs), (all_quads, d_quads)):
+                store.append(t.cpu().numpy())
+            if return_pages:
+                pages.extend(d_pages.cpu().numpy())
+            if return_labels:
+                region_labels.extend(d_region_labels.cpu().numpy())
+        if len(rows):
+            at, all_points, all_probs, all_quads = (np.concatenate(t) for t in (at, all_points, all_probs, all_quads))
+            order = np.argsort(at, kind='stable')  # the characters of a region stay in np.nonzero order
+            lo = np.searchsorted(at[order], by_region[:, 11], side='left')
+            hi = np.searchsorted(at[order], by_region[:, 11], side='right')
+        results = []
+        for i, regions in enumerate(all_regions):
+            n = int(counts[i])
+            mine = np.flatnonzero(by_region[:, 0] == i)
+            points = [np.zeros((0, 2), np.int32) for _ in range(n)]
+            probs = [np.zeros((0,), np.float32) for _ in range(n)]
+            polygons = [np.zeros((0, 4, 2), np.float64) for _ in range(n)]
+            for k in mine.tolist():
+                sel, r = order[lo[k]:hi[k]], int(by_region[k, 10]) - 1
+                points[r] = np.ascontiguousarray(all_points[sel])
+                probs[r] = all_probs[sel]
+                polygons[r] = remap_polygons(all_quads[sel], by_region[k, 2:10])
+            placement_pages = np.ascontiguousarray(by_region[mine, 1])
+            page = int(placement_pages[0]) if len(mine) else 0
+            results.append(AdaptiveScalingInferencingResult(
+                image_shape=shapes[i], regions=regions, packed=packed[first[i]:first[i + 1]],
+                too_large=too_large[first[i]:first[i + 1]], placements=np.ascontiguousarray(by_region[mine, 2:10]),
+                placement_regions=np.ascontiguousarray(by_region[mine, 10]), page_shape=page_shapes[page],
+                page=pages[page] if return_pages and len(mine) else None,
+                region_labels=region_labels[page] if return_labels and len(mine) else None, points=points, probs=probs,
+                polygons=polygons, placement_pages=placement_pages))
+        return AdaptiveScalingInferencingBatchResult(
+            results=results, page_shapes=page_shapes, rows=rows, pages=pages if return_pages else None,
+            region_labels=region_labels if return_labels else None)
 
     @staticmethod
     def precise_group_char_polygons(result: AdaptiveScalingInferencingPreciseCharPolygons,

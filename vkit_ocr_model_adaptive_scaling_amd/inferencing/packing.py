@@ -157,6 +157,81 @@ def pack_region_labels_host(labels: np.ndarray, valid_shape: Tuple[int, int], im
     return out
 
 
+# ---- several sources, several pages (infer_batch; the multi kernels of csrc/respack.hip) ---------------------------------
+# A **multi row** is ``(src, page, sy, sx, sh, sw, dy, dx, dh, dw, local_id, global_id)`` of int32: the placement in columns
+# 2..9 reads source image ``src`` and writes page ``page``; ``local_id`` is the region's label in that image's rough label
+# map, ``global_id`` the label it gets on the label page.  Rows are sorted by page; destinations are disjoint per page.
+def check_multi_rows(rows, source_shapes, page_shape: Tuple[int, int], num_pages: int) -> np.ndarray:
+    """Validates an (n, 12) multi-row table against the (S, 2) source shapes (Hs, Ws) and ``num_pages`` pages of
+    ``page_shape`` - integer rows sorted by page, ``src`` and ``page`` in range, ids at least 1, sides in [1, SIDE_MAX],
+    rectangles inside their source / page, destinations pairwise disjoint per page - and returns it as contiguous int32.
+    Raises ValueError."""
+    r = np.asarray(rows)
+    if r.ndim != 2 or r.shape[1] != 12 or not np.issubdtype(r.dtype, np.integer):
+        raise ValueError(f'multi rows must be an (n, 12) integer table, got {r.dtype} {r.shape}')
+    shapes = np.asarray(source_shapes, dtype=np.int64).reshape(-1, 2)
+    S, Q = len(shapes), int(num_pages)
+    Hp, Wp = (int(v) for v in page_shape)
+    q = r.astype(np.int64)
+    src, page, sy, sx, sh, sw, dy, dx, dh, dw = q[:, :10].T
+    if ((src < 0) | (src >= S)).any():
+        raise ValueError(f'multi rows: a source index is outside [0, {S})')
+    if ((page < 0) | (page >= Q)).any():
+        raise ValueError(f'multi rows: a page index is outside [0, {Q})')
+    if (np.diff(page) < 0).any():
+        raise ValueError('multi rows: the rows must be sorted by page')
+    if (q[:, 10:] < 1).any():
+        raise ValueError('multi rows: region ids start at 1 (0 is "no region")')
+    sides = q[:, [4, 5, 8, 9]]
+    if ((sides < 1) | (sides > SIDE_MAX)).any():
+        raise ValueError(f'multi rows: every side must be in [1, {SIDE_MAX}]')
+    if ((sy < 0) | (sx < 0) | (sy + sh > shapes[src, 0]) | (sx + sw > shapes[src, 1])).any():
+        raise ValueError('multi rows: a source rectangle leaves its source')
+    if ((dy < 0) | (dx < 0) | (dy + dh > Hp) | (dx + dw > Wp)).any():
+        raise ValueError(f'multi rows: a destination rectangle leaves the {(Hp, Wp)} page')
+    order = np.lexsort((dy, page))  # the sweep of check_placements, page after page
+    live = []
+    for k in order:
+        live = [j for j in live if page[j] == page[k] and dy[j] + dh[j] > dy[k]]
+        for j in live:
+            if dx[j] < dx[k] + dw[k] and dx[k] < dx[j] + dw[j]:
+                raise ValueError(f'multi rows: destinations {int(min(j, k))} and {int(max(j, k))} overlap on page {int(page[k])}')
+        live.append(k)
+    return np.ascontiguousarray(r.astype(np.int32))
+
+
+def resample_pack_multi_host(sources: Sequence[np.ndarray], rows, page_shape: Tuple[int, int], num_pages: int) -> np.ndarray:
+    """The definition of the multi pack: (Hs, Ws, 3) uint8 images and an (n, 12) multi-row table -> the (Q, Hp, Wp, 3) uint8
+    pages; ``resample_host`` per (source, page).  Plain and slow."""
+    table = check_multi_rows(rows, [np.asarray(s).shape[:2] for s in sources], page_shape, num_pages)
+    Hp, Wp = (int(v) for v in page_shape)
+    pages = np.zeros((int(num_pages), Hp, Wp, 3), np.uint8)
+    for s, src in enumerate(sources):
+        for page in range(int(num_pages)):
+            sel = (table[:, 0] == s) & (table[:, 1] == page)
+            if sel.any():  # destinations are disjoint and a page is zero outside them: the pages of the sources add up
+                pages[page] += resample_host(src, table[sel][:, 2:10], (Hp, Wp))
+    return pages
+
+
+def pack_region_labels_multi_host(label_maps: Sequence[np.ndarray], valid_shapes, image_shapes, rows,
+                                  out_shape: Tuple[int, int], fdf: int, num_pages: int) -> np.ndarray:
+    """The label pages of the multi pack, (Q, Hq, Wq) int32: ``pack_region_labels_host`` per (source, page) with the
+    rows' ``local_id`` - the ids of that image's rough label map ``label_maps[src]`` -, then every cell it kept gets the
+    row's ``global_id``: the regions of two images may share a local id, never a global one."""
+    Hq, Wq = (int(v) for v in out_shape)
+    fdf, Q = int(fdf), int(num_pages)
+    table = check_multi_rows(rows, np.asarray(image_shapes).reshape(-1, 2), (Hq * fdf, Wq * fdf), Q)
+    out = np.zeros((Q, Hq, Wq), np.int32)
+    for s, labels in enumerate(label_maps):
+        for page in range(Q):
+            for row in table[(table[:, 0] == s) & (table[:, 1] == page)]:  # a row at a time: local ids may repeat
+                kept = pack_region_labels_host(labels, valid_shapes[s], image_shapes[s], row[None, 2:10], row[10:11],
+                                               (Hq, Wq), fdf)
+                out[page][kept != 0] = row[11]
+    return out
+
+
 def region_crops(boxes, image_shape: Tuple[int, int], resized_shape: Tuple[int, int]) -> np.ndarray:
     """Inclusive map-pixel boxes (N, 4) (y0, x0, y1, x1) -> (N, 4) int64 image rectangles (sy, sx, sh, sw): map row m covers
     the image rows ``[m*H/rs_h, (m+1)*H/rs_h)``, so ``Y0 = floor(y0*H/rs_h)`` and ``Y1 = min(H, ceil((y1+1)*H/rs_h))``;
@@ -212,6 +287,55 @@ def stack_regions(shapes, page_pad: int, pad: int, width_max: int, height_step: 
     width = min(width_max, -(-(right + page_pad) // 32) * 32)
     height = -(-(y + row_h + page_pad) // height_step) * height_step
     return (int(height), int(width)), boxes, fits, too_large
+
+
+def stack_regions_pages(shapes, page_pad: int, pad: int, width_max: int, height_step: int, height_max: int,
+                        keep: Optional[Sequence[bool]] = None, side_max: int = SIDE_MAX):
+    """``stack_regions`` onto pages of bounded height (``infer_batch``: the regions of many images share pages).  Same
+    order and shelf rule; a new row that would end below ``height_max - page_pad`` (a multiple of ``height_step``) opens the
+    next page at ``y = page_pad``.  All pages share one width - the smallest multiple of 32 that holds the widest row of
+    any page, at most ``width_max`` -; pages ``0 .. Q-2`` are ``height_max`` high, the last one has its own height, rounded
+    up to ``height_step``.
+
+    Returns ``(page_shapes, boxes, pages, packed, too_large)``: a list of Q >= 1 (Hp, Wp); (N, 4) int64 (dy, dx, dh, dw)
+    inside the region's page; (N,) int32 page index, -1 for a region that is not packed; (N,) bool; (N,) bool - as
+    ``stack_regions``, and also a kept region taller than ``height_max - 2*page_pad``: reported, never clamped.  Whenever
+    everything fits one page of ``height_max`` the result is ``stack_regions``' on the same arguments, with ``pages == 0``."""
+    shapes = np.asarray(shapes, dtype=np.int64).reshape(-1, 2)
+    n = len(shapes)
+    keep = np.ones((n,), bool) if keep is None else np.asarray(keep, dtype=bool).reshape(-1)
+    if len(keep) != n:
+        raise ValueError(f'{len(keep)} keep flags for {n} shapes')
+    page_pad, pad, width_max, height_step, height_max = (int(v) for v in (page_pad, pad, width_max, height_step, height_max))
+    if page_pad < 0 or pad < 0:
+        raise ValueError(f'pads must not be negative, got page_pad {page_pad}, pad {pad}')
+    if width_max < 32 or width_max % 32 or height_step < 32 or height_step % 32:
+        raise ValueError(f'width_max and height_step must be positive multiples of 32, got {width_max} and {height_step}')
+    if height_max < height_step or height_max % height_step:
+        raise ValueError(f'height_max must be a positive multiple of height_step {height_step}, got {height_max}')
+    if width_max - 2 * page_pad < 1 or height_max - 2 * page_pad < 1:
+        raise ValueError(f'a {height_max} x {width_max} page leaves no room between two page_pads of {page_pad}')
+    h, w = shapes[:, 0], shapes[:, 1]
+    too_large = keep & ((w > width_max - 2 * page_pad) | (h > height_max - 2 * page_pad) | (h > side_max) | (w > side_max))
+    fits = keep & ~too_large & (h >= 1) & (w >= 1)
+    order = [r for r in np.argsort(-h, kind='stable').tolist() if fits[r]]
+    boxes = np.zeros((n, 4), np.int64)
+    pages = np.full((n,), -1, np.int32)
+    x, y, row_h, right, q = page_pad, page_pad, 0, page_pad, 0
+    for r in order:
+        if x > page_pad and x + w[r] > width_max - page_pad:  # the row is full: the next one starts below its tallest
+            y += row_h + pad
+            x, row_h = page_pad, 0
+            if y + h[r] > height_max - page_pad:  # heights decrease: the first region of a row is its tallest
+                q, y = q + 1, page_pad
+        boxes[r] = (y, x, h[r], w[r])
+        pages[r] = q
+        right = max(right, x + int(w[r]))
+        row_h = max(row_h, int(h[r]))
+        x += int(w[r]) + pad
+    width = min(width_max, -(-(right + page_pad) // 32) * 32)
+    height = -(-(y + row_h + page_pad) // height_step) * height_step
+    return [(height_max, int(width))] * q + [(int(height), int(width))], boxes, pages, fits, too_large
 
 
 def remap_polygons(polygons, placement) -> np.ndarray:

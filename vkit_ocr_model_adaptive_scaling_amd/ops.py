@@ -2458,6 +2458,144 @@ def pack_region_labels(labels: torch.Tensor, valid_shape: Tuple[int, int], image
     return out
 
 
+def _multi_tables(who: str, sources, words: int, arena_size: int, rows, page_start, num_pages: int, page_shape, device,
+                  validate: bool):
+    """The three tables of a multi pack on ``device``: the (S, ``words``) int64 source table, the (n, 12) int32 rows and the
+    (Q + 1,) int32 ``page_start`` (None: taken from the rows' page column).  Host tables (numpy arrays or CPU tensors) are
+    always validated - every source entry inside the arena of ``arena_size`` elements, the rows by inferencing/packing.py::
+    check_multi_rows, ``page_start`` against the rows - and uploaded; device tables are copied to the host for the same
+    checks when ``validate`` - a synchronisation -, else trusted: the kernels skip a row that is out of range, but
+    overlapping destinations give an unspecified winner."""
+    import numpy as np
+    from .inferencing.packing import check_multi_rows
+    Q = int(num_pages)
+    if Q != num_pages or not 1 <= Q <= 65535:
+        raise ValueError(f'{who}: num_pages must be an integer in [1, 65535], got {num_pages}')
+
+    def host(t, name, shape, dtype):  # -> (the table on the host, or None for a trusted device table; is it on the device)
+        on_device = isinstance(t, torch.Tensor) and t.is_cuda
+        if on_device and t.device != device:
+            raise ValueError(f'{who}: {name} is on {t.device}, the arena on {device}')
+        if on_device:
+            a = t.detach().cpu().numpy() if validate else None
+        else:
+            a = t.numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        ref = t if a is None else a
+        if len(ref.shape) != len(shape) or any(w is not None and v != w for v, w in zip(ref.shape, shape)):
+            raise ValueError(f'{who}: {name} must be {shape}, got {tuple(ref.shape)}')
+        if str(ref.dtype).replace('torch.', '') != dtype:
+            raise ValueError(f'{who}: {name} must be {dtype}, got {ref.dtype}')
+        return a, on_device
+
+    h_sources, sources_on_device = host(sources, 'sources', (None, words), 'int64')
+    h_rows, rows_on_device = host(rows, 'rows', (None, 12), 'int32')
+    S = int((sources if h_sources is None else h_sources).shape[0])
+    n = int((rows if h_rows is None else h_rows).shape[0])
+    if S < 1:
+        raise ValueError(f'{who}: no sources')
+    if h_sources is not None:
+        t = h_sources
+        if words == 4:  # (byte offset, Hs, Ws, 0): an (Hs, Ws, 3) uint8 image
+            sides, need, shapes = t[:, 1:3], 3 * t[:, 1] * t[:, 2], t[:, 1:3]
+        else:           # (word offset, Hl, Wl, valid_h, valid_w, Hs, Ws, 0): an (Hl, Wl) int32 map of an (Hs, Ws) image
+            sides, need, shapes = t[:, [1, 2, 5, 6]], t[:, 1] * t[:, 2], t[:, 5:7]
+            if ((t[:, 3] < 1) | (t[:, 3] > t[:, 1]) | (t[:, 4] < 1) | (t[:, 4] > t[:, 2])).any():
+                raise ValueError(f'{who}: a valid part does not fit its label map')
+        if ((sides < 1) | (sides > _PACK_DIM_MAX)).any():
+            raise ValueError(f'{who}: source sides must be in [1, {_PACK_DIM_MAX}]')
+        if ((t[:, 0] < 0) | (t[:, 0] + need > arena_size)).any():
+            raise ValueError(f'{who}: a source leaves the arena of {arena_size} elements')
+        if h_rows is not None:
+            h_rows = check_multi_rows(h_rows, shapes, page_shape, Q)
+    elif h_rows is not None:
+        raise ValueError(f'{who}: host rows need a host source table (or validate=True) to be checked against')
+    if page_start is None:
+        if h_rows is None:
+            raise ValueError(f'{who}: page_start is needed with a device row table and validate=False')
+        page_start = np.searchsorted(h_rows[:, 1], np.arange(Q + 1)).astype(np.int32)
+    h_start, start_on_device = host(page_start, 'page_start', (Q + 1,), 'int32')
+    if h_start is not None:
+        if h_rows is not None:
+            if not np.array_equal(h_start, np.searchsorted(h_rows[:, 1], np.arange(Q + 1))):
+                raise ValueError(f'{who}: page_start does not give each page its rows')
+        elif h_start[0] < 0 or h_start[-1] > n or (np.diff(h_start) < 0).any():
+            raise ValueError(f'{who}: page_start must rise from 0 to at most {n}')
+
+    def up(t, a, on_device):
+        if on_device:
+            return t.contiguous()
+        return torch.from_numpy(np.ascontiguousarray(a)).to(device, non_blocking=True)
+
+    return (up(sources, h_sources, sources_on_device), up(rows, h_rows, rows_on_device),
+            up(page_start, h_start, start_on_device), S, n, Q)
+
+
+def resample_pack_u8_multi(arena: torch.Tensor, sources, rows, num_pages: int, page_shape: Tuple[int, int], page_start=None,
+                           validate: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Crops, rescales and packs rectangles of several images into several pages in one launch (``infer_batch``;
+    csrc/respack.hip).  ``arena``: a 1-D uint8 device tensor that holds the images; ``sources`` (S,4) int64 rows (byte
+    offset, Hs, Ws, 0); ``rows`` (n,12) int32 multi rows (src, page, sy, sx, sh, sw, dy, dx, dh, dw, local_id, global_id)
+    sorted by page; ``page_start`` (Q+1,) int32, computed from host rows when None - all three host or device (see
+    ``_multi_tables``).  Returns the (Q,Hp,Wp,3) uint8 pages (``out`` if given), equal to
+    inferencing/packing.py::resample_pack_multi_host byte for byte: every byte is written, zero where no row reaches.  With
+    device tables and ``validate=False`` it never synchronises, so it can be captured into a HIP graph."""
+    if arena.dim() != 1 or arena.dtype != torch.uint8:
+        raise ValueError(f'resample_pack_u8_multi: arena must be a 1-D uint8 tensor, got {arena.dtype} {tuple(arena.shape)}')
+    try:
+        Hp, Wp = (int(v) for v in page_shape)
+    except (TypeError, ValueError):
+        raise ValueError(f'resample_pack_u8_multi: page_shape must be (height, width), got {page_shape!r}') from None
+    if arena.numel() < 1 or Hp < 1 or Wp < 1 or max(Hp, Wp) > _PACK_DIM_MAX:
+        raise ValueError(f'resample_pack_u8_multi: empty arena, or page {(Hp, Wp)} sides outside [1, {_PACK_DIM_MAX}]')
+    if not arena.is_contiguous():
+        raise ValueError('resample_pack_u8_multi: arena must be contiguous')
+    d_sources, d_rows, d_start, S, n, Q = _multi_tables('resample_pack_u8_multi', sources, 4, int(arena.numel()), rows,
+                                                        page_start, num_pages, (Hp, Wp), arena.device, validate)
+    if out is not None and (tuple(out.shape) != (Q, Hp, Wp, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or
+                            out.device != arena.device):
+        raise ValueError(f'resample_pack_u8_multi: out must be a contiguous {(Q, Hp, Wp, 3)} uint8 tensor on {arena.device}')
+    _require_cuda(arena, out)
+    pages = out if out is not None else torch.empty((Q, Hp, Wp, 3), dtype=torch.uint8, device=arena.device)
+    check(lib.vkas_resample_pack_u8_multi(_p(arena), int(arena.numel()), _p(d_sources), S, _p(d_rows) if n else None, n,
+                                          _p(d_start), _p(pages), Q, Hp, Wp, _stream()), 'resample_pack_u8_multi')
+    return pages
+
+
+def pack_region_labels_multi(label_arena: torch.Tensor, label_sources, rows, num_pages: int, out_shape: Tuple[int, int],
+                             fdf: int, page_start=None, validate: bool = True,
+                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The int32 label pages of ``resample_pack_u8_multi`` at ``1/fdf`` of the pages' resolution (csrc/respack.hip; the
+    oracle: inferencing/packing.py::pack_region_labels_multi_host).  ``label_arena``: a 1-D int32 device tensor that holds
+    the rough label maps of the batch; ``label_sources`` (S,8) int64 rows (word offset, Hl, Wl, valid_h, valid_w, Hs, Ws,
+    0); ``rows`` / ``page_start`` as there, with the pages taken as ``out_shape * fdf``.  Returns (Q,Hq,Wq) int32 (``out`` if
+    given): a row's ``global_id`` where the cell's centre lies in its destination and the rough map of its source holds
+    neither another region's label than its ``local_id`` at the source position, else 0."""
+    if label_arena.dim() != 1 or label_arena.dtype != torch.int32:
+        raise ValueError(f'pack_region_labels_multi: label_arena must be a 1-D int32 tensor, got {label_arena.dtype} '
+                         f'{tuple(label_arena.shape)}')
+    Hq, Wq = (int(v) for v in out_shape)
+    if fdf != int(fdf) or not 1 <= int(fdf) <= 64:
+        raise ValueError(f'pack_region_labels_multi: fdf must be an integer in [1, 64], got {fdf}')
+    fdf = int(fdf)
+    if label_arena.numel() < 1 or Hq < 1 or Wq < 1 or max(Hq, Wq) * fdf > _PACK_DIM_MAX:
+        raise ValueError(f'pack_region_labels_multi: empty arena, or page {(Hq * fdf, Wq * fdf)} sides outside '
+                         f'[1, {_PACK_DIM_MAX}]')
+    if not label_arena.is_contiguous():
+        raise ValueError('pack_region_labels_multi: label_arena must be contiguous')
+    d_sources, d_rows, d_start, S, n, Q = _multi_tables('pack_region_labels_multi', label_sources, 8, int(label_arena.numel()),
+                                                        rows, page_start, num_pages, (Hq * fdf, Wq * fdf),
+                                                        label_arena.device, validate)
+    if out is not None and (tuple(out.shape) != (Q, Hq, Wq) or out.dtype != torch.int32 or not out.is_contiguous() or
+                            out.device != label_arena.device):
+        raise ValueError(f'pack_region_labels_multi: out must be a contiguous {(Q, Hq, Wq)} int32 tensor on {label_arena.device}')
+    _require_cuda(label_arena, out)
+    pages = out if out is not None else torch.empty((Q, Hq, Wq), dtype=torch.int32, device=label_arena.device)
+    check(lib.vkas_pack_region_labels_multi(_p(label_arena), int(label_arena.numel()), _p(d_sources), S,
+                                            _p(d_rows) if n else None, n, _p(d_start), fdf, _p(pages), Q, Hq, Wq, _stream()),
+          'pack_region_labels_multi')
+    return pages
+
+
 def _label_maps(who: str, labels: torch.Tensor, max_regions) -> Tuple[int, int, int, int]:
     if labels.dim() != 3:
         raise ValueError(f'{who}: labels must be (B, H, W), got {tuple(labels.shape)}')
