@@ -168,6 +168,40 @@ def test_label_page_matches_host(case):
         assert not want[~inside].any() and set(np.unique(want).tolist()) <= {0, *ids.tolist()}
 
 
+@pytest.mark.parametrize('Wp', [128, 130])  # dword / 16-byte stores, and byte / scalar stores
+def test_rows_that_must_be_skipped(Wp):
+    # a trusted device table (validate=False) whose bad rows the kernels must treat as absent; they point at page area that
+    # no good row reaches, and neither the source (every byte >= 1) nor the label rule (zero map: the row's id) would leave
+    # that area zero if one of them were taken
+    from vkit_ocr_model_adaptive_scaling_amd import ops
+    from vkit_ocr_model_adaptive_scaling_amd.inferencing import pack_region_labels_host, resample_host
+    src = np.maximum(C.image(40, 50, 13), 1)
+    lab = np.zeros((20, 25), np.int32)
+    lab[4:9, 3:12] = 2  # another region's label under part of the first good row
+    good = [(0, 0, 40, 50, 0, 0, 16, 20), (5, 7, 10, 12, 3, 60, 20, 30), (30, 40, 10, 10, 17, 100, 15, 28)]
+    bad = [(0, 0, 0, 4, 0, 24, 4, 4),         # an empty source side ...
+           (0, 0, 4, 4, 0, 30, 4, 0),         # ... and an empty destination side
+           (0, 0, 4, 4, 0, 36, 8193, 4),      # a side above 8192
+           (37, 0, 4, 4, 24, 40, 4, 4),       # a source rectangle one pixel past the source, below ...
+           (0, 47, 4, 4, 24, 46, 4, 4),       # ... and to the right
+           (0, 0, 4, 4, -2, 52, 4, 4)]        # a negative dy
+    rows = np.array(good[:1] + bad[:3] + good[1:2] + bad[3:] + good[2:], np.int32)
+    ids = np.arange(1, len(rows) + 1, dtype=np.int32)
+    is_good = np.array([tuple(r) in good for r in rows.tolist()])
+    want_page = resample_host(src, rows[is_good], (32, Wp))
+    d_rows, d_ids = torch.from_numpy(rows).cuda(), torch.from_numpy(ids).cuda()
+    got_page = ops.resample_pack_u8(torch.from_numpy(src).cuda(), d_rows, (32, Wp), validate=False).cpu().numpy()
+    assert not want_page[0:8, 24:56].any() and not want_page[24:28, 40:50].any(), 'the bad rows point at free page area'
+    assert np.array_equal(got_page, want_page)
+    for fdf in (1, 2):
+        out_shape = (32 // fdf, Wp // fdf)
+        want = pack_region_labels_host(lab, (20, 25), (40, 50), rows[is_good], ids[is_good], out_shape, fdf)
+        got = ops.pack_region_labels(torch.from_numpy(lab).cuda(), (20, 25), (40, 50), d_rows, d_ids, out_shape, fdf,
+                                     validate=False).cpu().numpy()
+        assert set(np.unique(want).tolist()) == {0, *ids[is_good].tolist()} and (want[:16 // fdf, :20 // fdf] == 0).any()
+        assert np.array_equal(got, want), fdf
+
+
 def test_same_call_twice_is_bit_equal():
     table, page = stacked_table(7, 60)
     a, b = device_pack(SRC, table, page), device_pack(SRC, table, page, prefill=0x55)

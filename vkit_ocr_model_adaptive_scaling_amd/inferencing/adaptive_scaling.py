@@ -212,6 +212,12 @@ def _ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def _no_characters(n: int):
+    """``points, probs, polygons`` of a result for n regions, each without characters."""
+    return ([np.zeros((0, 2), np.int32) for _ in range(n)], [np.zeros((0,), np.float32) for _ in range(n)],
+            [np.zeros((0, 4, 2), np.float64) for _ in range(n)])
+
+
 class AdaptiveScalingInferencing:
     """:79-188,295-396 without the vkit geometry."""
 
@@ -633,10 +639,7 @@ class AdaptiveScalingInferencing:
         for k, rid in enumerate(warp_ids.tolist()):
             warps[k] = warp_row(dirs[rid - 1], rects[rid - 1], image_shape, regions.resized_shape, boxes[rid - 1],
                                 regions.scales[rid - 1])
-        empty = lambda *shape, dtype: np.zeros(shape, dtype)
-        points = [empty(0, 2, dtype=np.int32) for _ in range(n)]
-        probs = [empty(0, dtype=np.float32) for _ in range(n)]
-        polygons = [empty(0, 4, 2, dtype=np.float64) for _ in range(n)]
+        points, probs, polygons = _no_characters(n)
         page = region_labels = None
         if len(ids) or len(warp_ids):
             fdf = 4 // c.precise_head_upsampling_factor
@@ -754,9 +757,7 @@ class AdaptiveScalingInferencing:
         for i, regions in enumerate(all_regions):
             n = int(counts[i])
             mine = np.flatnonzero(by_region[:, 0] == i)
-            points = [np.zeros((0, 2), np.int32) for _ in range(n)]
-            probs = [np.zeros((0,), np.float32) for _ in range(n)]
-            polygons = [np.zeros((0, 4, 2), np.float64) for _ in range(n)]
+            points, probs, polygons = _no_characters(n)
             for k in mine.tolist():
                 sel, r = order[lo[k]:hi[k]], int(by_region[k, 10]) - 1
                 points[r] = np.ascontiguousarray(all_points[sel])

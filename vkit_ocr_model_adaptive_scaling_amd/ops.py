@@ -2345,64 +2345,117 @@ def text_regions(mask: torch.Tensor, height: torch.Tensor, max_regions: int):
     return count, labels, boxes, areas, valid, medians
 
 
-def _placement_table(who: str, placements, src_shape, page_shape, device, validate: bool) -> torch.Tensor:
-    """The (n, 8) int32 placement table on ``device``.  A host table (numpy array or CPU tensor) is always validated
-    (inferencing/packing.py::check_placements: sides, bounds, disjoint destinations) and uploaded; a device table is copied
-    to the host for the same check when ``validate`` - a synchronisation -, else trusted (a captured graph's static table:
-    the kernels skip a row that is out of range, but overlapping destinations give an unspecified winner)."""
-    import numpy as np
-    from .inferencing.packing import check_placements
-    if isinstance(placements, torch.Tensor):
-        if placements.dim() != 2 or placements.shape[1] != 8:
-            raise ValueError(f'{who}: placements must be (n, 8), got {tuple(placements.shape)}')
-        if placements.dtype != torch.int32:
-            raise ValueError(f'{who}: placements must be int32, got {placements.dtype}')
-        if placements.is_cuda:
-            if validate:
-                check_placements(placements.cpu().numpy(), src_shape, page_shape)
-            if placements.device != device:
-                raise ValueError(f'{who}: placements are on {placements.device}, the image on {device}')
-            return placements.contiguous()
-        placements = placements.numpy()
-    else:
-        placements = np.asarray(placements)
-        if placements.ndim != 2 or placements.shape[1] != 8:
-            raise ValueError(f'{who}: placements must be (n, 8), got {placements.shape}')
-        if placements.dtype != np.int32:
-            raise ValueError(f'{who}: placements must be int32, got {placements.dtype}')
-    table = check_placements(placements, src_shape, page_shape)
-    if device.type != 'cuda':
-        return torch.from_numpy(table)
-    return torch.from_numpy(table).to(device, non_blocking=True)
-
-
 _PACK_DIM_MAX = 32768
+
+
+def _pack_sides(who: str, name: str, shape, fdf: int = 1) -> Tuple[int, int]:
+    """``shape`` as the (height, width) of ``name`` - a source, a page, or a label page at ``1/fdf`` of its page: both sides
+    are at least 1 and, times ``fdf``, at most ``_PACK_DIM_MAX`` (csrc/respack.hip's DIM_MAX)."""
+    try:
+        H, W = (int(v) for v in shape)
+    except (TypeError, ValueError):
+        raise ValueError(f'{who}: {name} must be (height, width), got {shape!r}') from None
+    if H < 1 or W < 1:
+        raise ValueError(f'{who}: empty {name} {(H, W)}')
+    if max(H, W) * fdf > _PACK_DIM_MAX:
+        raise ValueError(f'{who}: {name} {(H * fdf, W * fdf)} sides must not exceed {_PACK_DIM_MAX}')
+    return H, W
+
+
+def _pack_image(who: str, name: str, t: torch.Tensor) -> Tuple[int, int]:
+    if t.dim() != 3 or t.shape[2] != 3:
+        raise ValueError(f'{who}: {name} must be (H, W, 3), got {tuple(t.shape)}')
+    if t.dtype != torch.uint8:
+        raise ValueError(f'{who}: {name} must be uint8, got {t.dtype}')
+    return _pack_sides(who, name, t.shape[:2])
+
+
+def _pack_factor(who: str, fdf) -> int:
+    if fdf != int(fdf) or not 1 <= int(fdf) <= 64:
+        raise ValueError(f'{who}: fdf must be an integer in [1, 64], got {fdf}')
+    return int(fdf)
+
+
+def _pack_table(who: str, name: str, t, shape, dtype: str, device, validate: bool, check=None):
+    """A table of a pack - a numpy array, a CPU tensor or a device tensor of ``shape`` (an entry that is no int: any size) and
+    ``dtype`` - as a contiguous tensor on ``device``, and its host array (None for a trusted device table).  Host data is
+    always checked - ``check(array)`` returns what is uploaded - and uploaded; device data must be on ``device`` and is copied
+    to the host for the same check only when ``validate`` - a synchronisation -, else trusted (a captured graph's static
+    table: the kernels skip a row that is out of range, but overlapping destinations give an unspecified winner)."""
+    import numpy as np
+    if not isinstance(t, torch.Tensor):
+        t = np.asarray(t)
+    if len(t.shape) != len(shape) or any(isinstance(w, int) and v != w for v, w in zip(t.shape, shape)):
+        raise ValueError(f'{who}: {name} must be {shape}, got {tuple(t.shape)}'.replace("'", ''))  # ('n', 8) -> (n, 8)
+    if str(t.dtype).replace('torch.', '') != dtype:
+        raise ValueError(f'{who}: {name} must be {dtype}, got {t.dtype}')
+    if isinstance(t, torch.Tensor) and t.is_cuda:
+        if t.device != device:
+            raise ValueError(f'{who}: {name} is on {t.device}, not on {device}')
+        a = t.detach().cpu().numpy() if validate else None
+        if a is not None and check is not None:
+            check(a)
+        return t.contiguous(), a
+    a = t.numpy() if isinstance(t, torch.Tensor) else t
+    if check is not None:
+        a = check(a)
+    return torch.from_numpy(np.ascontiguousarray(a)).to(device, non_blocking=True), a
+
+
+def _placements(who: str, placements, src_shape, page_shape, device, validate: bool) -> torch.Tensor:
+    from .inferencing.packing import check_placements  # sides, bounds, disjoint destinations
+    return _pack_table(who, 'placements', placements, ('n', 8), 'int32', device, validate,
+                       lambda a: check_placements(a, src_shape, page_shape))[0]
+
+
+def _warps(who: str, warps, page_shape, device, validate: bool) -> torch.Tensor:
+    from .inferencing.packing import check_warps  # bounds, destinations inside the page and pairwise disjoint
+    return _pack_table(who, 'warps', warps, ('K', 12), 'int64', device, validate, lambda a: check_warps(a, page_shape))[0]
+
+
+def _label_args(who: str, labels: torch.Tensor, valid_shape, image_shape, out_shape, fdf):
+    """The geometry of a label pack, checked: ``(Hl, Wl, vh, vw, Hs, Ws, Hq, Wq, fdf)``."""
+    if labels.dim() != 2:
+        raise ValueError(f'{who}: labels must be (H, W), got {tuple(labels.shape)}')
+    if labels.dtype != torch.int32:
+        raise ValueError(f'{who}: labels must be int32, got {labels.dtype}')
+    Hl, Wl = _pack_sides(who, 'labels', labels.shape)
+    vh, vw = (int(v) for v in valid_shape)
+    if not (1 <= vh <= Hl and 1 <= vw <= Wl):
+        raise ValueError(f'{who}: valid_shape {(vh, vw)} does not fit the {(Hl, Wl)} label map')
+    fdf = _pack_factor(who, fdf)
+    Hs, Ws = _pack_sides(who, 'image_shape', image_shape)
+    Hq, Wq = _pack_sides(who, 'label page', out_shape, fdf)
+    return Hl, Wl, vh, vw, Hs, Ws, Hq, Wq, fdf
+
+
+def _region_ids(who: str, region_ids, n: int, device) -> torch.Tensor:
+    """The (n,) int32 region ids on ``device``; host ids are checked to start at 1, device ids are trusted."""
+    if not isinstance(region_ids, torch.Tensor):
+        import numpy as np
+        region_ids = torch.from_numpy(np.ascontiguousarray(np.asarray(region_ids)))
+    if region_ids.dim() != 1 or region_ids.shape[0] != n:
+        raise ValueError(f'{who}: region_ids must be ({n},), got {tuple(region_ids.shape)}')
+    if region_ids.dtype != torch.int32:
+        raise ValueError(f'{who}: region_ids must be int32, got {region_ids.dtype}')
+    if not region_ids.is_cuda and n and int(region_ids.min()) < 1:
+        raise ValueError(f'{who}: region ids start at 1 (0 is "no region")')
+    return region_ids.to(device, non_blocking=True).contiguous()
 
 
 def resample_pack_u8(src: torch.Tensor, placements, page_shape: Tuple[int, int], validate: bool = True,
                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Crops, rescales and packs rectangles of one image into a page (the step between the two passes,
     inferencing/adaptive_scaling.py:190-293 restated on pixels, csrc/respack.hip).  src (Hs,Ws,3) uint8 on the device;
-    ``placements`` (n,8) int32 rows (sy, sx, sh, sw, dy, dx, dh, dw), host or device (see ``_placement_table``); returns the
+    ``placements`` (n,8) int32 rows (sy, sx, sh, sw, dy, dx, dh, dw), host or device (see ``_pack_table``); returns the
     (Hp,Wp,3) uint8 page (``out`` if given): the resampled pixels inside the placements - the integer rule of
     inferencing/packing.py, equal to ``resample_host`` byte for byte - and zero elsewhere.  One launch; with a device table
     and ``validate=False`` it never synchronises, so it can be captured into a HIP graph."""
-    if src.dim() != 3 or src.shape[2] != 3:
-        raise ValueError(f'resample_pack_u8: src must be (H, W, 3), got {tuple(src.shape)}')
-    if src.dtype != torch.uint8:
-        raise ValueError(f'resample_pack_u8: src must be uint8, got {src.dtype}')
-    Hs, Ws = int(src.shape[0]), int(src.shape[1])
-    try:
-        Hp, Wp = (int(v) for v in page_shape)
-    except (TypeError, ValueError):
-        raise ValueError(f'resample_pack_u8: page_shape must be (height, width), got {page_shape!r}') from None
-    if Hs < 1 or Ws < 1 or Hp < 1 or Wp < 1:
-        raise ValueError(f'resample_pack_u8: empty source {(Hs, Ws)} or page {(Hp, Wp)}')
-    if max(Hs, Ws, Hp, Wp) > _PACK_DIM_MAX:
-        raise ValueError(f'resample_pack_u8: source {(Hs, Ws)} and page {(Hp, Wp)} sides must not exceed {_PACK_DIM_MAX}')
+    Hs, Ws = _pack_image('resample_pack_u8', 'src', src)
+    Hp, Wp = _pack_sides('resample_pack_u8', 'page_shape', page_shape)
     if out is not None and (tuple(out.shape) != (Hp, Wp, 3) or out.dtype != torch.uint8 or not out.is_contiguous()):
         raise ValueError(f'resample_pack_u8: out must be a contiguous {(Hp, Wp, 3)} uint8 tensor')
-    table = _placement_table('resample_pack_u8', placements, (Hs, Ws), (Hp, Wp), src.device, validate)
+    table = _placements('resample_pack_u8', placements, (Hs, Ws), (Hp, Wp), src.device, validate)
     _require_cuda(src, out)
     if out is not None and out.device != src.device:
         raise ValueError(f'resample_pack_u8: out is on {out.device}, src on {src.device}')
@@ -2421,36 +2474,11 @@ def pack_region_labels(labels: torch.Tensor, valid_shape: Tuple[int, int], image
     ``resample_pack_u8`` with the page taken as ``out_shape * fdf``; ``region_ids`` (n,) int32 >= 1, host or device.  Returns
     (Hq,Wq) int32: region_ids[k] where the pixel's centre lies in placement k and the rough map holds no other region's label
     at its source position, else 0."""
-    if labels.dim() != 2:
-        raise ValueError(f'pack_region_labels: labels must be (H, W), got {tuple(labels.shape)}')
-    if labels.dtype != torch.int32:
-        raise ValueError(f'pack_region_labels: labels must be int32, got {labels.dtype}')
-    Hl, Wl = int(labels.shape[0]), int(labels.shape[1])
-    vh, vw = (int(v) for v in valid_shape)
-    Hs, Ws = (int(v) for v in image_shape)
-    Hq, Wq = (int(v) for v in out_shape)
-    if not (1 <= vh <= Hl and 1 <= vw <= Wl):
-        raise ValueError(f'pack_region_labels: valid_shape {(vh, vw)} does not fit the {(Hl, Wl)} label map')
-    if fdf != int(fdf) or not 1 <= int(fdf) <= 64:
-        raise ValueError(f'pack_region_labels: fdf must be an integer in [1, 64], got {fdf}')
-    fdf = int(fdf)
-    if Hs < 1 or Ws < 1 or Hq < 1 or Wq < 1:
-        raise ValueError(f'pack_region_labels: empty image {(Hs, Ws)} or label page {(Hq, Wq)}')
-    if max(Hl, Wl, Hs, Ws, Hq * fdf, Wq * fdf) > _PACK_DIM_MAX:
-        raise ValueError(f'pack_region_labels: map, image and page sides must not exceed {_PACK_DIM_MAX}')
-    table = _placement_table('pack_region_labels', placements, (Hs, Ws), (Hq * fdf, Wq * fdf), labels.device, validate)
+    Hl, Wl, vh, vw, Hs, Ws, Hq, Wq, fdf = _label_args('pack_region_labels', labels, valid_shape, image_shape, out_shape, fdf)
+    table = _placements('pack_region_labels', placements, (Hs, Ws), (Hq * fdf, Wq * fdf), labels.device, validate)
     n = int(table.shape[0])
-    if not isinstance(region_ids, torch.Tensor):
-        import numpy as np
-        region_ids = torch.from_numpy(np.ascontiguousarray(np.asarray(region_ids)))
-    if region_ids.dim() != 1 or region_ids.shape[0] != n:
-        raise ValueError(f'pack_region_labels: region_ids must be ({n},), got {tuple(region_ids.shape)}')
-    if region_ids.dtype != torch.int32:
-        raise ValueError(f'pack_region_labels: region_ids must be int32, got {region_ids.dtype}')
-    if not region_ids.is_cuda and n and int(region_ids.min()) < 1:
-        raise ValueError('pack_region_labels: region ids start at 1 (0 is "no region")')
+    ids = _region_ids('pack_region_labels', region_ids, n, labels.device)
     _require_cuda(labels)
-    ids = region_ids.to(labels.device, non_blocking=True).contiguous()
     labels = labels.contiguous()
     out = torch.empty((Hq, Wq), dtype=torch.int32, device=labels.device)
     check(lib.vkas_pack_region_labels(_p(labels), Hl, Wl, vh, vw, Hs, Ws, _p(table) if n else None, _p(ids) if n else None, n,
@@ -2460,37 +2488,18 @@ def pack_region_labels(labels: torch.Tensor, valid_shape: Tuple[int, int], image
 
 def _multi_tables(who: str, sources, words: int, arena_size: int, rows, page_start, num_pages: int, page_shape, device,
                   validate: bool):
-    """The three tables of a multi pack on ``device``: the (S, ``words``) int64 source table, the (n, 12) int32 rows and the
-    (Q + 1,) int32 ``page_start`` (None: taken from the rows' page column).  Host tables (numpy arrays or CPU tensors) are
-    always validated - every source entry inside the arena of ``arena_size`` elements, the rows by inferencing/packing.py::
-    check_multi_rows, ``page_start`` against the rows - and uploaded; device tables are copied to the host for the same
-    checks when ``validate`` - a synchronisation -, else trusted: the kernels skip a row that is out of range, but
-    overlapping destinations give an unspecified winner."""
+    """The three tables of a multi pack on ``device`` (each as ``_pack_table`` takes it): the (S, ``words``) int64 source
+    table, the (n, 12) int32 rows and the (Q + 1,) int32 ``page_start`` (None: taken from the rows' page column).  What is
+    checked on the host: every source entry inside the arena of ``arena_size`` elements, the rows by
+    inferencing/packing.py::check_multi_rows, ``page_start`` against the rows."""
     import numpy as np
     from .inferencing.packing import check_multi_rows
     Q = int(num_pages)
     if Q != num_pages or not 1 <= Q <= 65535:
         raise ValueError(f'{who}: num_pages must be an integer in [1, 65535], got {num_pages}')
-
-    def host(t, name, shape, dtype):  # -> (the table on the host, or None for a trusted device table; is it on the device)
-        on_device = isinstance(t, torch.Tensor) and t.is_cuda
-        if on_device and t.device != device:
-            raise ValueError(f'{who}: {name} is on {t.device}, the arena on {device}')
-        if on_device:
-            a = t.detach().cpu().numpy() if validate else None
-        else:
-            a = t.numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
-        ref = t if a is None else a
-        if len(ref.shape) != len(shape) or any(w is not None and v != w for v, w in zip(ref.shape, shape)):
-            raise ValueError(f'{who}: {name} must be {shape}, got {tuple(ref.shape)}')
-        if str(ref.dtype).replace('torch.', '') != dtype:
-            raise ValueError(f'{who}: {name} must be {dtype}, got {ref.dtype}')
-        return a, on_device
-
-    h_sources, sources_on_device = host(sources, 'sources', (None, words), 'int64')
-    h_rows, rows_on_device = host(rows, 'rows', (None, 12), 'int32')
-    S = int((sources if h_sources is None else h_sources).shape[0])
-    n = int((rows if h_rows is None else h_rows).shape[0])
+    d_sources, h_sources = _pack_table(who, 'sources', sources, (None, words), 'int64', device, validate)
+    d_rows, h_rows = _pack_table(who, 'rows', rows, (None, 12), 'int32', device, validate)
+    S, n = int(d_sources.shape[0]), int(d_rows.shape[0])
     if S < 1:
         raise ValueError(f'{who}: no sources')
     if h_sources is not None:
@@ -2506,28 +2515,21 @@ def _multi_tables(who: str, sources, words: int, arena_size: int, rows, page_sta
         if ((t[:, 0] < 0) | (t[:, 0] + need > arena_size)).any():
             raise ValueError(f'{who}: a source leaves the arena of {arena_size} elements')
         if h_rows is not None:
-            h_rows = check_multi_rows(h_rows, shapes, page_shape, Q)
+            check_multi_rows(h_rows, shapes, page_shape, Q)
     elif h_rows is not None:
         raise ValueError(f'{who}: host rows need a host source table (or validate=True) to be checked against')
     if page_start is None:
         if h_rows is None:
             raise ValueError(f'{who}: page_start is needed with a device row table and validate=False')
         page_start = np.searchsorted(h_rows[:, 1], np.arange(Q + 1)).astype(np.int32)
-    h_start, start_on_device = host(page_start, 'page_start', (Q + 1,), 'int32')
+    d_start, h_start = _pack_table(who, 'page_start', page_start, (Q + 1,), 'int32', device, validate)
     if h_start is not None:
         if h_rows is not None:
             if not np.array_equal(h_start, np.searchsorted(h_rows[:, 1], np.arange(Q + 1))):
                 raise ValueError(f'{who}: page_start does not give each page its rows')
         elif h_start[0] < 0 or h_start[-1] > n or (np.diff(h_start) < 0).any():
             raise ValueError(f'{who}: page_start must rise from 0 to at most {n}')
-
-    def up(t, a, on_device):
-        if on_device:
-            return t.contiguous()
-        return torch.from_numpy(np.ascontiguousarray(a)).to(device, non_blocking=True)
-
-    return (up(sources, h_sources, sources_on_device), up(rows, h_rows, rows_on_device),
-            up(page_start, h_start, start_on_device), S, n, Q)
+    return d_sources, d_rows, d_start, S, n, Q
 
 
 def resample_pack_u8_multi(arena: torch.Tensor, sources, rows, num_pages: int, page_shape: Tuple[int, int], page_start=None,
@@ -2541,14 +2543,9 @@ def resample_pack_u8_multi(arena: torch.Tensor, sources, rows, num_pages: int, p
     device tables and ``validate=False`` it never synchronises, so it can be captured into a HIP graph."""
     if arena.dim() != 1 or arena.dtype != torch.uint8:
         raise ValueError(f'resample_pack_u8_multi: arena must be a 1-D uint8 tensor, got {arena.dtype} {tuple(arena.shape)}')
-    try:
-        Hp, Wp = (int(v) for v in page_shape)
-    except (TypeError, ValueError):
-        raise ValueError(f'resample_pack_u8_multi: page_shape must be (height, width), got {page_shape!r}') from None
-    if arena.numel() < 1 or Hp < 1 or Wp < 1 or max(Hp, Wp) > _PACK_DIM_MAX:
-        raise ValueError(f'resample_pack_u8_multi: empty arena, or page {(Hp, Wp)} sides outside [1, {_PACK_DIM_MAX}]')
-    if not arena.is_contiguous():
-        raise ValueError('resample_pack_u8_multi: arena must be contiguous')
+    Hp, Wp = _pack_sides('resample_pack_u8_multi', 'page_shape', page_shape)
+    if arena.numel() < 1 or not arena.is_contiguous():
+        raise ValueError('resample_pack_u8_multi: arena must be contiguous and not empty')
     d_sources, d_rows, d_start, S, n, Q = _multi_tables('resample_pack_u8_multi', sources, 4, int(arena.numel()), rows,
                                                         page_start, num_pages, (Hp, Wp), arena.device, validate)
     if out is not None and (tuple(out.shape) != (Q, Hp, Wp, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or
@@ -2573,15 +2570,10 @@ def pack_region_labels_multi(label_arena: torch.Tensor, label_sources, rows, num
     if label_arena.dim() != 1 or label_arena.dtype != torch.int32:
         raise ValueError(f'pack_region_labels_multi: label_arena must be a 1-D int32 tensor, got {label_arena.dtype} '
                          f'{tuple(label_arena.shape)}')
-    Hq, Wq = (int(v) for v in out_shape)
-    if fdf != int(fdf) or not 1 <= int(fdf) <= 64:
-        raise ValueError(f'pack_region_labels_multi: fdf must be an integer in [1, 64], got {fdf}')
-    fdf = int(fdf)
-    if label_arena.numel() < 1 or Hq < 1 or Wq < 1 or max(Hq, Wq) * fdf > _PACK_DIM_MAX:
-        raise ValueError(f'pack_region_labels_multi: empty arena, or page {(Hq * fdf, Wq * fdf)} sides outside '
-                         f'[1, {_PACK_DIM_MAX}]')
-    if not label_arena.is_contiguous():
-        raise ValueError('pack_region_labels_multi: label_arena must be contiguous')
+    fdf = _pack_factor('pack_region_labels_multi', fdf)
+    Hq, Wq = _pack_sides('pack_region_labels_multi', 'label page', out_shape, fdf)
+    if label_arena.numel() < 1 or not label_arena.is_contiguous():
+        raise ValueError('pack_region_labels_multi: label_arena must be contiguous and not empty')
     d_sources, d_rows, d_start, S, n, Q = _multi_tables('pack_region_labels_multi', label_sources, 8, int(label_arena.numel()),
                                                         rows, page_start, num_pages, (Hq * fdf, Wq * fdf),
                                                         label_arena.device, validate)
@@ -2658,33 +2650,6 @@ def region_extents(labels: torch.Tensor, dirs, validate: bool = True) -> torch.T
     return out
 
 
-def _warp_table(who: str, warps, page_shape, device, validate: bool) -> torch.Tensor:
-    """The (K, 12) int64 warp table on ``device``, checked as ``_placement_table`` checks placements
-    (inferencing/packing.py::check_warps: bounds, destinations inside the page and pairwise disjoint)."""
-    import numpy as np
-    from .inferencing.packing import check_warps
-    if isinstance(warps, torch.Tensor):
-        if warps.dim() != 2 or warps.shape[1] != 12:
-            raise ValueError(f'{who}: warps must be (K, 12), got {tuple(warps.shape)}')
-        if warps.dtype != torch.int64:
-            raise ValueError(f'{who}: warps must be int64, got {warps.dtype}')
-        if warps.is_cuda:
-            if validate:
-                check_warps(warps.cpu().numpy(), page_shape)
-            if warps.device != device:
-                raise ValueError(f'{who}: warps are on {warps.device}, the image on {device}')
-            return warps.contiguous()
-        warps = warps.numpy()
-    else:
-        warps = np.asarray(warps)
-        if warps.ndim != 2 or warps.shape[1] != 12:
-            raise ValueError(f'{who}: warps must be (K, 12), got {warps.shape}')
-        if warps.dtype != np.int64:
-            raise ValueError(f'{who}: warps must be int64, got {warps.dtype}')
-    table = torch.from_numpy(check_warps(warps, page_shape))
-    return table if device.type != 'cuda' else table.to(device, non_blocking=True)
-
-
 def warp_pack_u8(src: torch.Tensor, warps, page: torch.Tensor, validate: bool = True) -> torch.Tensor:
     """Cuts slanted rectangles out of one image along their own axes into a page (csrc/respack.hip; the rule and the oracle:
     inferencing/packing.py::warp_host).  src (Hs,Ws,3) uint8 and ``page`` (Hp,Wp,3) uint8, contiguous, on the device;
@@ -2692,18 +2657,11 @@ def warp_pack_u8(src: torch.Tensor, warps, page: torch.Tensor, validate: bool = 
     the warps' destinations - it runs after ``resample_pack_u8`` has written the page and its zeros - and returns ``page``.
     The destinations must also be disjoint from that call's placements (``check_warps(..., placements)``: the caller's
     check).  One launch; with a device table and ``validate=False`` it never synchronises."""
-    if src.dim() != 3 or src.shape[2] != 3 or page.dim() != 3 or page.shape[2] != 3:
-        raise ValueError(f'warp_pack_u8: src and page must be (H, W, 3), got {tuple(src.shape)} and {tuple(page.shape)}')
-    if src.dtype != torch.uint8 or page.dtype != torch.uint8:
-        raise ValueError(f'warp_pack_u8: src and page must be uint8, got {src.dtype} and {page.dtype}')
-    Hs, Ws, Hp, Wp = int(src.shape[0]), int(src.shape[1]), int(page.shape[0]), int(page.shape[1])
-    if Hs < 1 or Ws < 1 or Hp < 1 or Wp < 1:
-        raise ValueError(f'warp_pack_u8: empty source {(Hs, Ws)} or page {(Hp, Wp)}')
-    if max(Hs, Ws, Hp, Wp) > _PACK_DIM_MAX:
-        raise ValueError(f'warp_pack_u8: source {(Hs, Ws)} and page {(Hp, Wp)} sides must not exceed {_PACK_DIM_MAX}')
+    Hs, Ws = _pack_image('warp_pack_u8', 'src', src)
+    Hp, Wp = _pack_image('warp_pack_u8', 'page', page)
     if not page.is_contiguous():
         raise ValueError('warp_pack_u8: page must be contiguous (it is written in place)')
-    table = _warp_table('warp_pack_u8', warps, (Hp, Wp), src.device, validate)
+    table = _warps('warp_pack_u8', warps, (Hp, Wp), src.device, validate)
     _require_cuda(src, page)
     if page.device != src.device:
         raise ValueError(f'warp_pack_u8: page is on {page.device}, src on {src.device}')
@@ -2719,40 +2677,17 @@ def warp_region_labels(labels: torch.Tensor, valid_shape: Tuple[int, int], image
     respack.hip; the rule and the oracle: inferencing/packing.py::warp_region_labels_host).  Arguments as
     ``pack_region_labels`` with ``warps`` as in ``warp_pack_u8``; writes ONLY the cells whose centres lie inside the warps'
     destinations and returns ``out``."""
-    if labels.dim() != 2 or out.dim() != 2:
-        raise ValueError(f'warp_region_labels: labels and out must be (H, W), got {tuple(labels.shape)} and {tuple(out.shape)}')
-    if labels.dtype != torch.int32 or out.dtype != torch.int32:
-        raise ValueError(f'warp_region_labels: labels and out must be int32, got {labels.dtype} and {out.dtype}')
-    Hl, Wl = int(labels.shape[0]), int(labels.shape[1])
-    vh, vw = (int(v) for v in valid_shape)
-    Hs, Ws = (int(v) for v in image_shape)
-    Hq, Wq = int(out.shape[0]), int(out.shape[1])
-    if not (1 <= vh <= Hl and 1 <= vw <= Wl):
-        raise ValueError(f'warp_region_labels: valid_shape {(vh, vw)} does not fit the {(Hl, Wl)} label map')
-    if fdf != int(fdf) or not 1 <= int(fdf) <= 64:
-        raise ValueError(f'warp_region_labels: fdf must be an integer in [1, 64], got {fdf}')
-    fdf = int(fdf)
-    if Hs < 1 or Ws < 1 or Hq < 1 or Wq < 1:
-        raise ValueError(f'warp_region_labels: empty image {(Hs, Ws)} or label page {(Hq, Wq)}')
-    if max(Hl, Wl, Hs, Ws, Hq * fdf, Wq * fdf) > _PACK_DIM_MAX:
-        raise ValueError(f'warp_region_labels: map, image and page sides must not exceed {_PACK_DIM_MAX}')
-    if not out.is_contiguous():
-        raise ValueError('warp_region_labels: out must be contiguous (it is written in place)')
-    table = _warp_table('warp_region_labels', warps, (Hq * fdf, Wq * fdf), labels.device, validate)
+    if out.dim() != 2 or out.dtype != torch.int32 or not out.is_contiguous():
+        raise ValueError(f'warp_region_labels: out must be a contiguous (H, W) int32 tensor (it is written in place), got '
+                         f'{out.dtype} {tuple(out.shape)}')
+    Hl, Wl, vh, vw, Hs, Ws, Hq, Wq, fdf = _label_args('warp_region_labels', labels, valid_shape, image_shape, out.shape,
+                                                      fdf)
+    table = _warps('warp_region_labels', warps, (Hq * fdf, Wq * fdf), labels.device, validate)
     K = int(table.shape[0])
-    if not isinstance(region_ids, torch.Tensor):
-        import numpy as np
-        region_ids = torch.from_numpy(np.ascontiguousarray(np.asarray(region_ids)))
-    if region_ids.dim() != 1 or region_ids.shape[0] != K:
-        raise ValueError(f'warp_region_labels: region_ids must be ({K},), got {tuple(region_ids.shape)}')
-    if region_ids.dtype != torch.int32:
-        raise ValueError(f'warp_region_labels: region_ids must be int32, got {region_ids.dtype}')
-    if not region_ids.is_cuda and K and int(region_ids.min()) < 1:
-        raise ValueError('warp_region_labels: region ids start at 1 (0 is "no region")')
+    ids = _region_ids('warp_region_labels', region_ids, K, labels.device)
     _require_cuda(labels, out)
     if out.device != labels.device:
         raise ValueError(f'warp_region_labels: out is on {out.device}, labels on {labels.device}')
-    ids = region_ids.to(labels.device, non_blocking=True).contiguous()
     labels = labels.contiguous()
     check(lib.vkas_warp_region_labels(_p(labels), Hl, Wl, vh, vw, Hs, Ws, _p(table) if K else None, _p(ids) if K else None, K,
                                       fdf, _p(out), Hq, Wq, _stream()), 'warp_region_labels')
