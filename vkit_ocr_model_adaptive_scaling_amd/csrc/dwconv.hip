@@ -454,11 +454,6 @@ __global__ __launch_bounds__(512, 4) void dwconv7x7_mfma_kernel(const T* __restr
       sv[k] = v;
     }
   };
-  int t = walker;
-  if (t >= nsp) return;
-  // the first halo tile is requested in front of the weight table: the two round trips to memory of a workgroup's prologue
-  // travel together (at small maps - one or two tiles per workgroup - the prologue is most of the launch)
-  fetch(t);
   // band matrices of this wave's 4 channels: A_ky[i][k], lane = (i, k = 8g .. 8g+7).  The slice's 49 x 16 weights go
   // through LDS (the result planes are idle): per-lane gathers straight from global memory would keep 224 loads in flight
   for (int i = tid; i < 49 * 16; i += NTHR) {
@@ -487,6 +482,10 @@ __global__ __launch_bounds__(512, 4) void dwconv7x7_mfma_kernel(const T* __restr
   float bv[2];
 #pragma unroll
   for (int cc = 0; cc < 2; ++cc) bv[cc] = (bias && c0 + wave * 2 + cc < Cp) ? bias[c0 + wave * 2 + cc] : 0.f;
+
+  int t = walker;
+  if (t >= nsp) return;
+  fetch(t);
 
   // channel 8*chunk + k of the slice -> plane 2k + chunk (the two chunk lanes of a pixel land 24 banks apart)
   auto stage = [&]() {
@@ -598,15 +597,20 @@ __global__ __launch_bounds__(512, 4) void dwconv7x7_mfma_kernel(const T* __restr
 
 // ---------------------------------------------------------------------------------------------------------------------
 // 16-bit weight gradient on the matrix cores: gw[c][ky][kx] = sum_{y,x} dy[y][x][c] * x[y+ky-3][x+kx-3][c].
-// For one channel, one input row r and the 32 columns of a tile,
-//      D[i][j] += A[i][k] * B[k][j],   A[i][k] = dy[r - 3 + i][x0 + k]        (i < 7: the 7 output rows that see row r),
-//                                      B[k][j] = x[r][x0 + k + j - 3]         (j < 7: the 7 lags; a Toeplitz matrix),
-// accumulates all 49 taps at once: D[i][j] -> gw[ky = 6 - i][kx = j].  Column j = 7 of B is all ones, so D[3][7] collects
-// sum dy (the bias gradient, counted once: i = 3 is the row r itself).  22 MFMAs per channel and tile instead of
-// 16 * 32 * 49 FMAs.  A is a 16-byte aligned row read; B needs 8 consecutive elements at an element offset 8g + j that
-// is odd for odd j: every lane reads 5 dwords and funnels them by 0 or 16 bits (v_alignbit).  Same persistent
-// 16-channel-slice workgroups as the forward kernel; the 4-register accumulator of a channel lives across all tiles of the
-// walker and leaves as one partial row per walker (summed by the finalize kernel).
+// For one channel, one PAIR of input rows (r, r + 1), r = y0 - 3 + 2m, and the 32 columns of a tile,
+//      D[i][j] += A[i][k] * B[k][j],   A[i][k]     = dy[r - 3 + i][x0 + k]    (i < 8: the 8 output rows that see r or r + 1),
+//                                      B[k][j]     = x[r][x0 + k + j - 3]     (j < 7: the 7 lags; a Toeplitz matrix),
+//                                      B[k][8 + j] = x[r + 1][x0 + k + j - 3] (j < 7: the same lags one row down),
+// accumulates all 49 taps twice over: D[i][j] -> gw[ky = 6 - i][kx = j] (i <= 6) and D[i][8 + j] -> gw[ky = 7 - i][kx = j]
+// (1 <= i <= 7); D[7][0..6] and D[0][8..14] pair a dy row with an input row it does not see and are dropped.  The two halves
+// of a tap sit in different lanes and are added once per walker, in a fixed order, by lane shuffles.  Column 7 of B is all
+// ones, so D[3][7] + D[4][7] collects sum dy (the bias gradient: pairs step by two rows, rows 3 and 4 together see every dy
+// row exactly once); column 15 is ones too and ignored.  11 MFMAs per channel and tile - all 16 B columns and 8 of 16 A
+// rows carry data - instead of 16 * 32 * 49 FMAs.  A is a 16-byte aligned row read; B needs 8 consecutive elements at an
+// element offset 8g + j that is odd for odd j: every lane reads 5 dwords and funnels them by 0 or 16 bits (v_alignbit);
+// lanes li >= 8 do so one staged row further down.  Same persistent 16-channel-slice workgroups as the forward kernel; the
+// 4-register accumulator of a channel lives across all tiles of the walker and leaves as one partial row per walker (summed
+// by the finalize kernel).
 constexpr int WXP = 40;                          // elements per staged x row (38 halo columns + 2)
 constexpr int WDP = 48;                          // elements per staged dy row (32 + 16: 96-byte pitch)
 constexpr int WPB_X = MIY * WXP;                 // elements per x plane
@@ -709,10 +713,12 @@ __global__ __launch_bounds__(512, 4) void dwconv7x7_wgrad_mfma_kernel(const T* _
   };
 
   f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-  // per-lane constants of the B gather: element offset 8g + j inside an x row (j clamped to a valid lag), funnel shift
-  const int jl = li < 7 ? li : 6;
+  // per-lane constants of the B gather: lanes li < 8 take the even row of a pair, lanes li >= 8 the odd one; element offset
+  // 8g + j inside that x row (j = li & 7 clamped to a valid lag), funnel shift
+  const int jl = (li & 7) < 7 ? (li & 7) : 6;
   const int eo = 8 * g + jl;
   const unsigned sh = (eo & 1) ? 16u : 0u;
+  const int xoff = (li >> 3) * (WXP / 2) + (eo >> 1);  // dwords from the start of the pair's even row
   v8 ones;
 #pragma unroll
   for (int e = 0; e < 8; ++e) ones[e] = (T)1.0f;
@@ -730,24 +736,24 @@ __global__ __launch_bounds__(512, 4) void dwconv7x7_wgrad_mfma_kernel(const T* _
       for (int cc = 0; cc < ((DW_ABL & 512) ? 0 : 2); ++cc) {
         const int cl = wave * 2 + cc;
         const int P = (cl & 7) * 2 + (cl >> 3);
-        const unsigned* xrow = reinterpret_cast<const unsigned*>(xp + P * WPB_X) + (eo >> 1);
+        const unsigned* xrow = reinterpret_cast<const unsigned*>(xp + P * WPB_X) + xoff;
         const T* dpl = dp + P * WPB_D + 8 * g;
         const T* zrow = dp + 16 * WPB_D + 8 * g;
 #pragma unroll 2
-        for (int rr = 0; rr < MIY; ++rr) {  // input row r = y0 - 3 + rr
-          // A: dy row (rr - 6 + i) of the tile for i < 7, zeros elsewhere
-          const int p = rr - 6 + li;
-          const T* ap = (li < 7 && (unsigned)p < (unsigned)MTY) ? dpl + p * WDP : zrow;
+        for (int m = 0; m < MIY / 2; ++m) {  // input rows r = y0 - 3 + 2m and r + 1
+          // A: dy row (2m - 6 + i) of the tile for i < 8, zeros elsewhere
+          const int p = 2 * m - 6 + li;
+          const T* ap = (li < 8 && (unsigned)p < (unsigned)MTY) ? dpl + p * WDP : zrow;
           const v8 af = *reinterpret_cast<const v8*>(ap);
-          // B: 8 elements of x row rr starting at element eo
-          const unsigned* bp = xrow + rr * (WXP / 2);
+          // B: 8 elements of x row 2m (li < 8) or 2m + 1 (li >= 8) starting at element eo
+          const unsigned* bp = xrow + m * WXP;
           const unsigned d0 = bp[0], d1 = bp[1], d2 = bp[2], d3 = bp[3], d4 = bp[4];
           union { unsigned u[4]; v8 v; } bf;
           bf.u[0] = __builtin_amdgcn_alignbit(d1, d0, sh);
           bf.u[1] = __builtin_amdgcn_alignbit(d2, d1, sh);
           bf.u[2] = __builtin_amdgcn_alignbit(d3, d2, sh);
           bf.u[3] = __builtin_amdgcn_alignbit(d4, d3, sh);
-          acc[cc] = dw_mfma(af, li == 7 ? ones : bf.v, acc[cc]);
+          acc[cc] = dw_mfma(af, (li & 7) == 7 ? ones : bf.v, acc[cc]);
         }
       }
       if (!more) break;
@@ -760,18 +766,25 @@ __global__ __launch_bounds__(512, 4) void dwconv7x7_wgrad_mfma_kernel(const T* _
       asm volatile("" ::: "memory");
     }
   }
-  // partial row of this walker: [tap = ky*7 + kx][Cp] + row 49 = bias; D[i][j]: lane holds i = 4g + r, j = li
+  // partial row of this walker: [tap = ky*7 + kx][Cp] + row 49 = bias; D[i][j]: lane holds i = 4g + r, j = li.  The second
+  // half of tap (6 - i, j) is D[i + 1][8 + j]: one register up in lane + 8, or register 0 of lane + 24 for r = 3.  Every
+  // lane of every wave takes the shuffles (walkers without a tile included: they write their zero row)
   float* prow = partial + (long)walker * 50 * Cp;
 #pragma unroll
   for (int cc = 0; cc < 2; ++cc) {
+    const float up = __shfl_down(acc[cc][0], 16, 64);  // D[4g + 4][li]
+    const float nxt[4] = {acc[cc][1], acc[cc][2], acc[cc][3], up};
+    float sum[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) sum[r] = acc[cc][r] + __shfl_down(nxt[r], 8, 64);
     const int ch = c0 + wave * 2 + cc;
     if (ch >= Cp) continue;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int i = 4 * g + r;
-      if (i < 7 && li < 7) prow[(long)((6 - i) * 7 + li) * Cp + ch] = acc[cc][r];
-      if (i == 3 && li == 7) prow[49L * Cp + ch] = acc[cc][r];
+      if (i < 7 && li < 7) prow[(long)((6 - i) * 7 + li) * Cp + ch] = sum[r];
     }
+    if (g == 0 && li == 7) prow[49L * Cp + ch] = acc[cc][3] + up;  // D[3][7] + D[4][7]
   }
 }
 
