@@ -286,7 +286,9 @@ int vkas_scale_res_bwd(const void* dout, long lddo, const void* z, long ldz, con
 size_t vkas_scale_res_bwd_ws_bytes(long M, int Cp);
 
 /* ---- resize: F.interpolate bilinear (upernext.py:79,178-195,237-244), nearest (fpn.py:125-142,197-204) */
-/* mode 0 bilinear (align_corners=False), 1 nearest.  accumulate != 0: y += resize(x) (top-down add). */
+/* mode 0 bilinear (align_corners=False), 1 nearest: src = min((int)floorf(dst * scale), in - 1) with scale = (float)in / out,
+   product and quotient rounded to float32 as F.interpolate rounds them (not floor(dst * in / out) in integers: the two part
+   where the exact quotient is an integer).  accumulate != 0: y += resize(x) (top-down add). */
 int vkas_resize_fwd(const void* x, long ldx, void* y, long ldy, int B, int Hin, int Win, int Hout, int Wout,
                     int Cp, int mode, int accumulate, int dtype, void* stream);
 /* dx (+)= resize^T(dy) */

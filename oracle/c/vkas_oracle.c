@@ -96,15 +96,21 @@ void vko_bilinear(const double* x, double* y, int B, int C, int Hi, int Wi, int 
   }
 }
 
-/* F.interpolate(mode='nearest'): src = min(floor(dst * in / out), in - 1): fpn.py:125-142,197-204 */
+/* F.interpolate(mode='nearest'): src = min((int)floorf(dst * scale), in - 1), scale = (float)in / out, every step rounded to
+   float32 as torch does (volatile: no excess precision, no contraction): fpn.py:125-142,197-204 */
+static int vko_nearest_index(int dst, int n_in, int n_out) {
+  volatile float scale = (float)n_in / (float)n_out;
+  volatile float prod = (float)dst * scale;
+  const int s = (int)floorf(prod);
+  return s < n_in - 1 ? s : n_in - 1;
+}
+
 void vko_nearest(const double* x, double* y, int B, int C, int Hi, int Wi, int Ho, int Wo) {
   for (int b = 0; b < B; ++b)
     for (int c = 0; c < C; ++c)
       for (int oy = 0; oy < Ho; ++oy)
         for (int ox = 0; ox < Wo; ++ox) {
-          int iy = (int)(((long)oy * Hi) / Ho), ix = (int)(((long)ox * Wi) / Wo);
-          if (iy > Hi - 1) iy = Hi - 1;
-          if (ix > Wi - 1) ix = Wi - 1;
+          const int iy = vko_nearest_index(oy, Hi, Ho), ix = vko_nearest_index(ox, Wi, Wo);
           y[IDX4(b, c, oy, ox, C, Ho, Wo)] = x[IDX4(b, c, iy, ix, C, Hi, Wi)];
         }
 }

@@ -145,13 +145,19 @@ def resize_bilinear(x: Tensor, size: Tuple[int, int]) -> Tensor:
 
 
 def resize_nearest(x: Tensor, size: Tuple[int, int]) -> Tensor:
-    """F.interpolate(mode='nearest') (model/fpn.py:125-129,138-142,197-204): src = floor(dst * in/out)."""
+    """F.interpolate(mode='nearest') (model/fpn.py:125-129,138-142,197-204): src = min(floor(dst * scale), in - 1) with
+    scale = in / out and the product both rounded to float32, as torch evaluates them."""
     hi, wi = x.shape[-2:]
     ho, wo = size
-    # integer form of floor(dst * in / out); exact for the sizes used here
-    iy = torch.clamp((torch.arange(ho, dtype=torch.int64) * hi) // ho, max=hi - 1)
-    ix = torch.clamp((torch.arange(wo, dtype=torch.int64) * wi) // wo, max=wi - 1)
-    return x.index_select(2, iy).index_select(3, ix)
+    return x.index_select(2, nearest_axis(hi, ho)).index_select(3, nearest_axis(wi, wo))
+
+
+def nearest_axis(n_in: int, n_out: int) -> Tensor:
+    """Source index of every destination index along one axis of F.interpolate(mode='nearest'), in torch's float32
+    arithmetic: where dst * in / out is an integer, the rounded product can fall just below it."""
+    scale = torch.tensor(float(n_in), dtype=torch.float32) / torch.tensor(float(n_out), dtype=torch.float32)
+    src = torch.floor(torch.arange(n_out, dtype=torch.float32) * scale).to(torch.int64)
+    return torch.clamp(src, max=n_in - 1)
 
 
 def adaptive_avg_pool(x: Tensor, s: int) -> Tensor:

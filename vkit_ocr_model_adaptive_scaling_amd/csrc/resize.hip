@@ -17,9 +17,17 @@ __device__ __forceinline__ void bilinear_src(int dst, float scale, int n_in, int
   i1 = i0 + 1 < n_in ? i0 + 1 : n_in - 1;
   w1 = src - (float)i0;
 }
-// nearest: src = min(floor(dst * in/out), in-1), evaluated in integers
+// a * (1 - w) + b * w with the contraction spelled out: one rounded product, one fused multiply-add.  Left to the compiler,
+// the generic and the x2 forward contracted these sums differently (mul + fma for some outputs, mul + mul + add for others)
+// and about a sixth of their fp32 outputs differed in the last bit (the 16-bit types rounded it away; the backwards agreed);
+// written this way both round the same products in the same places (tests/test_gpu_resize.py compares them).
+__device__ __forceinline__ float lerp2(float a, float b, float w) { return fmaf(b, w, __fmul_rn(a, 1.f - w)); }
+// nearest: src = min((int)floorf(dst * scale), in-1) with the float32 scale = (float)in / out, as F.interpolate evaluates it
+// (one rounded division, one rounded product: where dst * in / out is an integer the product may fall just below it, and
+// the integer form floor(dst * in / out) would then pick the next source index)
 __device__ __forceinline__ int nearest_src(int dst, int n_in, int n_out) {
-  const int s = (int)(((long)dst * n_in) / n_out);
+  const float scale = __fdiv_rn((float)n_in, (float)n_out);
+  const int s = (int)floorf(__fmul_rn((float)dst, scale));
   return s < n_in - 1 ? s : n_in - 1;
 }
 
@@ -69,9 +77,9 @@ __global__ __launch_bounds__(256) void resize_fwd_kernel(const T* __restrict__ x
     load8(xb + ((long)y1 * Win + x1) * ldx, d);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      const float top = a[k] * (1.f - wx) + bq[k] * wx;
-      const float bot = c[k] * (1.f - wx) + d[k] * wx;
-      o[k] = top * (1.f - wy) + bot * wy;
+      const float top = lerp2(a[k], bq[k], wx);
+      const float bot = lerp2(c[k], d[k], wx);
+      o[k] = lerp2(top, bot, wy);
     }
   } else {
     const int iy = nearest_src(oy, Hin, Hout), ix = nearest_src(ox, Win, Wout);
@@ -109,7 +117,7 @@ __device__ __forceinline__ void dst_range(int i, int n_in, int n_out, float scal
 // R = destination columns whose x weight is evaluated ONCE per source pixel and kept in registers (a x4 / x8 upsample - the
 // necks' final resize to level-0 size, upernext.py:191-195 - has 8 / 16 of them): the index function is then evaluated
 // nx + ny times per source pixel instead of nx * ny times (at x8 that arithmetic, not the 256 L1 / L2 resident loads, was
-// 90% of the launch).  Columns beyond R (never at the instantiated factors) take the per-pair evaluation.  Same products,
+// 90% of the launch).  Columns beyond R (bilinear at ratios above 8) take the per-pair evaluation.  Same products,
 // same order (oy ascending, then ox ascending) as before: bit-identical sums.
 template <typename T, int R>
 __global__ __launch_bounds__(256) void resize_bwd_kernel(const T* __restrict__ dy, long lddy, T* __restrict__ dx,
@@ -287,9 +295,9 @@ __global__ __launch_bounds__(256) void resize2x_fwd_kernel(const T* __restrict__
         const float r1c1 = a == 0 ? (i == 0 ? (c2 == 0 ? (j == 0 ? n[2][2][k] : n[2][1][k]) : n[2][2][k])
                                             : (c2 == 0 ? (j == 0 ? n[1][2][k] : n[1][1][k]) : n[1][2][k]))
                                   : (c2 == 0 ? (j == 0 ? n[2][2][k] : n[2][1][k]) : n[2][2][k]);
-        const float top = a00 * (1.f - wx[c2]) + a01 * wx[c2];
-        const float bot = r1c0 * (1.f - wx[c2]) + r1c1 * wx[c2];
-        o[k] = top * (1.f - wy[a]) + bot * wy[a];
+        const float top = lerp2(a00, a01, wx[c2]);
+        const float bot = lerp2(r1c0, r1c1, wx[c2]);
+        o[k] = lerp2(top, bot, wy[a]);
       }
       T* dst = y + (((long)b * Hout + 2 * i + a) * Wout + 2 * j + c2) * ldy + v * 8;
       if (accumulate) {
