@@ -499,6 +499,22 @@ long vkas_char_polygons_workspace_bytes(int B, int H, int W, int size);
 int vkas_char_polygons(const float* prob, const float* offset, const float* angle, const float* dist, int B, int H, int W,
                        int size, float thr, float scale_y, float scale_x, void* workspace, size_t workspace_bytes,
                        int* count, int* points, float* probs, float* quads, void* stream);
+/* Training label maps from character quadrilaterals (dataset/labels.py holds the rule - this project's own, restated on
+ * pixels - and the host oracle char_label_maps_host).  rows (B,K,20) int32, one row per quad: 8 Q4 corners (y, x) of up-left,
+ * up-right, down-right, down-left in map coordinates; the inclusive pixel box (y0, x0, y1, x1); fp32 bits of the centre (cy,
+ * cx), of the inverse frame (m00, m01, m10, m11) and of the height; valid.  count (B) is clamped to [0, K] on the device.  A
+ * cell (y, x) of the h x w map is inside a row iff the row is valid, the cell lies in the row's box and the four int64 edge
+ * functions of the corners are >= 0 at (16y + 8, 16x + 8); its owner is the inside row with the smallest fp32 a = k * (s*s +
+ * t*t), s = m00*dy + m01*dx, t = m10*dy + m11*dx, dy = (float(y) + 0.5f) - cy (every operation rounded, no fma), ties to the
+ * lowest index.  Outputs, each (B,CH,CW) = the map cropped to rows [up, up+CH) and columns [left, left+CW), each may be NULL
+ * (not all): owner int32 = index + 1 or 0; mask = owner != 0; height = the owner's; score = expf(-a) of the owner; 0 without
+ * one.  One launch; no atomics, no allocation, no synchronisation; every output element is written exactly once: capture-safe
+ * and bit-identical from run to run.  A row with valid == 0 is skipped and a row's box is intersected with the tile, whatever
+ * it holds, so no table content makes the kernel touch memory outside its buffers.  B in 0..65535, K >= 0, B*h*w < 2^31, the
+ * crop inside the map, k finite and positive; rows 16-byte aligned.  16-byte stores when CW % 4 == 0 and the outputs are
+ * 16-byte aligned, scalar stores otherwise. */
+int vkas_char_label_maps(const int* rows, const int* count, int B, int K, int h, int w, int up, int left, int CH, int CW,
+                         float k, int* owner, float* mask, float* height, float* score, void* stream);
 /* Text regions of the rough maps (the step between the passes, :190-279, restated on pixels).  mask (B,H,W) uint8 and height
  * (B,H,W) fp32 as vkas_rough_postprocess writes them.  A region is an 8-connected component of mask != 0; the regions of each
  * image are numbered 1..N by their first pixel in row-major order.  Outputs: count (B) = the true N of each image; labels

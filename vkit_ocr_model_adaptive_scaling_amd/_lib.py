@@ -186,6 +186,8 @@ _SIGS = {
     'vkas_char_polygons_workspace_bytes': (c_long, [c_int, c_int, c_int, c_int]),
     'vkas_char_polygons': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, _P, c_size_t,
                                    _P, _P, _P, _P, _P]),
+    'vkas_char_label_maps': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, _P,
+                                     _P]),
     'vkas_text_regions_workspace_bytes': (c_longlong, [c_int, c_int, c_int, c_int]),
     'vkas_text_regions': (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, c_longlong, _P, _P, _P, _P, _P, _P, _P]),
     'vkas_resample_pack_u8': (c_int, [_P, c_int, c_int, _P, c_int, _P, c_int, c_int, _P]),

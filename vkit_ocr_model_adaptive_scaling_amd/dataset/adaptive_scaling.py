@@ -9,7 +9,8 @@ the hot path consumes is the COLLATED batch, whose schema this module reproduces
                      | corner_angles (B,P,4) f32 | corner_distances (B,P,3) f32
 
 ``SyntheticAdaptiveScalingIterableDataset`` yields seeded random records of that shape (the role ``bench.py`` and the tests
-need a loader for); real data plugs in by yielding ``(RoughSample, PreciseSample)`` records from any other source."""
+need a loader for); real data plugs in by yielding ``(RoughSample, PreciseSample)`` records from any other source, or - from
+character quadrilaterals, with the dense maps rasterised on the device - through ``dataset/labels.py``."""
 from typing import Any, Dict, Iterable, Iterator, List, Mapping, Optional, Sequence, Tuple
 
 import attrs

@@ -2299,6 +2299,50 @@ def char_polygons(prob: torch.Tensor, offset: torch.Tensor, angle: torch.Tensor,
     return count, points, probs, quads
 
 
+def char_label_maps(rows: torch.Tensor, count: torch.Tensor, h: int, w: int, box, sigma: float = 0.5,
+                    with_owner: bool = False, with_height: bool = True, with_score: bool = True):
+    """Training label maps from character quadrilaterals on the device (csrc/labels.hip; the rule and the host oracle:
+    dataset/labels.py).  ``rows`` (B, K, 20) int32 quad rows and ``count`` (B,) int32 on the device, the (h, w) map, the
+    inclusive core ``box`` (``.up/.down/.left/.right`` or a 4-tuple in that order).  Returns ``(owner, mask, height, score)``,
+    each (B, CH, CW) cropped to the box - int32 ``index + 1`` (0 = none), and fp32 ``owner != 0``, the owner's height, ``exp(-a)``
+    of the owner - with None for an output that was not asked for.  One launch; never synchronises, so it can be captured
+    into a HIP graph."""
+    if rows.dim() != 3 or rows.shape[2] != 20:
+        raise ValueError(f'char_label_maps: rows must be (B, K, 20), got {tuple(rows.shape)}')
+    B, K, _ = rows.shape
+    if tuple(count.shape) != (B,):
+        raise ValueError(f'char_label_maps: count must be {(B,)}, got {tuple(count.shape)}')
+    for name, t in (('rows', rows), ('count', count)):
+        if t.dtype != torch.int32:
+            raise ValueError(f'char_label_maps: {name} must be int32, got {t.dtype}')
+    up, down, left, right = (int(v) for v in (box if isinstance(box, (tuple, list)) else
+                                              (box.up, box.down, box.left, box.right)))
+    h, w = int(h), int(w)
+    if h < 1 or w < 1:
+        raise ValueError(f'char_label_maps: empty map {(h, w)}')
+    if not (0 <= up <= down < h and 0 <= left <= right < w):
+        raise ValueError(f'char_label_maps: core box {(up, down, left, right)} outside the {(h, w)} map')
+    if B > 65535:
+        raise ValueError(f'char_label_maps: B = {B} above 65535')
+    if B * h * w >= 1 << 31:
+        raise ValueError(f'char_label_maps: B*h*w = {B * h * w} must stay below 2^31')
+    sigma = float(sigma)
+    if not (sigma > 0.0 and sigma < float('inf')):
+        raise ValueError(f'char_label_maps: sigma must be finite and positive, got {sigma}')
+    _require_cuda(rows, count)
+    if rows.device != count.device:
+        raise ValueError(f'char_label_maps: rows are on {rows.device}, count on {count.device}')
+    rows, count = rows.contiguous(), count.contiguous()
+    CH, CW, dev = down - up + 1, right - left + 1, rows.device
+    new = lambda want, dtype: torch.empty((B, CH, CW), dtype=dtype, device=dev) if want else None
+    owner, mask = new(with_owner, torch.int32), new(True, _FLOAT)
+    height, score = new(with_height, _FLOAT), new(with_score, _FLOAT)
+    if B:
+        check(lib.vkas_char_label_maps(_p(rows), _p(count), B, K, h, w, up, left, CH, CW, 1.0 / (2.0 * sigma * sigma),
+                                       _p(owner), _p(mask), _p(height), _p(score), _stream()), 'char_label_maps')
+    return owner, mask, height, score
+
+
 def text_regions(mask: torch.Tensor, height: torch.Tensor, max_regions: int):
     """Text regions of the rough maps and the median character height of each (the step between the two passes,
     inferencing/adaptive_scaling.py:190-279 restated on pixels, csrc/regions.hip).  mask (B,H,W) uint8 and height (B,H,W)
