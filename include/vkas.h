@@ -307,10 +307,15 @@ int vkas_resize_bwd_ws(const void* dy, long lddy, void* dx, long lddx, float* ws
 int vkas_upconv_adj(const void* dz, long lddz, void* E, int B, int h, int w, int N, int dtype, void* stream);
 /* the same E (bit for bit), and out[n] (+)= the column sums of dz over all B * 2h * 2w rows - what vkas_colsum delivers - from
  * the values the kernel loads anyway.  N <= 2048; ws: vkas_upconv_adj_colsum_ws_bytes of per-workgroup partial rows; fixed
- * summation order. */
+ * summation order.  A thread walks down the source rows of one segment of an image with the horizontal partial sums of its six
+ * window rows in registers, so each dz row is loaded once per column instead of three times. */
 size_t vkas_upconv_adj_colsum_ws_bytes(int B, int h, int w, int N);
 int vkas_upconv_adj_colsum(const void* dz, long lddz, void* E, int B, int h, int w, int N, float* out, int accumulate, float* ws,
                            size_t ws_bytes, int dtype, void* stream);
+/* the same with the segment length in source rows given: 0 = the rule of the plain entry, longer than the image = one segment.
+ * The results do not depend on it (E bit for bit; the column sums up to the order of the fp32 additions). */
+int vkas_upconv_adj_colsum_seg(const void* dz, long lddz, void* E, int B, int h, int w, int N, float* out, int accumulate,
+                               float* ws, size_t ws_bytes, int dtype, void* stream, int seg_rows);
 /* gE (9 N, Cp) fp32, row k * N + n [the weight-gradient GEMM of E against x] added onto the packed gradient of the forward
  * taps: gwp (N, 3, 3, Cp)[n][8 - k][c] += gE[k * N + n][c] */
 int vkas_upconv_adj_unpack_wgrad(const float* gE, float* gwp, int N, int Cp, void* stream);

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Time the E pass of the dense heads' backward alone, through the C ABI, at the two shapes of the benchmark (B = 8,
-h = w = 256; N = 400 rough pass, N = 200 precise probability head): vkas_upconv_adj, vkas_colsum over the same dz, and
+h = w = 256; N = 384 rough pass, N = 192 precise probability head): vkas_upconv_adj, vkas_colsum over the same dz, and
 vkas_upconv_adj_colsum, which delivers both.  Milliseconds per launch: median of 5 rounds of 10 launches, and the spread
-(max - min) of the rounds.  VKAS_LIB_PATH selects a variant build."""
+(max - min) of the rounds.  VKAS_LIB_PATH selects a variant build.  Arguments, if any, are segment lengths: the row walk of
+vkas_upconv_adj_colsum_seg is timed at each of them as well (the plain entry chooses its own, csrc/upconv_adj.hip)."""
 import ctypes
 import os
 import sys
@@ -36,7 +37,7 @@ def p(t):
 
 B, h, w = 8, 256, 256
 g = torch.Generator(device='cuda').manual_seed(0)
-for N in (400, 200):
+for N in (384, 192):
     M = B * 4 * h * w
     dz = torch.randn((M, N), generator=g, device='cuda').bfloat16()
     E = torch.empty((B * h * w, 9 * N), dtype=torch.bfloat16, device='cuda')
@@ -62,4 +63,8 @@ for N in (400, 200):
                                                                                      if has_cs else ()):
         ms, spread = timed(fn)
         print(f'N={N:4d} {name:18s} {ms:7.3f} ms  spread {spread:6.3f} ms  {nbytes / ms / 1e9:5.2f} TB/s', flush=True)
+    for seg in [int(a) for a in sys.argv[1:]]:
+        ms, spread = timed(lambda: lib.vkas_upconv_adj_colsum_seg(p(dz), N, p(E), B, h, w, N, p(out), 1, p(ws2), nb2, _lib.BF16, st,
+                                                                  seg))
+        print(f'N={N:4d} seg_rows {seg:9d} {ms:7.3f} ms  spread {spread:6.3f} ms  {3.25 * e / ms / 1e9:5.2f} TB/s', flush=True)
     del dz, E

@@ -150,6 +150,7 @@ _SIGS = {
     'vkas_upconv_adj': (c_int, [_P, c_long, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     'vkas_upconv_adj_colsum_ws_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
     'vkas_upconv_adj_colsum': (c_int, [_P, c_long, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, c_size_t, c_int, _P]),
+    'vkas_upconv_adj_colsum_seg': (c_int, [_P, c_long, _P, c_int, c_int, c_int, c_int, _P, c_int, _P, c_size_t, c_int, _P, c_int]),
     'vkas_upconv_adj_unpack_wgrad': (c_int, [_P, _P, c_int, c_int, _P]),
     'vkas_adaptive_avgpool_fwd':(c_int, [_P, c_long, _P, c_long, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     'vkas_adaptive_avgpool_bwd': (c_int, [_P, c_long, _P, c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),

@@ -36,12 +36,10 @@ __device__ __forceinline__ void ut_weights(int i, int n, float* w) {
   w[3] = i == n - 1 ? 0.f : 0.25f;
 }
 
-// One (source pixel, 8-channel vector) pair: E's nine vectors from the 6 x 6 window of dz.  CS: also add the centre 2 x 2 block
-// (upsampled pixels 2i, 2i+1 x 2j, 2j+1: every upsampled pixel is in exactly one pair's centre block) onto the thread's own
-// sums cs[k * 256], row-major (in LDS: the kernel has no registers to spare).
-template <typename T, bool CS>
+// One (source pixel, 8-channel vector) pair: E's nine vectors from the 6 x 6 window of dz.
+template <typename T>
 __device__ __forceinline__ void upconv_adj_pair(const T* __restrict__ dz, long lddz, T* __restrict__ E, int h, int w, int nvec,
-                                                int b, int i, int j, int v, float* cs) {
+                                                int b, int i, int j, int v) {
   const int H2 = 2 * h, W2 = 2 * w;
   float wy[4], wx[4];
   ut_weights(i, h, wy);
@@ -68,17 +66,9 @@ __device__ __forceinline__ void upconv_adj_pair(const T* __restrict__ dz, long l
     const bool yok = Y >= 0 && Y < H2;
     const int yc = Y < 0 ? 0 : (Y >= H2 ? H2 - 1 : Y);
     Raw8<T> raw[6];  // the row's six requests first, conversions afterwards
-    if constexpr (CS) {
-      // a row base that is the same in every lane plus six 32-bit element offsets that serve all six rows (the host
-      // checks that a row of dz stays below 2^31 elements): fewer address registers than six 64-bit pointers per row
-      const T* rowb = dz + ((long)b * H2 + yc) * W2 * lddz;
+    const T* rowp = db + (long)yc * W2 * lddz;
 #pragma unroll
-      for (int c = 0; c < 6; ++c) raw[c].load(rowb + (unsigned)(xc[c] * (int)lddz + v * 8));
-    } else {
-      const T* rowp = db + (long)yc * W2 * lddz;
-#pragma unroll
-      for (int c = 0; c < 6; ++c) raw[c].load(rowp + (long)xc[c] * lddz);
-    }
+    for (int c = 0; c < 6; ++c) raw[c].load(rowp + (long)xc[c] * lddz);
     float hs[3][8];
 #pragma unroll
     for (int kx = 0; kx < 3; ++kx)
@@ -89,10 +79,6 @@ __device__ __forceinline__ void upconv_adj_pair(const T* __restrict__ dz, long l
       raw[c].keep_if(yok && xok[c]);
       float t[8];
       raw[c].unpack(t);
-      if (CS && (r == 2 || r == 3) && (c == 2 || c == 3)) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) cs[k * 256] += t[k];
-      }
 #pragma unroll
       for (int kx = 0; kx < 3; ++kx) {
         const int a = c - kx;  // window column c is destination 2j-1+a moved by tap kx
@@ -129,28 +115,174 @@ __global__ __launch_bounds__(256) void upconv_adj_kernel(const T* __restrict__ d
   if (j >= w) return;
   const int row = xcd_row(blockIdx.x, gridDim.x);
   const int b = row / h;
-  upconv_adj_pair<T, false>(dz, lddz, E, h, w, nvec, b, row - b * h, j, v, nullptr);
+  upconv_adj_pair<T>(dz, lddz, E, h, w, nvec, b, row - b * h, j, v);
 }
 
-// The same E, and the column sums of dz on the way.  grid.x = B*h source rows; workgroup (x, y) takes the chunks y, y +
-// gridDim.y, ... of its row, a chunk being ppc = 256 / nvec whole pixels (nvec <= 256), so that a thread keeps its vector v
-// and adds its centre blocks onto its own eight sums in LDS (red[k * 256 + thread]), chunk after chunk.  The workgroup's threads of
-// one v are then summed in thread order by the first of them: partial[x * gridDim.y + y][v * 8 ..], a fixed order throughout.
+// ---- the same E by walking down the rows, and the column sums of dz on the way ----
+// Source rows i and i + 1 share four of their six window rows, and a window row's partial sums hs depend on the column
+// alone.  So a thread keeps its (j, v), walks down the source rows i0 .. i1-1 of one image segment with the partial sums
+// of the six window rows in registers (a ring of six slots, two replaced per step), and per source row loads the two new dz
+// rows only: 12 loads and two x passes instead of 36 and six.  The y pass is the fmaf chain of upconv_adj_pair over the four
+// window rows of each ky in ascending order, from zero: the same bits.
+
+// The x pass of one window row: its six vectors as loaded -> the three horizontal partial sums hs[kx], an fmaf chain over the
+// window columns in ascending order, as in upconv_adj_pair; a pixel outside the map enters as zero (by selects: keep_if
+// compiles to a branch per vector here, which costs the walk registers).  centre: also add window columns 2 and 3 (upsampled
+// pixels 2j, 2j+1) onto cs.
+template <typename T>
+__device__ __forceinline__ void upconv_adj_x_pass(Raw8<T>* raw, bool yok, const bool* xok, const float* wx, float (*hs)[8],
+                                                  bool centre, float* cs) {
+#pragma unroll
+  for (int kx = 0; kx < 3; ++kx)
+#pragma unroll
+    for (int k = 0; k < 8; ++k) hs[kx][k] = 0.f;
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    raw[c].a = (yok && xok[c]) ? raw[c].a : decltype(raw[c].a){};
+    float t[8];
+    raw[c].unpack(t);
+    if (centre && (c == 2 || c == 3)) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) cs[k] += t[k];
+    }
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx) {
+      const int a = c - kx;  // window column c is destination 2j-1+a moved by tap kx
+      if (a < 0 || a > 3) continue;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) hs[kx][k] = fmaf(wx[a], t[k], hs[kx][k]);
+    }
+  }
+}
+
+// the six window columns 2j-2 .. 2j+3 of source column j: inside the map?, and clamped
+__device__ __forceinline__ void window_cols(int j, int W2, bool* xok, int* xc) {
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    const int X = 2 * j - 2 + c;
+    xok[c] = X >= 0 && X < W2;
+    xc[c] = X < 0 ? 0 : (X >= W2 ? W2 - 1 : X);
+  }
+}
+
+// dz row Y (clamped into the map: always readable) at one thread's six window columns: a row base that is the same in every
+// lane plus six 32-bit byte offsets (the host checks that a row of dz stays below 2^31 elements)
+template <typename T>
+__device__ __forceinline__ void upconv_adj_load_row(Raw8<T>* raw, const T* img, long rowstride, int Y, int H2, const unsigned* off) {
+  const char* rowb = reinterpret_cast<const char*>(img + (long)(Y < 0 ? 0 : (Y >= H2 ? H2 - 1 : Y)) * rowstride);
+#pragma unroll
+  for (int c = 0; c < 6; ++c) raw[c].load(reinterpret_cast<const T*>(rowb + off[c]));
+}
+
+// two window rows as loaded -> their partial sums hs0, hs1; where sum is set their pixels 2j, 2j+1, added up in registers
+// first, go onto the thread's column sums cs[k * 256] in LDS
+template <typename T>
+__device__ __forceinline__ void upconv_adj_x_pass2(Raw8<T>* raw, bool yok, const bool* xok, const float* wx, float (*hs0)[8],
+                                                   float (*hs1)[8], bool sum, float* cs) {
+  float rs[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) rs[k] = 0.f;
+  upconv_adj_x_pass<T>(raw, yok, xok, wx, hs0, sum, rs);
+  upconv_adj_x_pass<T>(raw + 6, yok, xok, wx, hs1, sum, rs);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) cs[k * 256] += rs[k];
+}
+
+// One step of the walk, for source row i with the window's rows 0 .. 5 in slots (2 PH + r) % 6 and raw holding rows 4, 5
+// (dz rows 2i+2, 2i+3), which go to the column sums here: every dz row is x-passed as a row 4 or 5 by exactly one step of
+// exactly one segment (rows 0 and 1 of an image: by the warm-up of its first segment), so every upsampled pixel is added
+// once.  The next step's two rows are requested ahead of the y pass, the second of them once ky = 0 is done and window row 0
+// is dead (that keeps the kernel inside 256 registers); after a segment's last step they are not used.
+template <typename T, int PH>
+__device__ __forceinline__ void upconv_adj_step(Raw8<T>* raw, float (*hs)[3][8], const T* img, long rowstride, int h, int i,
+                                                const bool* xok, const float* wx, const unsigned* off, T* dst, long N, float* cs) {
+  upconv_adj_x_pass2<T>(raw, i + 1 < h, xok, wx, hs[(2 * PH + 4) % 6], hs[(2 * PH + 5) % 6], true, cs);
+  upconv_adj_load_row<T>(raw, img, rowstride, 2 * i + 4, 2 * h, off);
+  float wy[4];
+  ut_weights(i, h, wy);
+#pragma unroll
+  for (int ky = 0; ky < 3; ++ky) {
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx) {
+      float acc[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) acc[k] = 0.f;
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc[k] = fmaf(wy[a], hs[(2 * PH + ky + a) % 6][kx][k], acc[k]);
+      store8(dst + (ky * 3 + kx) * N, acc);
+    }
+    if (ky == 0) upconv_adj_load_row<T>(raw + 6, img, rowstride, 2 * i + 5, 2 * h, off);
+  }
+}
+
+// source rows i0 .. i1-1 of column j, vector v, image b.  The warm-up builds window rows 0 .. 3 of source row i0 without storing.
+template <typename T>
+__device__ __forceinline__ void upconv_adj_walk(const T* __restrict__ dz, long lddz, T* __restrict__ E, int h, int w, int nvec,
+                                                int b, int i0, int i1, int j, int v, float* cs) {
+  const int H2 = 2 * h, W2 = 2 * w;
+  float wx[4];
+  ut_weights(j, w, wx);
+  int xc[6];
+  bool xok[6];
+  window_cols(j, W2, xok, xc);
+  unsigned off[6];
+#pragma unroll
+  for (int c = 0; c < 6; ++c) off[c] = (unsigned)(xc[c] * (int)lddz + v * 8) * (unsigned)sizeof(T);
+  const long rowstride = (long)W2 * lddz, N = (long)nvec * 8, dstep = (long)w * 9 * N;
+  const T* img = dz + (long)b * H2 * rowstride;
+  T* dst = E + (((long)b * h + i0) * w + j) * (9 * N) + v * 8;
+  float hs[6][3][8];
+  Raw8<T> raw[12];
+  upconv_adj_load_row<T>(raw, img, rowstride, 2 * i0 - 2, H2, off);
+  upconv_adj_load_row<T>(raw + 6, img, rowstride, 2 * i0 - 1, H2, off);
+  upconv_adj_x_pass2<T>(raw, i0 > 0, xok, wx, hs[0], hs[1], false, cs);
+  upconv_adj_load_row<T>(raw, img, rowstride, 2 * i0, H2, off);
+  upconv_adj_load_row<T>(raw + 6, img, rowstride, 2 * i0 + 1, H2, off);
+  upconv_adj_x_pass2<T>(raw, true, xok, wx, hs[2], hs[3], i0 == 0, cs);
+  upconv_adj_load_row<T>(raw, img, rowstride, 2 * i0 + 2, H2, off);
+  upconv_adj_load_row<T>(raw + 6, img, rowstride, 2 * i0 + 3, H2, off);
+  for (int i = i0;;) {  // three steps: every slot index is static
+    upconv_adj_step<T, 0>(raw, hs, img, rowstride, h, i, xok, wx, off, dst, N, cs);
+    dst += dstep;
+    if (++i == i1) break;
+    upconv_adj_step<T, 1>(raw, hs, img, rowstride, h, i, xok, wx, off, dst, N, cs);
+    dst += dstep;
+    if (++i == i1) break;
+    upconv_adj_step<T, 2>(raw, hs, img, rowstride, h, i, xok, wx, off, dst, N, cs);
+    dst += dstep;
+    if (++i == i1) break;
+  }
+}
+
+// An image is cut into nseg segments of seg_rows source rows (the last one may be shorter), a row of pixels into chunks of
+// ppc = 256 / nvec whole pixels (nvec <= 256).  Workgroup (b, s, y), dealt so that every XCD gets one contiguous run of them
+// (y fastest: neighbours in a row share window columns), walks segment s of image b for the chunks y, y + G, ...; a thread
+// keeps its vector v throughout and adds the dz rows it x-passes onto its own eight sums.  The workgroup's threads of
+// one v are then summed in thread order by the first of them into partial[(b * nseg + s) * G + y][v * 8 ..]: a fixed order.
 template <typename T>
 __global__ __launch_bounds__(256, 2) void upconv_adj_colsum_kernel(const T* __restrict__ dz, long lddz, T* __restrict__ E, int h,
-                                                                int w, int nvec, float* __restrict__ partial) {
+                                                                int w, int nvec, int seg_rows, int nseg, int G,
+                                                                float* __restrict__ partial) {
   const int ppc = 256 / nvec;
   const int jl = threadIdx.x / nvec;
   const int v = threadIdx.x - jl * nvec;
-  const int row = xcd_row(blockIdx.x, gridDim.x);
-  const int b = __builtin_amdgcn_readfirstlane(row / h);  // the same in every lane: row addresses stay in scalar registers
-  const int i = row - b * h;
+  // the same in every lane: row addresses and the walk's bounds stay in scalar registers
+  const int work = __builtin_amdgcn_readfirstlane(xcd_row(blockIdx.x, gridDim.x));
+  const int bs = __builtin_amdgcn_readfirstlane(work / G);
+  const int y = work - bs * G;
+  const int b = __builtin_amdgcn_readfirstlane(bs / nseg);
+  const int i0 = (bs - b * nseg) * seg_rows;
+  const int i1 = i0 + seg_rows < h ? i0 + seg_rows : h;
   __shared__ float red[8 * 256];  // [k][thread]
 #pragma unroll
   for (int k = 0; k < 8; ++k) red[k * 256 + threadIdx.x] = 0.f;
   if (jl < ppc) {
-    for (int j = blockIdx.y * ppc + jl; j < w; j += gridDim.y * ppc)
-      upconv_adj_pair<T, true>(dz, lddz, E, h, w, nvec, b, i, j, v, red + threadIdx.x);
+    for (int c = y; c * ppc < w; c += G) {  // the chunk is the same in every lane: nothing per lane is carried from walk to walk
+      const int j = c * ppc + jl;
+      if (j < w) upconv_adj_walk<T>(dz, lddz, E, h, w, nvec, b, i0, i1, j, v, red + threadIdx.x);
+    }
   }
   __syncthreads();
   if (jl == 0) {
@@ -160,7 +292,7 @@ __global__ __launch_bounds__(256, 2) void upconv_adj_colsum_kernel(const T* __re
     for (int r = 1; r < ppc; ++r)
 #pragma unroll
       for (int k = 0; k < 8; ++k) cs[k] += red[k * 256 + r * nvec + v];
-    store8(partial + ((long)blockIdx.x * gridDim.y + blockIdx.y) * ((long)nvec * 8) + v * 8, cs);
+    store8(partial + (long)work * ((long)nvec * 8) + v * 8, cs);
   }
 }
 
@@ -201,13 +333,63 @@ extern "C" int vkas_upconv_adj(const void* dz, long lddz, void* E, int B, int h,
 }
 
 namespace {
-// workgroups per source row of the column-sum variant: as many as keep the partial rows near 4096 (B*h = 2048 rows of the
-// benchmark's passes: 2), at most one per chunk
+// partial rows of the column sums per source row: as many as keep them near 4096 in all (B*h = 2048 rows of the benchmark's
+// passes: 2), at most one per chunk.  The workspace holds B * h * cs_groups rows; a launch uses B * nseg * G of them.
+static inline long cs_chunks(int w, int N) { return vkas_cdiv(w, 256 / (N / 8)); }
 static inline long cs_groups(int B, int h, int w, int N) {
-  const long chunks = vkas_cdiv(w, 256 / (N / 8));
+  const long chunks = cs_chunks(w, N);
   long g = 4096 / ((long)B * h);
   g = g < 1 ? 1 : g;
   return g < chunks ? g : chunks;
+}
+// workgroups per (image, segment): one per chunk where the workspace has the rows for it
+static inline long cs_seg_groups(int B, int h, int w, int N, long nseg) {
+  const long chunks = cs_chunks(w, N), room = (long)h * cs_groups(B, h, w, N) / nseg;
+  return room < chunks ? room : chunks;
+}
+// The segment length of the plain entry.  Two 256-thread workgroups fit a CU (two waves per SIMD), 512 on the MI355X's 256
+// CUs, and all workgroups of a launch take about the same time, so a launch runs in ceil(workgroups / 512) rounds of
+// (walks per workgroup) * (seg_rows + 2) row steps each - the warm-up of a walk loads and x-passes four rows, two steps'
+// worth.  Take the length with the fewest row steps among those that fill every CU twice (if any does); ties: the longer.
+static inline int cs_seg_rows(int B, int h, int w, int N) {
+  const long chunks = cs_chunks(w, N), slots = 2 * 256;
+  long best = h, best_cost = -1;
+  bool best_full = false;
+  for (long seg = h; seg >= 1; --seg) {
+    const long nseg = vkas_cdiv(h, seg);
+    if (vkas_cdiv(h, nseg) != seg) continue;  // the same cut with a shorter last segment
+    const long G = cs_seg_groups(B, h, w, N, nseg), wgs = (long)B * nseg * G;
+    const long cost = vkas_cdiv(wgs, slots) * vkas_cdiv(chunks, G) * (seg + 2);
+    const bool full = wgs >= slots;
+    if (best_cost < 0 || (full && !best_full) || (full == best_full && cost < best_cost)) {
+      best = seg; best_cost = cost; best_full = full;
+    }
+  }
+  return (int)best;
+}
+
+static int colsum_seg(const char* who, const void* dz, long lddz, void* E, int B, int h, int w, int N, float* out, int accumulate,
+                      float* ws, size_t ws_bytes, int dtype, void* stream, int seg_rows) {
+  VKAS_CHECK(dz && E && out && ws && vkas_aligned16(dz) && vkas_aligned16(E) && vkas_aligned16(ws),
+             "%s: null/misaligned pointer", who);
+  VKAS_CHECK(B > 0 && h > 0 && w > 0 && (long)B * h < (1L << 31) && 2L * w * lddz < (1L << 31), "%s: bad spatial dims", who);
+  VKAS_CHECK(N > 0 && N % 8 == 0 && N <= 2048 && lddz >= N && lddz % 8 == 0, "%s: bad channels/stride (N=%d lddz=%ld)", who, N,
+             lddz);
+  VKAS_CHECK(dtype == VKAS_BF16 || dtype == VKAS_F16, "%s: 16-bit storage only", who);
+  VKAS_CHECK(ws_bytes >= vkas_upconv_adj_colsum_ws_bytes(B, h, w, N), "%s: workspace too small", who);
+  VKAS_CHECK(seg_rows >= 0, "%s: bad segment length %d", who, seg_rows);
+  if (seg_rows == 0) seg_rows = cs_seg_rows(B, h, w, N);
+  if (seg_rows > h) seg_rows = h;
+  const long nseg = vkas_cdiv(h, seg_rows), G = cs_seg_groups(B, h, w, N, nseg), P = (long)B * nseg * G;
+  hipStream_t st = vkas_stream(stream);
+  if (dtype == VKAS_BF16)
+    upconv_adj_colsum_kernel<bf16_t><<<(unsigned)P, 256, 0, st>>>((const bf16_t*)dz, lddz, (bf16_t*)E, h, w, N / 8, seg_rows,
+                                                                  (int)nseg, (int)G, ws);
+  else
+    upconv_adj_colsum_kernel<f16_t><<<(unsigned)P, 256, 0, st>>>((const f16_t*)dz, lddz, (f16_t*)E, h, w, N / 8, seg_rows,
+                                                                 (int)nseg, (int)G, ws);
+  VKAS_LAUNCH_CHECK(who);
+  return vkas_colreduce_finalize(ws, P, N, N, out, accumulate, st);
 }
 }  // namespace
 
@@ -220,23 +402,13 @@ extern "C" size_t vkas_upconv_adj_colsum_ws_bytes(int B, int h, int w, int N) {
 // ws, summed by the finalize kernel of vkas_colsum.  Fixed summation order: two launches give the same bits.
 extern "C" int vkas_upconv_adj_colsum(const void* dz, long lddz, void* E, int B, int h, int w, int N, float* out, int accumulate,
                                       float* ws, size_t ws_bytes, int dtype, void* stream) {
-  VKAS_CHECK(dz && E && out && ws && vkas_aligned16(dz) && vkas_aligned16(E) && vkas_aligned16(ws),
-             "vkas_upconv_adj_colsum: null/misaligned pointer");
-  VKAS_CHECK(B > 0 && h > 0 && w > 0 && (long)B * h < (1L << 31) && 2L * w * lddz < (1L << 31),
-             "vkas_upconv_adj_colsum: bad spatial dims");
-  VKAS_CHECK(N > 0 && N % 8 == 0 && N <= 2048 && lddz >= N && lddz % 8 == 0,
-             "vkas_upconv_adj_colsum: bad channels/stride (N=%d lddz=%ld)", N, lddz);
-  VKAS_CHECK(dtype == VKAS_BF16 || dtype == VKAS_F16, "vkas_upconv_adj_colsum: 16-bit storage only");
-  VKAS_CHECK(ws_bytes >= vkas_upconv_adj_colsum_ws_bytes(B, h, w, N), "vkas_upconv_adj_colsum: workspace too small");
-  const long G = cs_groups(B, h, w, N);
-  dim3 grid((unsigned)((long)B * h), (unsigned)G);
-  hipStream_t st = vkas_stream(stream);
-  if (dtype == VKAS_BF16)
-    upconv_adj_colsum_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)dz, lddz, (bf16_t*)E, h, w, N / 8, ws);
-  else
-    upconv_adj_colsum_kernel<f16_t><<<grid, 256, 0, st>>>((const f16_t*)dz, lddz, (f16_t*)E, h, w, N / 8, ws);
-  VKAS_LAUNCH_CHECK("upconv_adj_colsum");
-  return vkas_colreduce_finalize(ws, (long)B * h * G, N, N, out, accumulate, st);
+  return colsum_seg("vkas_upconv_adj_colsum", dz, lddz, E, B, h, w, N, out, accumulate, ws, ws_bytes, dtype, stream, 0);
+}
+
+// the same with the segment length given (0: the plain entry's rule; longer than the image: one segment)
+extern "C" int vkas_upconv_adj_colsum_seg(const void* dz, long lddz, void* E, int B, int h, int w, int N, float* out,
+                                          int accumulate, float* ws, size_t ws_bytes, int dtype, void* stream, int seg_rows) {
+  return colsum_seg("vkas_upconv_adj_colsum_seg", dz, lddz, E, B, h, w, N, out, accumulate, ws, ws_bytes, dtype, stream, seg_rows);
 }
 
 extern "C" int vkas_upconv_adj_unpack_wgrad(const float* gE, float* gwp, int N, int Cp, void* stream) {
