@@ -520,6 +520,27 @@ int vkas_char_polygons(const float* prob, const float* offset, const float* angl
  * 16-byte aligned, scalar stores otherwise. */
 int vkas_char_label_maps(const int* rows, const int* count, int B, int K, int h, int w, int up, int left, int CH, int CW,
                          float k, int* owner, float* mask, float* height, float* score, void* stream);
+/* Matching predicted character quadrilaterals to annotated ones by IoU (inferencing/evaluation.py holds the rule - this
+ * project's own - and the host oracles quad_iou_host / match_quads_host).  gt_rows (B,M,16) and pred_rows (B,N,16) int32, one
+ * row per quad: 8 Q4 corners (y, x) of up-left, up-right, down-right, down-left; the inclusive Q4 box (y0, x0, y1, x1); twice
+ * the area in Q4^2 as int64 (low word first); valid; zero.  gt_count, pred_count (B) are clamped to [0, M] / [0, N] on the
+ * device.  A pair takes part iff both rows are valid and their boxes overlap (inclusive); its IoU is the Sutherland-Hodgman
+ * clip of the pred against the gt's edges in binary64, every operation rounded once (no fma); pairs with iou >= iou_thr are
+ * the candidates, matched one to one by the greedy rule (iou descending, gt ascending, pred ascending), computed as
+ * mutual-best rounds.  Outputs: gt_match (B,M) int32 = the pred index or -1; pred_match (B,N) int32; gt_iou (B,M) binary64,
+ * 0 where unmatched; stats (B,6) int64 = tp, n_gt, n_pred (valid rows within the count), pairs, candidates, status; rounds (B)
+ * int32, may be NULL = the rounds that took an edge.  An image with more than max_pairs candidates keeps its true pairs and
+ * candidates, and gets status = 1, every match -1, tp = 0 and rounds = 0: never a partial result.  Four launches on one
+ * stream; integer atomics in LDS only, no allocation, no synchronisation, every output element and every workspace word that
+ * is read is written by the call's own kernels: capture-safe and bit-identical from run to run.  Counts are clamped, ring
+ * stores bounded by 8 vertices and candidate stores by max_pairs: no table content makes a kernel touch memory outside its
+ * buffers.  B in 0..65535, M and N in 1..8192 (beyond: an error, not a clamp), max_pairs >= 0, B*max_pairs < 2^31, iou_thr in
+ * (0, 1]; tables and workspace 16-byte aligned, workspace at least vkas_quad_match_workspace_bytes (which returns -1 on bad
+ * arguments). */
+long long vkas_quad_match_workspace_bytes(int B, int M, int N, int max_pairs);
+int vkas_quad_match(const int* gt_rows, const int* gt_count, const int* pred_rows, const int* pred_count, int B, int M, int N,
+                    double iou_thr, int max_pairs, void* workspace, size_t workspace_bytes, int* gt_match, int* pred_match,
+                    double* gt_iou, long long* stats, int* rounds, void* stream);
 /* Text regions of the rough maps (the step between the passes, :190-279, restated on pixels).  mask (B,H,W) uint8 and height
  * (B,H,W) fp32 as vkas_rough_postprocess writes them.  A region is an 8-connected component of mask != 0; the regions of each
  * image are numbered 1..N by their first pixel in row-major order.  Outputs: count (B) = the true N of each image; labels

@@ -1,0 +1,497 @@
+// Matching predicted character quadrilaterals to annotated ones by IoU (inferencing/evaluation.py holds the rule and the host
+// oracles quad_iou_host / match_quads_host; the rule is this project's own).  rows (B, K, 16) int32: Q4 corners (8), the
+// inclusive Q4 box (4), twice the area as int64 (2), valid, zero.  Four launches on one stream:
+//
+//   qm_pair_kernel<false>  a 128-thread workgroup owns a 64 gt x 64 pred tile of one image.  The boxes and valid words of its
+//                          128 rows go to LDS; wave w box-tests gts [32w, 32w + 32) against pred = lane and appends the
+//                          overlapping valid pairs to its LDS list at the ballot's prefix count (a list is bounded by the
+//                          tile: no overflow path).  A tile without a pair - most tiles of a page - ends there.  Otherwise
+//                          the corners follow and all threads take pairs from the two lists, so the clip is balanced
+//                          whatever the tile holds.  A pair at or above iou_thr sets bit pj of the tile's 64-bit word of its
+//                          gt (LDS atomic OR: integer, order-free).  Out: the tile's words and its pair count.
+//   qm_scan_kernel         one workgroup per image: per gt the prefix of the words' popcounts over the pred tiles, then the
+//                          exclusive scan over the gts = the CSR row offsets; n_gt, n_pred, pairs, candidates, status.
+//   qm_pair_kernel<true>   the same tile body with the stored words in place of the box test: only candidates are clipped
+//                          again (same code, same bits), each stored at  row offset + tile prefix + popcount of the lower
+//                          bits: no slot atomics, pred ascending within a gt.  A tile whose words are all zero ends on
+//                          them, and an image with status set is skipped.
+//   qm_match_kernel        one workgroup per image, mutual-best rounds on integer atomicMax / atomicMin in LDS.
+//
+// The clip is Sutherland-Hodgman in binary64, every operation rounded once (qm_* helpers under contract(off): see labels.hip
+// for why __dmul_rn alone is not enough).  The two 8-vertex rings are indexed dynamically, so they live in per-thread LDS
+// slots, [ring][vertex][coordinate][thread]: consecutive lanes hit consecutive 8-byte banks, and nothing goes to scratch.
+// No float atomics, no allocation, no synchronisation: capture-safe and bit-identical from run to run.  Table reads are
+// bounded by the tables' K rows (a row beyond the clamped count is dropped after its load), ring stores by RING_MAX, candidate stores by max_pairs, tile stores by the padded tile grid
+// the workspace is sized for: no table content makes a kernel touch memory outside its buffers.
+#include "vkas_common.h"
+
+#include <limits.h>
+
+namespace {
+
+constexpr int QM_TILE = 64;                // gts and preds per tile
+constexpr int QM_THREADS = 128;            // pair pass
+constexpr int QM_WAVES = QM_THREADS / 64;
+constexpr int QM_LIST = QM_TILE * QM_TILE / QM_WAVES;  // list slots per wave
+constexpr int QM_RING = 8;                 // vertices per ring
+constexpr int QM_MAX = 8192;               // quads per image and side (the LDS state of the scan and matching passes)
+constexpr int QM_BLOCK = 1024;             // scan and matching passes
+constexpr int QM_STATS = 6;                // tp, n_gt, n_pred, pairs, candidates, status
+constexpr unsigned long long QM_TAKEN = ~0ull;
+
+#pragma clang fp contract(off)
+__device__ __forceinline__ double qm_mul(double a, double b) { return a * b; }
+__device__ __forceinline__ double qm_add(double a, double b) { return a + b; }
+__device__ __forceinline__ double qm_sub(double a, double b) { return a - b; }
+__device__ __forceinline__ double qm_div(double a, double b) { return a / b; }
+#pragma clang fp contract(fast)
+
+__device__ __forceinline__ int qm_clamp(int v, int hi) { return min(max(v, 0), hi); }
+
+// The rule's IoU of the LDS rows g and p (four int4 each).  ring: this thread's slots, element (r, k, c) at
+// ring[((r * QM_RING + k) * 2 + c) * QM_THREADS].
+__device__ __forceinline__ double qm_iou(const int4* g, const int4* p, double* ring) {
+#define QM_AT(r, k, c) ring[(((r) * QM_RING + (k)) * 2 + (c)) * QM_THREADS]
+  const int4 g01 = g[0], g23 = g[1], gb = g[2], ga = g[3];
+  const int4 p01 = p[0], p23 = p[1], pb = p[2], pa = p[3];
+  const long oy = min(gb.x, pb.x), ox = min(gb.y, pb.y);
+  const double gy[4] = {(double)(g01.x - oy), (double)(g01.z - oy), (double)(g23.x - oy), (double)(g23.z - oy)};
+  const double gx[4] = {(double)(g01.y - ox), (double)(g01.w - ox), (double)(g23.y - ox), (double)(g23.w - ox)};
+  QM_AT(0, 0, 0) = (double)(p01.x - oy);
+  QM_AT(0, 0, 1) = (double)(p01.y - ox);
+  QM_AT(0, 1, 0) = (double)(p01.z - oy);
+  QM_AT(0, 1, 1) = (double)(p01.w - ox);
+  QM_AT(0, 2, 0) = (double)(p23.x - oy);
+  QM_AT(0, 2, 1) = (double)(p23.y - ox);
+  QM_AT(0, 3, 0) = (double)(p23.z - oy);
+  QM_AT(0, 3, 1) = (double)(p23.w - ox);
+  int n = 4;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int src = e & 1, dst = src ^ 1;
+    const double ay = gy[e], ax = gx[e];
+    const double ey = qm_sub(gy[(e + 1) & 3], ay), ex = qm_sub(gx[(e + 1) & 3], ax);
+    int m = 0;
+    if (n > 0) {
+      const double fy = QM_AT(src, 0, 0), fx = QM_AT(src, 0, 1);
+      const double fd = qm_sub(qm_mul(ex, qm_sub(fy, ay)), qm_mul(ey, qm_sub(fx, ax)));
+      double vy = fy, vx = fx, dv = fd;
+      for (int k = 0; k < n; ++k) {
+        double wy = fy, wx = fx, dw = fd;
+        if (k + 1 < n) {
+          wy = QM_AT(src, k + 1, 0);
+          wx = QM_AT(src, k + 1, 1);
+          dw = qm_sub(qm_mul(ex, qm_sub(wy, ay)), qm_mul(ey, qm_sub(wx, ax)));
+        }
+        if (dv >= 0.0 && m < QM_RING) {
+          QM_AT(dst, m, 0) = vy;
+          QM_AT(dst, m, 1) = vx;
+          ++m;
+        }
+        if ((dv >= 0.0) != (dw >= 0.0) && m < QM_RING) {
+          const double t = qm_div(dv, qm_sub(dv, dw));
+          QM_AT(dst, m, 0) = qm_add(vy, qm_mul(t, qm_sub(wy, vy)));
+          QM_AT(dst, m, 1) = qm_add(vx, qm_mul(t, qm_sub(wx, vx)));
+          ++m;
+        }
+        vy = wy;
+        vx = wx;
+        dv = dw;
+      }
+    }
+    n = m;
+  }
+  double acc = 0.0;  // four clips: the result is in ring 0
+  if (n > 0) {
+    const double fy = QM_AT(0, 0, 0), fx = QM_AT(0, 0, 1);
+    double y0 = fy, x0 = fx;
+    for (int k = 0; k < n; ++k) {
+      double y1 = fy, x1 = fx;
+      if (k + 1 < n) {
+        y1 = QM_AT(0, k + 1, 0);
+        x1 = QM_AT(0, k + 1, 1);
+      }
+      acc = qm_add(acc, qm_sub(qm_mul(x0, y1), qm_mul(x1, y0)));
+      y0 = y1;
+      x0 = x1;
+    }
+  }
+#undef QM_AT
+  const double ag = (double)(long)(((unsigned long long)(unsigned)ga.y << 32) | (unsigned)ga.x);
+  const double ap = (double)(long)(((unsigned long long)(unsigned)pa.y << 32) | (unsigned)pa.x);
+  const double hi = ap < ag ? ap : ag;
+  double inter2 = acc;
+  if (inter2 > hi) inter2 = hi;
+  if (inter2 < 0.0) inter2 = 0.0;
+  const double den = qm_sub(qm_add(ag, ap), inter2);
+  return den > 0.0 ? qm_div(inter2, den) : 0.0;
+}
+
+// workspace: words (B, NT, Mp) u64, cand_iou (B, max_pairs) u64, tpre (B, NT, Mp) int, rowoff (B, Mp + 1) int,
+// tile_pairs (B, MT * NT) int, cand_pred (B, max_pairs) int
+struct QmLayout {
+  size_t words, cand_iou, tpre, rowoff, tile_pairs, cand_pred, bytes;
+  int MT, NT, Mp;
+};
+
+template <bool FILL>
+__global__ __launch_bounds__(QM_THREADS) void qm_pair_kernel(const int* __restrict__ gt_rows, const int* __restrict__ gt_count,
+                                                              const int* __restrict__ pred_rows,
+                                                              const int* __restrict__ pred_count, int M, int N, int Mp,
+                                                              int NT, double thr, unsigned long long* __restrict__ words,
+                                                              int* __restrict__ tpre, int* __restrict__ tile_pairs,
+                                                              const int* __restrict__ rowoff,
+                                                              const long long* __restrict__ stats, int* __restrict__ cand_pred,
+                                                              unsigned long long* __restrict__ cand_iou, int max_pairs) {
+  __shared__ int4 s_rows[2 * QM_TILE * 4];
+  __shared__ unsigned long long s_word[QM_TILE];
+  __shared__ unsigned short s_list[QM_WAVES * QM_LIST];
+  __shared__ int s_cnt[QM_WAVES];
+  __shared__ double s_ring[2 * QM_RING * 2 * QM_THREADS];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tn = blockIdx.x, tm = blockIdx.y, b = blockIdx.z;
+  const int g0 = tm * QM_TILE, p0 = tn * QM_TILE;
+  const long word_at = ((long)b * NT + tn) * Mp + g0;
+  // Most tiles of a page end early: the status, the counts, the words and (below) the rows are read at addresses that depend
+  // on no other load, so such a workgroup lives one load's latency.  Every early return is taken by the whole workgroup.
+  const long long status = FILL ? stats[(long)b * QM_STATS + 5] : 0;
+  const int ng = qm_clamp(gt_count[b], M), np = qm_clamp(pred_count[b], N);
+  if (FILL && status != 0) return;  // nothing of this image is stored
+  unsigned long long word = 0ull;
+  if (FILL && tid < QM_TILE) word = words[word_at + tid];
+  // a part of the 128 rows of the tile: 0, 1 = the corners, 2 = the box, 3 = area and valid; two loads per thread and half.
+  // The row index is clamped to the table; a row beyond the count becomes a zero row (valid = 0) after the load.
+  const auto stage = [&](int half) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int i = tid + k * QM_THREADS, row = i >> 1, part = 2 * half + (i & 1);
+      int4 v;
+      bool keep;
+      if (row < QM_TILE) {
+        v = reinterpret_cast<const int4*>(gt_rows)[((long)b * M + min(g0 + row, M - 1)) * 4 + part];
+        keep = g0 + row < ng;
+      } else {
+        v = reinterpret_cast<const int4*>(pred_rows)[((long)b * N + min(p0 + row - QM_TILE, N - 1)) * 4 + part];
+        keep = p0 + row - QM_TILE < np;
+      }
+      s_rows[row * 4 + part] = keep ? v : make_int4(0, 0, 0, 0);
+    }
+  };
+  if (tid < QM_TILE) s_word[tid] = word;
+  if (FILL) {  // most tiles of a page hold no candidate: they end here, on 512 bytes
+    __syncthreads();
+    if (__ballot(s_word[lane] != 0ull) == 0ull) return;
+  }
+  stage(1);  // the box test needs boxes and valid only; a tile without a pair ends on them
+  __syncthreads();
+
+  const int4 pbox = s_rows[(QM_TILE + lane) * 4 + 2];
+  const bool pvalid = s_rows[(QM_TILE + lane) * 4 + 3].z != 0;
+  int cnt = 0;
+  for (int s = 0; s < QM_TILE / QM_WAVES; ++s) {
+    const int gi = wave * (QM_TILE / QM_WAVES) + s;
+    bool hit;
+    if (FILL) {
+      hit = (s_word[gi] >> lane) & 1ull;
+    } else {
+      const int4 gbox = s_rows[gi * 4 + 2];
+      hit = pvalid && s_rows[gi * 4 + 3].z != 0 && gbox.x <= pbox.z && pbox.x <= gbox.z && gbox.y <= pbox.w &&
+            pbox.y <= gbox.w;
+    }
+    const unsigned long long bits = __ballot(hit);
+    if (hit) s_list[wave * QM_LIST + cnt + __popcll(bits & ((1ull << lane) - 1ull))] = (unsigned short)(gi * QM_TILE + lane);
+    cnt += __popcll(bits);  // <= 32 * 64 = QM_LIST
+  }
+  if (lane == 0) s_cnt[wave] = cnt;
+  __syncthreads();
+  const int c0 = s_cnt[0], total = c0 + s_cnt[1];
+  static_assert(QM_WAVES == 2, "the two lists are read as one");
+  if (total == 0) {  // the whole workgroup
+    if (!FILL) {
+      if (tid < QM_TILE) words[word_at + tid] = 0ull;
+      if (tid == 0) tile_pairs[((long)b * gridDim.y + tm) * NT + tn] = 0;
+    }
+    return;
+  }
+  stage(0);
+  __syncthreads();
+  for (int e = tid; e < total; e += QM_THREADS) {
+    const int q = e < c0 ? s_list[e] : s_list[QM_LIST + e - c0];
+    const int gi = q >> 6, pj = q & 63;
+    const double iou = qm_iou(s_rows + gi * 4, s_rows + (QM_TILE + pj) * 4, s_ring + tid);
+    if (!(iou >= thr)) continue;
+    if (FILL) {
+      const int g = g0 + gi;
+      const long slot = (long)rowoff[(long)b * (Mp + 1) + g] + tpre[word_at + gi] +
+                        __popcll(s_word[gi] & ((1ull << pj) - 1ull));
+      if (slot >= 0 && slot < max_pairs) {
+        cand_pred[(long)b * max_pairs + slot] = p0 + pj;
+        cand_iou[(long)b * max_pairs + slot] = (unsigned long long)__double_as_longlong(iou);
+      }
+    } else {
+      atomicOr(&s_word[gi], 1ull << pj);
+    }
+  }
+  if (!FILL) {
+    __syncthreads();
+    if (tid < QM_TILE) words[word_at + tid] = s_word[tid];
+    if (tid == 0) tile_pairs[((long)b * gridDim.y + tm) * NT + tn] = total;
+  }
+}
+
+__device__ __forceinline__ int qm_wave_sum_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(QM_BLOCK) void qm_scan_kernel(const int* __restrict__ gt_rows, const int* __restrict__ gt_count,
+                                                            const int* __restrict__ pred_rows,
+                                                            const int* __restrict__ pred_count, int M, int N, int Mp, int NT,
+                                                            int MT, const unsigned long long* __restrict__ words,
+                                                            int* __restrict__ tpre, const int* __restrict__ tile_pairs,
+                                                            int* __restrict__ rowoff, long long* __restrict__ stats,
+                                                            int max_pairs) {
+  __shared__ int s_cnt[QM_MAX];
+  __shared__ int s_wave[QM_BLOCK / 64];
+  __shared__ int s_sum[3];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, b = blockIdx.x;
+  const int ng = qm_clamp(gt_count[b], M), np = qm_clamp(pred_count[b], N);
+  if (t < 3) s_sum[t] = 0;
+  for (int g = t; g < Mp; g += QM_BLOCK) {  // Mp <= QM_MAX
+    int run = 0;
+#pragma unroll 8
+    for (int tn = 0; tn < NT; ++tn) {
+      const long at = ((long)b * NT + tn) * Mp + g;
+      tpre[at] = run;
+      run += __popcll(words[at]);
+    }
+    s_cnt[g] = run;
+  }
+  int n_gt = 0, n_pred = 0, pairs = 0;
+  for (int g = t; g < ng; g += QM_BLOCK) n_gt += gt_rows[((long)b * M + g) * 16 + 14] != 0;
+  for (int p = t; p < np; p += QM_BLOCK) n_pred += pred_rows[((long)b * N + p) * 16 + 14] != 0;
+  for (int i = t; i < MT * NT; i += QM_BLOCK) pairs += tile_pairs[(long)b * MT * NT + i];  // <= M * N <= 2^26
+  __syncthreads();
+  n_gt = qm_wave_sum_i(n_gt);
+  n_pred = qm_wave_sum_i(n_pred);
+  pairs = qm_wave_sum_i(pairs);
+  if (lane == 0) {
+    atomicAdd(&s_sum[0], n_gt);
+    atomicAdd(&s_sum[1], n_pred);
+    atomicAdd(&s_sum[2], pairs);
+  }
+  // exclusive scan of s_cnt: each thread owns a contiguous run of gts
+  const int seg = (Mp + QM_BLOCK - 1) / QM_BLOCK;
+  const int lo = min(Mp, t * seg), hi = min(Mp, lo + seg);
+  int own = 0;
+  for (int g = lo; g < hi; ++g) own += s_cnt[g];
+  int v = own;
+  for (int d = 1; d < 64; d <<= 1) {
+    const int u = __shfl_up(v, d);
+    if (lane >= d) v += u;
+  }
+  if (lane == 63) s_wave[wave] = v;
+  __syncthreads();
+  int run = v - own, all = 0;
+  for (int w = 0; w < QM_BLOCK / 64; ++w) {
+    if (w < wave) run += s_wave[w];
+    all += s_wave[w];
+  }
+  for (int g = lo; g < hi; ++g) {
+    rowoff[(long)b * (Mp + 1) + g] = run;
+    run += s_cnt[g];
+  }
+  if (t == 0) {
+    rowoff[(long)b * (Mp + 1) + Mp] = all;
+    long long* st = stats + (long)b * QM_STATS;
+    st[0] = 0;
+    st[1] = s_sum[0];
+    st[2] = s_sum[1];
+    st[3] = s_sum[2];
+    st[4] = all;
+    st[5] = all > max_pairs ? 1 : 0;
+  }
+}
+
+// Mutual-best rounds.  Thread t owns the gts t + 1024 k (k < 8: one taken bit each, in a register); per pred the LDS holds the
+// best iou bits offered this round (QM_TAKEN once the pred is matched: no offer exceeds it, no offer equals it) and the lowest
+// gt that offers them.  Integer max / min only: the result does not depend on arrival order.
+__global__ __launch_bounds__(QM_BLOCK) void qm_match_kernel(const int* __restrict__ gt_count, const int* __restrict__ pred_count,
+                                                             int M, int N, int Mp, const int* __restrict__ rowoff,
+                                                             const int* __restrict__ cand_pred,
+                                                             const unsigned long long* __restrict__ cand_iou, int max_pairs,
+                                                             int* __restrict__ gt_match, int* __restrict__ pred_match,
+                                                             double* __restrict__ gt_iou, long long* __restrict__ stats,
+                                                             int* __restrict__ rounds) {
+  extern __shared__ unsigned long long s_dyn[];
+  __shared__ int s_any, s_tp;
+  unsigned long long* best_iou = s_dyn;                  // N
+  int* best_gt = reinterpret_cast<int*>(s_dyn + N);      // N
+  const int t = threadIdx.x, b = blockIdx.x;
+  static_assert(QM_MAX <= QM_BLOCK * 32, "one taken bit per owned gt");
+  for (int g = t; g < M; g += QM_BLOCK) {
+    gt_match[(long)b * M + g] = -1;
+    gt_iou[(long)b * M + g] = 0.0;
+  }
+  for (int p = t; p < N; p += QM_BLOCK) {
+    pred_match[(long)b * N + p] = -1;
+    best_iou[p] = 0ull;
+  }
+  if (t == 0) s_tp = 0;
+  int done = 0;
+  if (stats[(long)b * QM_STATS + 5] == 0) {  // uniform over the workgroup; an overflowed image keeps every match at -1
+    const int ng = qm_clamp(gt_count[b], M);
+    const int* off = rowoff + (long)b * (Mp + 1);
+    const int* cp = cand_pred + (long)b * max_pairs;
+    const unsigned long long* cw = cand_iou + (long)b * max_pairs;
+    unsigned taken = 0;
+    const int cap = min(M, N) + 1;
+    for (int round = 0; round < cap; ++round) {
+      for (int p = t; p < N; p += QM_BLOCK) {
+        if (best_iou[p] != QM_TAKEN) best_iou[p] = 0ull;
+        best_gt[p] = INT_MAX;
+      }
+      if (t == 0) s_any = 0;
+      __syncthreads();
+      for (int g = t, k = 0; g < ng; g += QM_BLOCK, ++k) {  // every free gt offers its iou to its free candidates
+        if ((taken >> k) & 1u) continue;
+        const int lo = max(off[g], 0), hi = min(off[g + 1], max_pairs);
+        for (int i = lo; i < hi; ++i) {
+          const int p = cp[i];
+          if ((unsigned)p < (unsigned)N && best_iou[p] != QM_TAKEN) atomicMax(&best_iou[p], cw[i]);
+        }
+      }
+      __syncthreads();
+      for (int g = t, k = 0; g < ng; g += QM_BLOCK, ++k) {  // the gts that offered a pred's best: the lowest of them
+        if ((taken >> k) & 1u) continue;
+        const int lo = max(off[g], 0), hi = min(off[g + 1], max_pairs);
+        for (int i = lo; i < hi; ++i) {
+          const int p = cp[i];
+          if ((unsigned)p < (unsigned)N && best_iou[p] == cw[i]) atomicMin(&best_gt[p], g);
+        }
+      }
+      __syncthreads();
+      for (int g = t, k = 0; g < ng; g += QM_BLOCK, ++k) {  // a gt takes its own best if it is that pred's best
+        if ((taken >> k) & 1u) continue;
+        const int lo = max(off[g], 0), hi = min(off[g + 1], max_pairs);
+        unsigned long long bw = 0ull;
+        int bp = -1;
+        for (int i = lo; i < hi; ++i) {
+          const int p = cp[i];
+          if ((unsigned)p < (unsigned)N && best_iou[p] != QM_TAKEN && cw[i] > bw) {  // strictly: the lowest p of a tie
+            bw = cw[i];
+            bp = p;
+          }
+        }
+        if (bp >= 0 && best_gt[bp] == g) {
+          taken |= 1u << k;
+          gt_match[(long)b * M + g] = bp;
+          gt_iou[(long)b * M + g] = __longlong_as_double((long long)bw);
+          pred_match[(long)b * N + bp] = g;
+          best_gt[bp] = -1 - g;  // only this thread holds best_gt[bp] == g: marks the pred for the sweep below
+          atomicAdd(&s_tp, 1);
+          s_any = 1;
+        }
+      }
+      __syncthreads();
+      for (int p = t; p < N; p += QM_BLOCK)
+        if (best_gt[p] < 0) best_iou[p] = QM_TAKEN;
+      const int any = s_any;
+      __syncthreads();
+      if (!any) break;
+      ++done;
+    }
+  }
+  __syncthreads();
+  if (t == 0) {
+    stats[(long)b * QM_STATS + 0] = s_tp;
+    if (rounds) rounds[b] = done;
+  }
+}
+
+size_t qm_align(size_t v) { return (v + 255) & ~(size_t)255; }
+
+QmLayout qm_layout(int B, int M, int N, int max_pairs) {
+  QmLayout l;
+  l.MT = (int)vkas_cdiv(M, QM_TILE);
+  l.NT = (int)vkas_cdiv(N, QM_TILE);
+  l.Mp = l.MT * QM_TILE;
+  const size_t tiles = (size_t)B * l.NT * l.Mp;
+  l.words = 0;
+  l.cand_iou = qm_align(l.words + tiles * sizeof(unsigned long long));
+  l.tpre = qm_align(l.cand_iou + (size_t)B * max_pairs * sizeof(unsigned long long));
+  l.rowoff = qm_align(l.tpre + tiles * sizeof(int));
+  l.tile_pairs = qm_align(l.rowoff + (size_t)B * (l.Mp + 1) * sizeof(int));
+  l.cand_pred = qm_align(l.tile_pairs + (size_t)B * l.MT * l.NT * sizeof(int));
+  l.bytes = qm_align(l.cand_pred + (size_t)B * max_pairs * sizeof(int));
+  return l;
+}
+
+int qm_check_dims(const char* what, int B, int M, int N, int max_pairs) {
+  VKAS_CHECK(B >= 0 && B <= 65535, "%s: bad B=%d (0..65535)", what, B);
+  VKAS_CHECK(M >= 1 && M <= QM_MAX && N >= 1 && N <= QM_MAX, "%s: M=%d and N=%d must lie in 1..%d", what, M, N, QM_MAX);
+  VKAS_CHECK(max_pairs >= 0, "%s: max_pairs=%d must be >= 0", what, max_pairs);
+  VKAS_CHECK((long)B * max_pairs < (1L << 31), "%s: B*max_pairs = %ld must stay below 2^31", what, (long)B * max_pairs);
+  return VKAS_OK;
+}
+
+}  // namespace
+
+extern "C" long long vkas_quad_match_workspace_bytes(int B, int M, int N, int max_pairs) {
+  if (qm_check_dims("vkas_quad_match_workspace_bytes", B, M, N, max_pairs) != VKAS_OK) return -1;
+  return (long long)qm_layout(B, M, N, max_pairs).bytes;
+}
+
+extern "C" int vkas_quad_match(const int* gt_rows, const int* gt_count, const int* pred_rows, const int* pred_count, int B,
+                               int M, int N, double iou_thr, int max_pairs, void* workspace, size_t workspace_bytes,
+                               int* gt_match, int* pred_match, double* gt_iou, long long* stats, int* rounds,
+                               void* stream) {
+  const int rc = qm_check_dims("vkas_quad_match", B, M, N, max_pairs);
+  if (rc != VKAS_OK) return rc;
+  VKAS_CHECK(iou_thr > 0.0 && iou_thr <= 1.0, "vkas_quad_match: iou_thr = %g must lie in (0, 1]", iou_thr);
+  if (B == 0) return VKAS_OK;
+  VKAS_CHECK(gt_rows && gt_count && pred_rows && pred_count && workspace && gt_match && pred_match && gt_iou && stats,
+             "vkas_quad_match: null pointer");
+  VKAS_CHECK(vkas_aligned16(gt_rows) && vkas_aligned16(pred_rows) && vkas_aligned16(workspace),
+             "vkas_quad_match: the row tables and the workspace must be 16-byte aligned");
+  VKAS_CHECK((((uintptr_t)gt_iou) & 7u) == 0 && (((uintptr_t)stats) & 7u) == 0,
+             "vkas_quad_match: gt_iou and stats must be 8-byte aligned");
+  const QmLayout l = qm_layout(B, M, N, max_pairs);
+  VKAS_CHECK(workspace_bytes >= l.bytes, "vkas_quad_match: workspace of %zu bytes, %zu needed", workspace_bytes, l.bytes);
+  // the matching pass keeps 12 bytes per pred in LDS: above the default 64 KB the kernel is opted in, once
+  const size_t lds = (size_t)N * (sizeof(unsigned long long) + sizeof(int));
+  static size_t lds_allowed = 48 * 1024;
+  if (lds > lds_allowed) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(qm_match_kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)((size_t)QM_MAX * (sizeof(unsigned long long) + sizeof(int))));
+    if (e != hipSuccess) {
+      vkas_set_error("vkas_quad_match: %zu bytes of LDS for N = %d refused: %s", lds, N, hipGetErrorString(e));
+      return VKAS_E_LAUNCH;
+    }
+    lds_allowed = (size_t)QM_MAX * (sizeof(unsigned long long) + sizeof(int));
+  }
+  char* ws = static_cast<char*>(workspace);
+  unsigned long long* words = reinterpret_cast<unsigned long long*>(ws + l.words);
+  unsigned long long* cand_iou = reinterpret_cast<unsigned long long*>(ws + l.cand_iou);
+  int* tpre = reinterpret_cast<int*>(ws + l.tpre);
+  int* rowoff = reinterpret_cast<int*>(ws + l.rowoff);
+  int* tile_pairs = reinterpret_cast<int*>(ws + l.tile_pairs);
+  int* cand_pred = reinterpret_cast<int*>(ws + l.cand_pred);
+  hipStream_t s = vkas_stream(stream);
+  const dim3 grid((unsigned)l.NT, (unsigned)l.MT, (unsigned)B);
+  qm_pair_kernel<false><<<grid, QM_THREADS, 0, s>>>(gt_rows, gt_count, pred_rows, pred_count, M, N, l.Mp, l.NT, iou_thr,
+                                                     words, tpre, tile_pairs, rowoff, stats, cand_pred, cand_iou, max_pairs);
+  VKAS_LAUNCH_CHECK("quad_match pairs");
+  qm_scan_kernel<<<B, QM_BLOCK, 0, s>>>(gt_rows, gt_count, pred_rows, pred_count, M, N, l.Mp, l.NT, l.MT, words, tpre,
+                                        tile_pairs, rowoff, stats, max_pairs);
+  VKAS_LAUNCH_CHECK("quad_match scan");
+  qm_pair_kernel<true><<<grid, QM_THREADS, 0, s>>>(gt_rows, gt_count, pred_rows, pred_count, M, N, l.Mp, l.NT, iou_thr, words,
+                                                    tpre, tile_pairs, rowoff, stats, cand_pred, cand_iou, max_pairs);
+  VKAS_LAUNCH_CHECK("quad_match fill");
+  qm_match_kernel<<<B, QM_BLOCK, lds, s>>>(gt_count, pred_count, M, N, l.Mp, rowoff, cand_pred, cand_iou, max_pairs, gt_match,
+                                           pred_match, gt_iou, stats, rounds);
+  VKAS_LAUNCH_CHECK("quad_match rounds");
+  return VKAS_OK;
+}

@@ -15,4 +15,6 @@ from .regions import region_scales, text_regions_host
 from .packing import (SIDE_MAX, axis_weights, check_placements, pack_region_labels_host, region_crops, remap_polygons,
                       resample_host, stack_regions, check_warps, remap_polygons_affine, warp_host, warp_region_labels_host,
                       check_multi_rows, pack_region_labels_multi_host, resample_pack_multi_host, stack_regions_pages)
+from .evaluation import (DetectionScore, QuadMatchResult, evaluate_quads, evaluate_quads_host, evaluation_tables,
+                         match_quads_host, match_rows, quad_iou_host, result_quads)
 from .orient import (orient_regions, oriented_rects, region_directions, region_extents_host, region_moments_host, warp_row)

@@ -2343,6 +2343,61 @@ def char_label_maps(rows: torch.Tensor, count: torch.Tensor, h: int, w: int, box
     return owner, mask, height, score
 
 
+def match_quads(gt_rows: torch.Tensor, gt_count: torch.Tensor, pred_rows: torch.Tensor, pred_count: torch.Tensor,
+                iou_thr: float = 0.5, max_pairs: Optional[int] = None, rounds: Optional[torch.Tensor] = None):
+    """Predicted character quadrilaterals matched one to one to annotated ones by IoU on the device (csrc/quadmatch.hip; the
+    rule and the host oracles: inferencing/evaluation.py).  ``gt_rows`` (B, M, 16) / ``gt_count`` (B,) and ``pred_rows``
+    (B, N, 16) / ``pred_count`` (B,): int32 match rows (``inferencing.match_rows``) and counts on the device; M and N at most
+    8192.  ``max_pairs`` is the capacity for stored candidates (pairs with iou >= ``iou_thr``) per image, 4 * max(M, N) by
+    default.  Returns ``(gt_match, pred_match, gt_iou, stats)`` - (B, M) int32 pred index or -1, (B, N) int32 gt index or -1,
+    (B, M) float64 (0 where unmatched), (B, 6) int64 ``tp, n_gt, n_pred, pairs, candidates, status``.  An image with more
+    candidates than ``max_pairs`` keeps its true ``pairs`` and ``candidates`` and gets ``status = 1``, every match -1 and
+    ``tp = 0``.  ``rounds``, if given, is a (B,) int32 device tensor that receives the matching rounds of each image.  Four
+    launches; never synchronises, so it can be captured into a HIP graph."""
+    for name, t, other in (('gt', gt_rows, gt_count), ('pred', pred_rows, pred_count)):
+        if t.dim() != 3 or t.shape[2] != 16:
+            raise ValueError(f'match_quads: {name}_rows must be (B, K, 16), got {tuple(t.shape)}')
+        if tuple(other.shape) != (t.shape[0],):
+            raise ValueError(f'match_quads: {name}_count must be {(t.shape[0],)}, got {tuple(other.shape)}')
+        if t.dtype != torch.int32 or other.dtype != torch.int32:
+            raise ValueError(f'match_quads: {name}_rows and {name}_count must be int32, got {t.dtype} and {other.dtype}')
+    B, M, _ = gt_rows.shape
+    N = pred_rows.shape[1]
+    if pred_rows.shape[0] != B:
+        raise ValueError(f'match_quads: {B} images of annotations against {pred_rows.shape[0]} of predictions')
+    if not (1 <= M <= 8192 and 1 <= N <= 8192):
+        raise ValueError(f'match_quads: M = {M} and N = {N} must lie in 1..8192')
+    if B > 65535:
+        raise ValueError(f'match_quads: B = {B} above 65535')
+    iou_thr = float(iou_thr)
+    if not (iou_thr > 0.0 and iou_thr <= 1.0):
+        raise ValueError(f'match_quads: iou_thr must lie in (0, 1], got {iou_thr}')
+    max_pairs = 4 * max(M, N) if max_pairs is None else int(max_pairs)
+    if max_pairs < 0 or B * max_pairs >= 1 << 31:
+        raise ValueError(f'match_quads: max_pairs = {max_pairs} must be >= 0 and B*max_pairs below 2^31')
+    if rounds is not None and (tuple(rounds.shape) != (B,) or rounds.dtype != torch.int32 or not rounds.is_contiguous()):
+        raise ValueError(f'match_quads: rounds must be a contiguous ({B},) int32 tensor')
+    tensors = (gt_rows, gt_count, pred_rows, pred_count) + (() if rounds is None else (rounds,))
+    _require_cuda(*tensors)
+    if any(t.device != gt_rows.device for t in tensors):
+        raise ValueError('match_quads: all tensors must be on one device')
+    gt_rows, gt_count, pred_rows, pred_count = (t.contiguous() for t in (gt_rows, gt_count, pred_rows, pred_count))
+    dev = gt_rows.device
+    gt_match = torch.empty((B, M), dtype=torch.int32, device=dev)
+    pred_match = torch.empty((B, N), dtype=torch.int32, device=dev)
+    gt_iou = torch.empty((B, M), dtype=torch.float64, device=dev)
+    stats = torch.empty((B, 6), dtype=torch.int64, device=dev)
+    if B:
+        nbytes = lib.vkas_quad_match_workspace_bytes(B, M, N, max_pairs)
+        if nbytes < 0:
+            check(-1, 'match_quads')
+        ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+        check(lib.vkas_quad_match(_p(gt_rows), _p(gt_count), _p(pred_rows), _p(pred_count), B, M, N, iou_thr, max_pairs, _p(ws),
+                                  ws.numel(), _p(gt_match), _p(pred_match), _p(gt_iou), _p(stats), _p(rounds), _stream()),
+              'match_quads')
+    return gt_match, pred_match, gt_iou, stats
+
+
 def text_regions(mask: torch.Tensor, height: torch.Tensor, max_regions: int):
     """Text regions of the rough maps and the median character height of each (the step between the two passes,
     inferencing/adaptive_scaling.py:190-279 restated on pixels, csrc/regions.hip).  mask (B,H,W) uint8 and height (B,H,W)
