@@ -364,49 +364,39 @@ typedef struct vkas_precise_loss_cfg {
  * The reference's advanced indexing (loss_function/adaptive_scaling.py:235-262) raises for such a point; the host reads this
  * value asynchronously instead of synchronising inside the step. */
 int vkas_points_margin(const int64_t* py, const int64_t* px, long n, int H, int W, int64_t* margin, void* stream);
-/* prob (B,1,H,W), offset (B,2,H,W), angle (B,4,H,W), dist (B,4,H,W) fp32 NCHW; py/px (B,P) int64;
- * gt_offsets (B,P,2), gt_angles (B,P,4), gt_dists (B,P,3) fp32. */
-int vkas_precise_loss_fwd(const float* prob, const float* offset, const float* angle, const float* dist,
-                          const float* gt_score, const float* gt_mask, const int64_t* py, const int64_t* px,
-                          const float* gt_offsets, const float* gt_angles, const float* gt_dists, int B, int H,
-                          int W, int up, int left, int CH, int CW, int P, const vkas_precise_loss_cfg* cfg,
-                          double* sums, float* loss, void* stream);
-int vkas_precise_loss_bwd(const float* prob, const float* offset, const float* angle, const float* dist,
-                          const float* gt_score, const float* gt_mask, const int64_t* py, const int64_t* px,
-                          const float* gt_offsets, const float* gt_angles, const float* gt_dists, int B, int H,
-                          int W, int up, int left, int CH, int CW, int P, const vkas_precise_loss_cfg* cfg,
-                          const double* sums, const float* dloss, float* d_prob, float* d_offset, float* d_angle,
-                          float* d_dist, void* stream);
-/* The precise loss with the three terms the reference's config can switch on (all off by default, :136-140):
+/* The three terms the reference's config can switch on (all off by default, :136-140):
  * mask_focal  sigmoid focal loss (mean over B*CH*CW) of the cropped mask logits against gt_mask, :272-277
  * prob_l1     smooth-L1 (beta prob_l1_beta) of sigmoid(prob) against gt_score, sum(e * gt_mask) / (sum(gt_mask) + 1e-6),
  *             :284-289
  * prob_wahr   weight-adaptive heatmap regression of sigmoid(prob) against gt_score (mean), :303-307 and
  *             weight_adaptive_heatmap_regression.py:20-32
- * A factor <= 0 switches its term off; with all three off the result equals vkas_precise_loss_fwd/bwd. */
+ * A factor <= 0 switches its term off. */
 typedef struct vkas_precise_loss_extra_cfg {
   float mask_focal, prob_l1, prob_wahr; /* char_mask_focal_factor, char_prob_l1_factor, char_prob_wahr_factor */
   float prob_l1_beta;                   /* 0.25, :156 (must be positive when prob_l1 > 0) */
   float wahr_gamma;                     /* 0.01, weight_adaptive_heatmap_regression.py:20 */
   float focal_alpha, focal_gamma;       /* 0.25, 2: focal_with_logits.py:21-23 (alpha < 0: no alpha weighting) */
 } vkas_precise_loss_extra_cfg;
-#define VKAS_PRECISE_LOSS_EX_SUMS 16 /* doubles of the ex `sums` workspace, kept from forward for backward */
-/* Arguments as vkas_precise_loss_fwd/bwd, plus: mask_feat (B,1,H,W) fp32 mask logits, read over the same crop as prob
- * (may be NULL unless mask_focal > 0); ex; sums of VKAS_PRECISE_LOSS_EX_SUMS doubles; d_mask_feat (B,1,H,W), written in
- * full (zeros outside the crop and everywhere when mask_focal <= 0), may be NULL unless mask_focal > 0. */
-int vkas_precise_loss_ex_fwd(const float* prob, const float* offset, const float* angle, const float* dist,
-                             const float* gt_score, const float* gt_mask, const int64_t* py, const int64_t* px,
-                             const float* gt_offsets, const float* gt_angles, const float* gt_dists, int B, int H,
-                             int W, int up, int left, int CH, int CW, int P, const vkas_precise_loss_cfg* cfg,
-                             const float* mask_feat, const vkas_precise_loss_extra_cfg* ex, double* sums, float* loss,
-                             void* stream);
-int vkas_precise_loss_ex_bwd(const float* prob, const float* offset, const float* angle, const float* dist,
-                             const float* gt_score, const float* gt_mask, const int64_t* py, const int64_t* px,
-                             const float* gt_offsets, const float* gt_angles, const float* gt_dists, int B, int H,
-                             int W, int up, int left, int CH, int CW, int P, const vkas_precise_loss_cfg* cfg,
-                             const float* mask_feat, const vkas_precise_loss_extra_cfg* ex, const double* sums,
-                             const float* dloss, float* d_prob, float* d_offset, float* d_angle, float* d_dist,
-                             float* d_mask_feat, void* stream);
+#define VKAS_PRECISE_LOSS_SUMS 16 /* doubles of the `sums` workspace, kept from forward for backward */
+/* prob (B,1,H,W), offset (B,2,H,W), angle (B,4,H,W), dist (B,4,H,W) fp32 NCHW; py/px (B,P) int64;
+ * gt_offsets (B,P,2), gt_angles (B,P,4), gt_dists (B,P,3) fp32.  ex is required.  mask_feat (B,1,H,W) fp32 mask logits,
+ * read over the same crop as prob (may be NULL unless mask_focal > 0); sums of VKAS_PRECISE_LOSS_SUMS doubles;
+ * d_mask_feat (B,1,H,W), written in full (zeros outside the crop and everywhere when mask_focal <= 0), may be NULL
+ * unless mask_focal > 0.  Every output and the workspace are written by kernels alone, so both calls can be captured
+ * into a graph. */
+int vkas_precise_loss_fwd(const float* prob, const float* offset, const float* angle, const float* dist,
+                          const float* gt_score, const float* gt_mask, const int64_t* py, const int64_t* px,
+                          const float* gt_offsets, const float* gt_angles, const float* gt_dists, int B, int H,
+                          int W, int up, int left, int CH, int CW, int P, const vkas_precise_loss_cfg* cfg,
+                          const float* mask_feat, const vkas_precise_loss_extra_cfg* ex, double* sums, float* loss,
+                          void* stream);
+int vkas_precise_loss_bwd(const float* prob, const float* offset, const float* angle, const float* dist,
+                          const float* gt_score, const float* gt_mask, const int64_t* py, const int64_t* px,
+                          const float* gt_offsets, const float* gt_angles, const float* gt_dists, int B, int H,
+                          int W, int up, int left, int CH, int CW, int P, const vkas_precise_loss_cfg* cfg,
+                          const float* mask_feat, const vkas_precise_loss_extra_cfg* ex, const double* sums,
+                          const float* dloss, float* d_prob, float* d_offset, float* d_angle, float* d_dist,
+                          float* d_mask_feat, void* stream);
 
 /* ---- primitive loss callables: loss_function/__init__.py:12-18 ------------------------------------------- */
 #define VKAS_LOSS_FOCAL 0     /* focal_with_logits.py:18-47: p0 = alpha (< 0: no alpha weighting), p1 = gamma */

@@ -112,7 +112,7 @@ def test_mask_feature_host_checks():
     for bad in (z(2, 1, 12, 13), z(2, 2, 12, 14), z(1, 1, 12, 14)):
         with pytest.raises(ValueError):
             _cpu_call({'char_mask_focal_factor': 1.0}, bad)
-    # valid arguments get as far as the device requirement (no CPU fallback), on both paths
+    # valid arguments get as far as the device requirement (no CPU fallback), with and without the extra terms
     for over, mf in (({'char_mask_focal_factor': 1.0}, z(2, 1, 12, 14)), ({'char_prob_l1_factor': 1.0}, None),
                      ({'char_prob_wahr_factor': 1.0}, z(3, 3)), ({}, z(3, 3))):
         with pytest.raises(RuntimeError, match='MI355X'):
@@ -149,13 +149,13 @@ def test_wahr_oracle_reproduces_reference_golden(variant, gamma):
 
 
 def test_c_abi_argument_checks_without_gpu():
-    """The new entry points refuse inconsistent arguments before anything is launched (VKAS_E_ARG + message)."""
+    """The precise-loss entry points refuse inconsistent arguments before anything is launched (VKAS_E_ARG + message)."""
     import ctypes
     from vkit_ocr_model_adaptive_scaling_amd import _lib
     a = lambda: ctypes.c_void_p(256)  # any aligned non-null address: the checks run before anything is dereferenced
     cfg = _lib.PreciseLossCfg(2.0, 1.0, 1.0, 1.0, 5.0, 1.0, 0.15, 2.5, 1.0)
     dims = (2, 12, 14, 2, 3, 8, 9, 3)
-    fwd, bwd = _lib.lib.vkas_precise_loss_ex_fwd, _lib.lib.vkas_precise_loss_ex_bwd
+    fwd, bwd = _lib.lib.vkas_precise_loss_fwd, _lib.lib.vkas_precise_loss_bwd
     ex = _lib.PreciseLossExtraCfg(1.0, 0.0, 0.0, 0.25, 0.01, 0.25, 2.0)
     assert fwd(*[a() for _ in range(11)], *dims, ctypes.byref(cfg), None, ctypes.byref(ex), a(), a(), None) == -1
     assert b'mask feature' in _lib.lib.vkas_last_error()

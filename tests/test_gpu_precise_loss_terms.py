@@ -1,6 +1,8 @@
-"""The precise loss's default-off terms on the GPU (vkas_precise_loss_ex_fwd/bwd, ops.PreciseLossEx) and the WAHR primitive
-(VKAS_LOSS_WAHR): against the reference's golden, against the fp64 oracle of tests/test_cpu_precise_loss_terms.py on a
-larger case, the all-off extended entry points against the default ones, a HIP-graph replay, and one TwoPassStep."""
+"""The precise loss with and without its default-off terms on the GPU (vkas_precise_loss_fwd/bwd, ops.PreciseLoss) and the
+WAHR primitive (VKAS_LOSS_WAHR): against the reference's golden, against the fp64 oracle of
+tests/test_cpu_precise_loss_terms.py on a larger case and, through the C ABI, on one whose grid-stride loops take a second
+trip, a HIP-graph replay of the default configuration and of every term on, and one TwoPassStep."""
+import ctypes
 import os
 
 import numpy as np
@@ -87,7 +89,7 @@ def _large_case(seed=7, B=4, H=256, W=256, box=(30, 229, 41, 220), P=200):
 def test_precise_terms_vs_oracle_large():
     from vkit_ocr_model_adaptive_scaling_amd.loss_function import Box
     t, box, shape = _large_case()
-    over = dict(char_mask_focal_factor=1.5, char_prob_l1_factor=0.7, char_prob_wahr_factor=3.0)
+    over = ALL_ON
     kw = dict(prob_smooth_beta=0.3, focal_alpha=0.4, focal_gamma=1.5, wahr_gamma=0.05)
     scale = 0.25
     k = Knobs(**over, prob_smooth_beta=0.3, focal_alpha=0.4, focal_gamma=1.5, wahr_gamma=0.05)
@@ -122,43 +124,103 @@ def _ops_args(t, box, shape, over, scale=1.0):
     return cfg, ex
 
 
-def test_extended_entry_points_all_off_match_default():
-    """vkas_precise_loss_ex_* with the three factors at 0 computes what vkas_precise_loss_* does (fp64 atomic order aside)."""
-    from vkit_ocr_model_adaptive_scaling_amd import ops
-    t, box, shape = _large_case(seed=8)
+ALL_ON = dict(char_mask_focal_factor=1.5, char_prob_l1_factor=0.7, char_prob_wahr_factor=3.0)
+
+
+def _abi_case(B=3, H=423, W=419, box=(2, 421, 1, 417), P=37):
+    """B*H*W = 531,711 and B*CH*CW = 525,420 both exceed the 2048 * 256 threads a launch is capped at, so the grid-stride
+    loops of the dense forward and backward take a second trip; H*W is no multiple of 256; the crop leaves a margin on
+    all four sides.  The label points include both corners of the map, pixels outside the crop and one duplicate."""
+    t, _, _ = _large_case(seed=11, B=B, H=H, W=W, box=box, P=P)
+    up, down, left, right = box
+    fixed = [(0, 0), (H - 1, W - 1), (0, W - 1), (H - 1, 0), (1, 200), (422, 7), (100, 0), (300, 418), (57, 91), (57, 91)]
+    for b in range(B):
+        for i, (y, x) in enumerate(fixed):
+            t['py'][b, i], t['px'][b, i] = y, x
+    inside = (t['py'] >= up) & (t['py'] <= down) & (t['px'] >= left) & (t['px'] <= right)
+    assert (~inside).sum() >= 8 * B and inside.any()
+    return t, box, (H, W)
+
+
+@pytest.fixture(scope='module')
+def abi_case():
+    return _abi_case()
+
+
+@pytest.mark.parametrize('terms', ['off', 'on'])
+def test_c_abi_vs_oracle_second_grid_trip(abi_case, terms):
+    """vkas_precise_loss_fwd/bwd called directly, every output and the sums workspace prefilled with NaN, against the fp64
+    oracle; the zero pattern of the gradients is held exactly."""
+    from vkit_ocr_model_adaptive_scaling_amd import _lib as L
+    t, box, (H, W) = abi_case
+    up, down, left, right = box
+    on = terms == 'on'
+    over = ALL_ON if on else {}
+    scale, dl = 0.5, 0.75
+    cfg, ex = _ops_args(t, box, (H, W), over, scale=scale)
+    to = lambda a: torch.from_numpy(a).double()
+    ref_in = {n: to(t[n]).requires_grad_(True) for n in PREDS}
+    ref = precise_loss_oracle(Knobs(**over), *(ref_in[n] for n in PREDS), to(t['gt_score_precise']), to(t['gt_mask']), box,
+                              torch.from_numpy(t['py']), torch.from_numpy(t['px']), to(t['gt_offsets']),
+                              to(t['gt_angles']), to(t['gt_dists']), scale=scale)
+    ref.backward(torch.tensor(dl, dtype=torch.float64))
     c = _on_gpu(t)
-    cfg, ex = _ops_args(t, box, shape, {}, scale=0.5)
-    gts = (c['gt_score_precise'], c['gt_mask'], c['py'], c['px'], c['gt_offsets'], c['gt_angles'], c['gt_dists'],
-           box[0], box[2], cfg)
-    a = [c[n].clone().requires_grad_(True) for n in ('prob', 'offset', 'angle', 'dist')]
-    la = ops.PreciseLoss.apply(*a, *gts)
-    la.backward()
-    b = [c[n].clone().requires_grad_(True) for n in ('prob', 'offset', 'angle', 'dist')]
-    lb = ops.PreciseLossEx.apply(b[0], None, *b[1:], *gts, ex)
-    lb.backward()
-    assert abs(float(la) - float(lb)) <= 1e-6 * abs(float(la))
-    for x, y in zip(a, b):
-        assert rel_err(y.grad, x.grad) < 1e-6
+    B, P = c['py'].shape
+    CH, CW = down - up + 1, right - left + 1
+    assert B * H * W > 2048 * 256 and B * CH * CW > 2048 * 256 and (H * W) % 256
+    nan = lambda *shape, dtype=torch.float32: torch.full(shape, float('nan'), dtype=dtype, device='cuda')
+    sums, loss = nan(L.PRECISE_LOSS_SUMS, dtype=torch.float64), nan(1)
+    grads = {n: nan(*c[n].shape) for n in PREDS if on or n != 'mask_feat'}
+    dloss = torch.full((1,), dl, device='cuda')
+    p = lambda x: None if x is None else ctypes.c_void_p(x.data_ptr())
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    common = (p(c['prob']), p(c['offset']), p(c['angle']), p(c['dist']), p(c['gt_score_precise']), p(c['gt_mask']),
+              p(c['py']), p(c['px']), p(c['gt_offsets']), p(c['gt_angles']), p(c['gt_dists']), B, H, W, up, left, CH, CW, P,
+              ctypes.byref(cfg), p(c['mask_feat']) if on else None, ctypes.byref(ex), p(sums))
+    L.check(L.lib.vkas_precise_loss_fwd(*common, p(loss), st), 'precise_loss_fwd')
+    L.check(L.lib.vkas_precise_loss_bwd(*common, p(dloss), p(grads['prob']), p(grads['offset']), p(grads['angle']),
+                                        p(grads['dist']), p(grads.get('mask_feat')), st), 'precise_loss_bwd')
+    torch.cuda.synchronize()
+    print(f'loss {float(loss):.9g} oracle {float(ref):.9g} rel {abs(float(loss) - float(ref)) / abs(float(ref)):.3g}')
+    for n, g in grads.items():
+        print(f'{n}: rel_err {rel_err(g, ref_in[n].grad):.3g}')
+    assert not bool(torch.isnan(sums).any()) and not bool(torch.isnan(loss).any())
+    assert abs(float(loss) - float(ref)) < 2e-5 * abs(float(ref))
+    outside = torch.ones((H, W), dtype=torch.bool)
+    outside[up:down + 1, left:right + 1] = False
+    at_point = torch.zeros((B, H, W), dtype=torch.bool)
+    at_point[torch.arange(B)[:, None], torch.from_numpy(t['py']), torch.from_numpy(t['px'])] = True
+    for n, g in grads.items():
+        g = g.cpu()
+        assert not bool(torch.isnan(g).any()), n
+        assert rel_err(g, ref_in[n].grad) < 1e-4, n
+        if n in ('prob', 'mask_feat'):
+            assert bool((g[:, 0][:, outside] == 0).all()), n
+        else:
+            assert bool((g.permute(0, 2, 3, 1)[~at_point] == 0).all()), n
 
 
-def _graph_worker(rank, out_dir):
+def _graph_worker(rank, out_dir, terms):
     """Child process of test_precise_terms_graph_replay: capture, replay, compare; raises on a mismatch."""
     from vkit_ocr_model_adaptive_scaling_amd import ops
     torch.cuda.set_device(0)
     t, box, shape = _large_case(seed=9, B=2)
     c = _on_gpu(t)
-    cfg, ex = _ops_args(t, box, shape, dict(char_mask_focal_factor=1.5, char_prob_l1_factor=0.7, char_prob_wahr_factor=3.0))
-    ins = [c[n].clone().requires_grad_(True) for n in PREDS]
+    # 'default': the three extra factors 0, no mask feature, gradients for the four maps only
+    names = PREDS if terms == 'on' else PREDS[1:]
+    cfg, ex = _ops_args(t, box, shape, ALL_ON if terms == 'on' else {})
+    ins = [c[n].clone().requires_grad_(True) for n in names]
+    maps = ins[-4:]
 
     def run():
-        loss = ops.PreciseLossEx.apply(ins[1], ins[0], ins[2], ins[3], ins[4], c['gt_score_precise'], c['gt_mask'],
-                                       c['py'], c['px'], c['gt_offsets'], c['gt_angles'], c['gt_dists'], box[0], box[2],
-                                       cfg, ex)
+        loss = ops.PreciseLoss.apply(maps[0], ins[0] if terms == 'on' else None, maps[1], maps[2], maps[3],
+                                     c['gt_score_precise'], c['gt_mask'], c['py'], c['px'], c['gt_offsets'],
+                                     c['gt_angles'], c['gt_dists'], box[0], box[2], cfg, ex)
         return (loss,) + torch.autograd.grad(loss, ins)
 
     def compare(static, eager, what):
         assert abs(float(static[0]) - float(eager[0])) <= 1e-6 * abs(float(eager[0])), what
-        for n, s_, e_ in zip(PREDS, static[1:], eager[1:]):
+        for n, s_, e_ in zip(names, static[1:], eager[1:]):
             assert rel_err(s_, e_) < 1e-6, (what, n)
 
     eager = [x.detach().clone() for x in run()]
@@ -187,12 +249,14 @@ def _graph_worker(rank, out_dir):
     open(os.path.join(out_dir, 'graph_ok'), 'w').write('ok')
 
 
-def test_precise_terms_graph_replay(tmp_path):
-    """Forward + backward of the extended loss with every term on, captured in one HIP graph (torch.cuda.graph, the
-    backward through torch.autograd.grad) and replayed, equals the eager run: nothing on the new path waits for the host or
-    allocates host-side state.  Runs in a child process so that a failed capture fails this test only."""
+@pytest.mark.parametrize('terms', ['on', 'default'])
+def test_precise_terms_graph_replay(tmp_path, terms):
+    """Forward + backward of the precise loss, with every term on and in the default configuration, captured in one HIP
+    graph (torch.cuda.graph, the backward through torch.autograd.grad) and replayed, equals the eager run: nothing on the
+    path waits for the host or allocates host-side state.  Runs in a child process so that a failed capture fails this
+    test only."""
     import torch.multiprocessing as mp
-    mp.spawn(_graph_worker, args=(str(tmp_path),), nprocs=1, join=True)
+    mp.spawn(_graph_worker, args=(str(tmp_path), terms), nprocs=1, join=True)
     assert (tmp_path / 'graph_ok').read_text() == 'ok'
 
 

@@ -16,7 +16,7 @@ F32, BF16, F16 = 0, 1, 2
 EPI_NONE, EPI_GELU, EPI_SCALE_RES, EPI_DGELU, EPI_ADD, EPI_PATCH, EPI_HEAD = range(7)
 LOSS_FOCAL, LOSS_DICE, LOSS_L1, LOSS_SMOOTH_L1, LOSS_L2 = range(5)
 LOSS_WAHR = 5
-PRECISE_LOSS_EX_SUMS = 16  # VKAS_PRECISE_LOSS_EX_SUMS
+PRECISE_LOSS_SUMS = 16  # VKAS_PRECISE_LOSS_SUMS
 
 
 class ConvGeom(Structure):
@@ -163,12 +163,10 @@ _SIGS = {
     'vkas_rough_loss_bwd': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                     POINTER(RoughLossCfg), _P, _P, _P, _P, _P]),
     'vkas_points_margin': (c_int, [_P, _P, c_long, c_int, c_int, _P, _P]),
-    'vkas_precise_loss_fwd': (c_int, [_P] * 11 + [c_int] * 8 + [POINTER(PreciseLossCfg), _P, _P, _P]),
-    'vkas_precise_loss_bwd': (c_int, [_P] * 11 + [c_int] * 8 + [POINTER(PreciseLossCfg), _P, _P, _P, _P, _P, _P, _P]),
-    'vkas_precise_loss_ex_fwd': (c_int, [_P] * 11 + [c_int] * 8 + [POINTER(PreciseLossCfg), _P, POINTER(PreciseLossExtraCfg),
-                                                                     _P, _P, _P]),
-    'vkas_precise_loss_ex_bwd': (c_int, [_P] * 11 + [c_int] * 8 + [POINTER(PreciseLossCfg), _P, POINTER(PreciseLossExtraCfg)]
-                                 + [_P] * 8),
+    'vkas_precise_loss_fwd': (c_int, [_P] * 11 + [c_int] * 8 + [POINTER(PreciseLossCfg), _P, POINTER(PreciseLossExtraCfg),
+                                                                  _P, _P, _P]),
+    'vkas_precise_loss_bwd': (c_int, [_P] * 11 + [c_int] * 8 + [POINTER(PreciseLossCfg), _P, POINTER(PreciseLossExtraCfg)]
+                              + [_P] * 8),
     'vkas_elementwise_loss_fwd': (c_int, [c_int, _P, _P, _P, c_long, c_float, c_float, c_float, _P, _P, _P]),
     'vkas_elementwise_loss_bwd': (c_int, [c_int, _P, _P, _P, c_long, c_float, c_float, c_float, _P, _P, _P, _P]),
     'vkas_cross_entropy_fwd': (c_int, [_P, _P, c_int, c_long, c_int, _P, _P, _P]),

@@ -122,28 +122,46 @@ __global__ __launch_bounds__(256) void rough_bwd_kernel(const float* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------- precise
-// sums: [0] sum (p-s)^2 m  [1] sum m  [2] sum (p-s)^2 (1-m)  [3] sum (1-m)
+// sums (VKAS_PRECISE_LOSS_SUMS doubles): [0] sum (p-s)^2 m  [1] sum m  [2] sum (p-s)^2 (1-m)  [3] sum (1-m)
 //       [4] offset smooth-L1  [5] distance regulariser  [6] soft-target CE  [7] corner-distance smooth-L1
+//       [8] sum smoothl1(p-s)*m  [9] sum WAHR  [10] sum mask focal
+// [8..10] belong to the three terms the reference's config switches on (adaptive_scaling.py:136,137,140); each is
+// computed only where its factor in vkas_precise_loss_extra_cfg is > 0.
+__global__ void zero_sums_kernel(double* __restrict__ sums) {
+  if (threadIdx.x < VKAS_PRECISE_LOSS_SUMS) sums[threadIdx.x] = 0.0;
+}
+
 __global__ __launch_bounds__(256) void precise_dense_fwd_kernel(const float* __restrict__ prob,
+                                                                const float* __restrict__ mf,
                                                                 const float* __restrict__ gs,
                                                                 const float* __restrict__ gm, int B, int H, int W, int up,
-                                                                int left, int CH, int CW, double* __restrict__ sums) {
-  double acc[4] = {0, 0, 0, 0};
+                                                                int left, int CH, int CW, vkas_precise_loss_extra_cfg ex,
+                                                                double* __restrict__ sums) {
+  double acc[4] = {0, 0, 0, 0}, xacc[3] = {0, 0, 0};
   const long n = (long)B * CH * CW;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     const int cx = (int)(i % CW);
     const long r = i / CW;
     const int cy = (int)(r % CH);
     const int b = (int)(r / CH);
-    const float p = sigmoidf_(prob[((long)b * H + up + cy) * W + left + cx]);
-    const float e = (p - gs[i]) * (p - gs[i]);  // l2.py:32
+    const long fi = ((long)b * H + up + cy) * W + left + cx;
+    const float p = sigmoidf_(prob[fi]);
+    const float g = gs[i], d = p - g;
+    const float e = d * d;  // l2.py:32
     const float m = gm[i];
     acc[0] += (double)(e * m);
     acc[1] += (double)m;
     acc[2] += (double)(e * (1.f - m));
     acc[3] += (double)(1.f - m);
+    if (ex.prob_l1 > 0.f) xacc[0] += (double)(sl1(d, ex.prob_l1_beta) * m);  // :284-289, l1.py:44-47
+    if (ex.prob_wahr > 0.f) {  // :303-307, weight_adaptive_heatmap_regression.py:29-32
+      const float s = powf(g, ex.wahr_gamma);
+      xacc[1] += (double)((s * (1.f - p) + (1.f - s) * p) * e);
+    }
+    if (ex.mask_focal > 0.f) xacc[2] += (double)vkas_focal_value(mf[fi], m, ex.focal_alpha, ex.focal_gamma);  // :272-277
   }
   block_accumulate<4>(acc, sums);
+  block_accumulate<3>(xacc, sums + 8);
 }
 
 // label coordinates come from the data pipeline; clamp so that a corrupt index can never fault the GPU
@@ -200,11 +218,14 @@ __global__ __launch_bounds__(256) void precise_points_fwd_kernel(const float* __
   block_accumulate<4>(acc, sums + 4);
 }
 
-__global__ void precise_finalize_kernel(const double* __restrict__ s, long npts, vkas_precise_loss_cfg cfg,
-                                        float* __restrict__ loss) {
+__global__ void precise_finalize_kernel(const double* __restrict__ s, long npts, long n, vkas_precise_loss_cfg cfg,
+                                        vkas_precise_loss_extra_cfg ex, float* __restrict__ loss) {
   double l = 0.0;
+  if (ex.mask_focal > 0.f) l += (double)ex.mask_focal * s[10] / (double)n;             // :272-277 (mean)
+  if (ex.prob_l1 > 0.f) l += (double)ex.prob_l1 * s[8] / (s[1] + 1e-6);                // :284-289
   if (cfg.pos_l2 > 0.f) l += (double)cfg.pos_l2 * s[0] / (s[1] + 1e-6);
   if (cfg.neg_l2 > 0.f) l += (double)cfg.neg_l2 * s[2] / (s[3] + 1e-6);
+  if (ex.prob_wahr > 0.f) l += (double)ex.prob_wahr * s[9] / (double)n;                // :303-307 (mean)
   if (cfg.offset_l1 > 0.f) l += (double)cfg.offset_l1 * s[4] / (double)(npts * 2);
   if (cfg.reg_l1 > 0.f) l += (double)cfg.reg_l1 * s[5] / (double)npts;
   if (cfg.angle_ce > 0.f) l += (double)cfg.angle_ce * s[6] / (double)npts;
@@ -213,30 +234,55 @@ __global__ void precise_finalize_kernel(const double* __restrict__ s, long npts,
 }
 
 __global__ __launch_bounds__(256) void precise_dense_bwd_kernel(const float* __restrict__ prob,
+                                                                const float* __restrict__ mf,
                                                                 const float* __restrict__ gs,
                                                                 const float* __restrict__ gm, int B, int H, int W, int up,
                                                                 int left, int CH, int CW, vkas_precise_loss_cfg cfg,
+                                                                vkas_precise_loss_extra_cfg ex,
                                                                 const double* __restrict__ sums,
                                                                 const float* __restrict__ dloss,
-                                                                float* __restrict__ dprob) {
-  const long n = (long)B * H * W;
+                                                                float* __restrict__ dprob, float* __restrict__ dmf,
+                                                                float* __restrict__ doff, float* __restrict__ dang,
+                                                                float* __restrict__ ddst) {
+  const long n = (long)B * H * W, hw = (long)H * W;
   const float go = dloss[0] * cfg.out_scale * cfg.loss_factor;
   const float kp = cfg.pos_l2 > 0.f ? (float)((double)cfg.pos_l2 / (sums[1] + 1e-6)) : 0.f;
   const float kn = cfg.neg_l2 > 0.f ? (float)((double)cfg.neg_l2 / (sums[3] + 1e-6)) : 0.f;
+  const float kl = ex.prob_l1 > 0.f ? (float)((double)ex.prob_l1 / (sums[1] + 1e-6)) : 0.f;
+  const double nc = (double)((long)B * CH * CW);
+  const float kw = ex.prob_wahr > 0.f ? (float)((double)ex.prob_wahr / nc) : 0.f;
+  const float kf = ex.mask_focal > 0.f ? (float)((double)ex.mask_focal / nc) : 0.f;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     const int x_ = (int)(i % W);
     const long r = i / W;
     const int y_ = (int)(r % H);
     const int b = (int)(r / H);
     const int cy = y_ - up, cx = x_ - left;
-    float g = 0.f;
+    float g = 0.f, gf = 0.f;
     if ((unsigned)cy < (unsigned)CH && (unsigned)cx < (unsigned)CW) {
       const long ci = ((long)b * CH + cy) * CW + cx;
       const float p = sigmoidf_(prob[i]);
-      const float m = gm[ci];
-      g = 2.f * (p - gs[ci]) * (kp * m + kn * (1.f - m)) * p * (1.f - p);
+      const float m = gm[ci], t = gs[ci], d = p - t;
+      float gp = 2.f * d * (kp * m + kn * (1.f - m));  // d/dp of the two L2 terms
+      if (ex.prob_l1 > 0.f) gp += kl * dsl1(d, ex.prob_l1_beta) * m;
+      if (ex.prob_wahr > 0.f) {  // d/dp [w d^2] = (1 - 2s) d^2 + 2 w d,  w = s (1 - p) + (1 - s) p
+        const float s = powf(t, ex.wahr_gamma);
+        gp += kw * ((1.f - 2.f * s) * d * d + 2.f * (s * (1.f - p) + (1.f - s) * p) * d);
+      }
+      g = gp * p * (1.f - p);
+      if (ex.mask_focal > 0.f) gf = kf * vkas_focal_grad(mf[i], m, ex.focal_alpha, ex.focal_gamma);
     }
     dprob[i] = g * go;
+    if (dmf) dmf[i] = gf * go;
+    // the label-point maps start at zero; precise_points_bwd_kernel, launched next, adds into them
+    const long pix = i % hw, bb = i / hw;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) doff[(bb * 2 + c) * hw + pix] = 0.f;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      dang[(bb * 4 + c) * hw + pix] = 0.f;
+      ddst[(bb * 4 + c) * hw + pix] = 0.f;
+    }
   }
 }
 
@@ -283,116 +329,6 @@ __global__ __launch_bounds__(256) void precise_points_bwd_kernel(const float* __
 #pragma unroll
     for (int c = 0; c < 3; ++c)
       atomicAdd(&ddst[((long)b * 4 + c + 1) * hw + pix], dsl1(v.dst[c + 1] - gd[i * 3 + c], beta) * k_d * go);
-  }
-}
-
-// ------------------------------------------------------------------------------- precise, default-off terms
-// The same dense pass with the three terms the reference's config switches on (adaptive_scaling.py:136,137,140).
-// sums (VKAS_PRECISE_LOSS_EX_SUMS doubles): [0..7] as above  [8] sum smoothl1(p-s)*m  [9] sum WAHR  [10] sum mask focal
-__global__ void zero_sums_kernel(double* __restrict__ sums) {
-  if (threadIdx.x < VKAS_PRECISE_LOSS_EX_SUMS) sums[threadIdx.x] = 0.0;
-}
-
-__global__ __launch_bounds__(256) void precise_dense_ex_fwd_kernel(const float* __restrict__ prob,
-                                                                   const float* __restrict__ mf,
-                                                                   const float* __restrict__ gs,
-                                                                   const float* __restrict__ gm, int B, int H, int W,
-                                                                   int up, int left, int CH, int CW,
-                                                                   vkas_precise_loss_extra_cfg ex,
-                                                                   double* __restrict__ sums) {
-  double acc[4] = {0, 0, 0, 0}, xacc[3] = {0, 0, 0};
-  const long n = (long)B * CH * CW;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    const int cx = (int)(i % CW);
-    const long r = i / CW;
-    const int cy = (int)(r % CH);
-    const int b = (int)(r / CH);
-    const long fi = ((long)b * H + up + cy) * W + left + cx;
-    const float p = sigmoidf_(prob[fi]);
-    const float g = gs[i], d = p - g;
-    const float e = d * d;  // l2.py:32
-    const float m = gm[i];
-    acc[0] += (double)(e * m);
-    acc[1] += (double)m;
-    acc[2] += (double)(e * (1.f - m));
-    acc[3] += (double)(1.f - m);
-    if (ex.prob_l1 > 0.f) xacc[0] += (double)(sl1(d, ex.prob_l1_beta) * m);  // :284-289, l1.py:44-47
-    if (ex.prob_wahr > 0.f) {  // :303-307, weight_adaptive_heatmap_regression.py:29-32
-      const float s = powf(g, ex.wahr_gamma);
-      xacc[1] += (double)((s * (1.f - p) + (1.f - s) * p) * e);
-    }
-    if (ex.mask_focal > 0.f) xacc[2] += (double)vkas_focal_value(mf[fi], m, ex.focal_alpha, ex.focal_gamma);  // :272-277
-  }
-  block_accumulate<4>(acc, sums);
-  block_accumulate<3>(xacc, sums + 8);
-}
-
-__global__ void precise_ex_finalize_kernel(const double* __restrict__ s, long npts, long n, vkas_precise_loss_cfg cfg,
-                                           vkas_precise_loss_extra_cfg ex, float* __restrict__ loss) {
-  double l = 0.0;
-  if (ex.mask_focal > 0.f) l += (double)ex.mask_focal * s[10] / (double)n;             // :272-277 (mean)
-  if (ex.prob_l1 > 0.f) l += (double)ex.prob_l1 * s[8] / (s[1] + 1e-6);                // :284-289
-  if (cfg.pos_l2 > 0.f) l += (double)cfg.pos_l2 * s[0] / (s[1] + 1e-6);
-  if (cfg.neg_l2 > 0.f) l += (double)cfg.neg_l2 * s[2] / (s[3] + 1e-6);
-  if (ex.prob_wahr > 0.f) l += (double)ex.prob_wahr * s[9] / (double)n;                // :303-307 (mean)
-  if (cfg.offset_l1 > 0.f) l += (double)cfg.offset_l1 * s[4] / (double)(npts * 2);
-  if (cfg.reg_l1 > 0.f) l += (double)cfg.reg_l1 * s[5] / (double)npts;
-  if (cfg.angle_ce > 0.f) l += (double)cfg.angle_ce * s[6] / (double)npts;
-  if (cfg.dist_l1 > 0.f) l += (double)cfg.dist_l1 * s[7] / (double)(npts * 3);
-  *loss = (float)(l * (double)cfg.loss_factor * (double)cfg.out_scale);  // :344
-}
-
-__global__ __launch_bounds__(256) void precise_dense_ex_bwd_kernel(const float* __restrict__ prob,
-                                                                   const float* __restrict__ mf,
-                                                                   const float* __restrict__ gs,
-                                                                   const float* __restrict__ gm, int B, int H, int W,
-                                                                   int up, int left, int CH, int CW,
-                                                                   vkas_precise_loss_cfg cfg,
-                                                                   vkas_precise_loss_extra_cfg ex,
-                                                                   const double* __restrict__ sums,
-                                                                   const float* __restrict__ dloss,
-                                                                   float* __restrict__ dprob, float* __restrict__ dmf,
-                                                                   float* __restrict__ doff, float* __restrict__ dang,
-                                                                   float* __restrict__ ddst) {
-  const long n = (long)B * H * W, hw = (long)H * W;
-  const float go = dloss[0] * cfg.out_scale * cfg.loss_factor;
-  const float kp = cfg.pos_l2 > 0.f ? (float)((double)cfg.pos_l2 / (sums[1] + 1e-6)) : 0.f;
-  const float kn = cfg.neg_l2 > 0.f ? (float)((double)cfg.neg_l2 / (sums[3] + 1e-6)) : 0.f;
-  const float kl = ex.prob_l1 > 0.f ? (float)((double)ex.prob_l1 / (sums[1] + 1e-6)) : 0.f;
-  const double nc = (double)((long)B * CH * CW);
-  const float kw = ex.prob_wahr > 0.f ? (float)((double)ex.prob_wahr / nc) : 0.f;
-  const float kf = ex.mask_focal > 0.f ? (float)((double)ex.mask_focal / nc) : 0.f;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    const int x_ = (int)(i % W);
-    const long r = i / W;
-    const int y_ = (int)(r % H);
-    const int b = (int)(r / H);
-    const int cy = y_ - up, cx = x_ - left;
-    float g = 0.f, gf = 0.f;
-    if ((unsigned)cy < (unsigned)CH && (unsigned)cx < (unsigned)CW) {
-      const long ci = ((long)b * CH + cy) * CW + cx;
-      const float p = sigmoidf_(prob[i]);
-      const float m = gm[ci], t = gs[ci], d = p - t;
-      float gp = 2.f * d * (kp * m + kn * (1.f - m));  // d/dp of the two L2 terms
-      if (ex.prob_l1 > 0.f) gp += kl * dsl1(d, ex.prob_l1_beta) * m;
-      if (ex.prob_wahr > 0.f) {  // d/dp [w d^2] = (1 - 2s) d^2 + 2 w d,  w = s (1 - p) + (1 - s) p
-        const float s = powf(t, ex.wahr_gamma);
-        gp += kw * ((1.f - 2.f * s) * d * d + 2.f * (s * (1.f - p) + (1.f - s) * p) * d);
-      }
-      g = gp * p * (1.f - p);
-      if (ex.mask_focal > 0.f) gf = kf * vkas_focal_grad(mf[i], m, ex.focal_alpha, ex.focal_gamma);
-    }
-    dprob[i] = g * go;
-    if (dmf) dmf[i] = gf * go;
-    // the label-point maps start at zero; precise_points_bwd_kernel, launched next, adds into them
-    const long pix = i % hw, bb = i / hw;
-#pragma unroll
-    for (int c = 0; c < 2; ++c) doff[(bb * 2 + c) * hw + pix] = 0.f;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      dang[(bb * 4 + c) * hw + pix] = 0.f;
-      ddst[(bb * 4 + c) * hw + pix] = 0.f;
-    }
   }
 }
 
@@ -469,24 +405,34 @@ extern "C" int vkas_points_margin(const int64_t* py, const int64_t* px, long n, 
   return VKAS_OK;
 }
 
+static int precise_extra_check(const char* who, const float* mask_feat, const vkas_precise_loss_extra_cfg* ex) {
+  VKAS_CHECK(!(ex->prob_l1 > 0.f) || ex->prob_l1_beta > 0.f, "%s: prob_l1_beta must be positive", who);
+  VKAS_CHECK(!(ex->mask_focal > 0.f) || mask_feat, "%s: mask_focal > 0 needs the mask feature", who);
+  return VKAS_OK;
+}
+
 extern "C" int vkas_precise_loss_fwd(const float* prob, const float* offset, const float* angle, const float* dist,
                                      const float* gt_score, const float* gt_mask, const int64_t* py, const int64_t* px,
                                      const float* gt_offsets, const float* gt_angles, const float* gt_dists, int B, int H,
                                      int W, int up, int left, int CH, int CW, int P, const vkas_precise_loss_cfg* cfg,
-                                     double* sums, float* loss, void* stream) {
+                                     const float* mask_feat, const vkas_precise_loss_extra_cfg* ex, double* sums,
+                                     float* loss, void* stream) {
   VKAS_CHECK(prob && offset && angle && dist && gt_score && gt_mask && py && px && gt_offsets && gt_angles && gt_dists &&
-                 cfg && sums && loss,
+                 cfg && ex && sums && loss,
              "vkas_precise_loss_fwd: null pointer");
   int rc = crop_check("vkas_precise_loss_fwd", B, H, W, up, left, CH, CW);
   if (rc) return rc;
   VKAS_CHECK(P > 0, "vkas_precise_loss_fwd: P must be positive");
+  rc = precise_extra_check("vkas_precise_loss_fwd", mask_feat, ex);
+  if (rc) return rc;
   hipStream_t st = vkas_stream(stream);
-  (void)hipMemsetAsync(sums, 0, 8 * sizeof(double), st);
-  precise_dense_fwd_kernel<<<grid_for((long)B * CH * CW), 256, 0, st>>>(prob, gt_score, gt_mask, B, H, W, up, left, CH, CW,
-                                                                       sums);
+  const long n = (long)B * CH * CW;
+  zero_sums_kernel<<<1, 64, 0, st>>>(sums);
+  precise_dense_fwd_kernel<<<grid_for(n), 256, 0, st>>>(prob, mask_feat, gt_score, gt_mask, B, H, W, up, left, CH, CW, *ex,
+                                                        sums);
   precise_points_fwd_kernel<<<grid_for((long)B * P), 256, 0, st>>>(offset, angle, dist, py, px, gt_offsets, gt_angles,
                                                                   gt_dists, B, H, W, P, cfg->smooth_beta, sums);
-  precise_finalize_kernel<<<1, 1, 0, st>>>(sums, (long)B * P, *cfg, loss);
+  precise_finalize_kernel<<<1, 1, 0, st>>>(sums, (long)B * P, n, *cfg, *ex, loss);
   VKAS_LAUNCH_CHECK("precise_loss_fwd");
   return VKAS_OK;
 }
@@ -495,84 +441,25 @@ extern "C" int vkas_precise_loss_bwd(const float* prob, const float* offset, con
                                      const float* gt_score, const float* gt_mask, const int64_t* py, const int64_t* px,
                                      const float* gt_offsets, const float* gt_angles, const float* gt_dists, int B, int H,
                                      int W, int up, int left, int CH, int CW, int P, const vkas_precise_loss_cfg* cfg,
-                                     const double* sums, const float* dloss, float* d_prob, float* d_offset,
-                                     float* d_angle, float* d_dist, void* stream) {
+                                     const float* mask_feat, const vkas_precise_loss_extra_cfg* ex, const double* sums,
+                                     const float* dloss, float* d_prob, float* d_offset, float* d_angle, float* d_dist,
+                                     float* d_mask_feat, void* stream) {
   VKAS_CHECK(prob && offset && angle && dist && gt_score && gt_mask && py && px && gt_offsets && gt_angles && gt_dists &&
-                 cfg && sums && dloss && d_prob && d_offset && d_angle && d_dist,
+                 cfg && ex && sums && dloss && d_prob && d_offset && d_angle && d_dist,
              "vkas_precise_loss_bwd: null pointer");
   int rc = crop_check("vkas_precise_loss_bwd", B, H, W, up, left, CH, CW);
   if (rc) return rc;
   VKAS_CHECK(P > 0, "vkas_precise_loss_bwd: P must be positive");
+  rc = precise_extra_check("vkas_precise_loss_bwd", mask_feat, ex);
+  if (rc) return rc;
+  VKAS_CHECK(!(ex->mask_focal > 0.f) || d_mask_feat, "vkas_precise_loss_bwd: mask_focal > 0 needs d_mask_feat");
   hipStream_t st = vkas_stream(stream);
-  const size_t hw = (size_t)H * W * sizeof(float);
-  (void)hipMemsetAsync(d_offset, 0, (size_t)B * 2 * hw, st);
-  (void)hipMemsetAsync(d_angle, 0, (size_t)B * 4 * hw, st);
-  (void)hipMemsetAsync(d_dist, 0, (size_t)B * 4 * hw, st);
-  precise_dense_bwd_kernel<<<grid_for((long)B * H * W), 256, 0, st>>>(prob, gt_score, gt_mask, B, H, W, up, left, CH, CW,
-                                                                     *cfg, sums, dloss, d_prob);
+  precise_dense_bwd_kernel<<<grid_for((long)B * H * W), 256, 0, st>>>(prob, mask_feat, gt_score, gt_mask, B, H, W, up, left,
+                                                                     CH, CW, *cfg, *ex, sums, dloss, d_prob, d_mask_feat,
+                                                                     d_offset, d_angle, d_dist);
   precise_points_bwd_kernel<<<grid_for((long)B * P), 256, 0, st>>>(offset, angle, dist, py, px, gt_offsets, gt_angles,
                                                                   gt_dists, B, H, W, P, *cfg, dloss, d_offset, d_angle,
                                                                   d_dist);
   VKAS_LAUNCH_CHECK("precise_loss_bwd");
-  return VKAS_OK;
-}
-
-static int precise_ex_check(const char* who, const float* mask_feat, const vkas_precise_loss_extra_cfg* ex) {
-  VKAS_CHECK(!(ex->prob_l1 > 0.f) || ex->prob_l1_beta > 0.f, "%s: prob_l1_beta must be positive", who);
-  VKAS_CHECK(!(ex->mask_focal > 0.f) || mask_feat, "%s: mask_focal > 0 needs the mask feature", who);
-  return VKAS_OK;
-}
-
-extern "C" int vkas_precise_loss_ex_fwd(const float* prob, const float* offset, const float* angle, const float* dist,
-                                        const float* gt_score, const float* gt_mask, const int64_t* py, const int64_t* px,
-                                        const float* gt_offsets, const float* gt_angles, const float* gt_dists, int B,
-                                        int H, int W, int up, int left, int CH, int CW, int P,
-                                        const vkas_precise_loss_cfg* cfg, const float* mask_feat,
-                                        const vkas_precise_loss_extra_cfg* ex, double* sums, float* loss, void* stream) {
-  VKAS_CHECK(prob && offset && angle && dist && gt_score && gt_mask && py && px && gt_offsets && gt_angles && gt_dists &&
-                 cfg && ex && sums && loss,
-             "vkas_precise_loss_ex_fwd: null pointer");
-  int rc = crop_check("vkas_precise_loss_ex_fwd", B, H, W, up, left, CH, CW);
-  if (rc) return rc;
-  VKAS_CHECK(P > 0, "vkas_precise_loss_ex_fwd: P must be positive");
-  rc = precise_ex_check("vkas_precise_loss_ex_fwd", mask_feat, ex);
-  if (rc) return rc;
-  hipStream_t st = vkas_stream(stream);
-  const long n = (long)B * CH * CW;
-  zero_sums_kernel<<<1, 64, 0, st>>>(sums);
-  precise_dense_ex_fwd_kernel<<<grid_for(n), 256, 0, st>>>(prob, mask_feat, gt_score, gt_mask, B, H, W, up, left, CH, CW,
-                                                           *ex, sums);
-  precise_points_fwd_kernel<<<grid_for((long)B * P), 256, 0, st>>>(offset, angle, dist, py, px, gt_offsets, gt_angles,
-                                                                  gt_dists, B, H, W, P, cfg->smooth_beta, sums);
-  precise_ex_finalize_kernel<<<1, 1, 0, st>>>(sums, (long)B * P, n, *cfg, *ex, loss);
-  VKAS_LAUNCH_CHECK("precise_loss_ex_fwd");
-  return VKAS_OK;
-}
-
-extern "C" int vkas_precise_loss_ex_bwd(const float* prob, const float* offset, const float* angle, const float* dist,
-                                        const float* gt_score, const float* gt_mask, const int64_t* py, const int64_t* px,
-                                        const float* gt_offsets, const float* gt_angles, const float* gt_dists, int B,
-                                        int H, int W, int up, int left, int CH, int CW, int P,
-                                        const vkas_precise_loss_cfg* cfg, const float* mask_feat,
-                                        const vkas_precise_loss_extra_cfg* ex, const double* sums, const float* dloss,
-                                        float* d_prob, float* d_offset, float* d_angle, float* d_dist, float* d_mask_feat,
-                                        void* stream) {
-  VKAS_CHECK(prob && offset && angle && dist && gt_score && gt_mask && py && px && gt_offsets && gt_angles && gt_dists &&
-                 cfg && ex && sums && dloss && d_prob && d_offset && d_angle && d_dist,
-             "vkas_precise_loss_ex_bwd: null pointer");
-  int rc = crop_check("vkas_precise_loss_ex_bwd", B, H, W, up, left, CH, CW);
-  if (rc) return rc;
-  VKAS_CHECK(P > 0, "vkas_precise_loss_ex_bwd: P must be positive");
-  rc = precise_ex_check("vkas_precise_loss_ex_bwd", mask_feat, ex);
-  if (rc) return rc;
-  VKAS_CHECK(!(ex->mask_focal > 0.f) || d_mask_feat, "vkas_precise_loss_ex_bwd: mask_focal > 0 needs d_mask_feat");
-  hipStream_t st = vkas_stream(stream);
-  precise_dense_ex_bwd_kernel<<<grid_for((long)B * H * W), 256, 0, st>>>(prob, mask_feat, gt_score, gt_mask, B, H, W, up,
-                                                                        left, CH, CW, *cfg, *ex, sums, dloss, d_prob,
-                                                                        d_mask_feat, d_offset, d_angle, d_dist);
-  precise_points_bwd_kernel<<<grid_for((long)B * P), 256, 0, st>>>(offset, angle, dist, py, px, gt_offsets, gt_angles,
-                                                                  gt_dists, B, H, W, P, *cfg, dloss, d_offset, d_angle,
-                                                                  d_dist);
-  VKAS_LAUNCH_CHECK("precise_loss_ex_bwd");
   return VKAS_OK;
 }

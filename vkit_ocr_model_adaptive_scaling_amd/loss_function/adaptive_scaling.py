@@ -4,7 +4,7 @@ vkit_open_model/loss_function/adaptive_scaling.py) as single fused HIP ops.
 Same config classes (including the reference's spelling ``...LossFunctionConifg``), same call signatures.
 Rough: focal + dice + masked log-space smooth-L1.  Precise: masked L2 x2, smooth-L1 offsets, distance regulariser,
 soft-target cross entropy, corner distances, and the default-off mask focal, prob smooth-L1 and weight-adaptive heatmap
-regression terms (ops.PreciseLossEx, used only when one of their factors is > 0).  The one default-off term without a HIP
+regression terms, each computed only when its factor is > 0 (ops.PreciseLoss).  The one default-off term without a HIP
 kernel, weighted BCE (rough ``bce_factor``), raises NotImplementedError instead of silently computing something else.
 """
 from typing import Any, Optional, Tuple
@@ -118,18 +118,12 @@ class AdaptiveScalingPreciseLossFunction:
         cfg = PreciseLossCfg(c.char_prob_pos_l2_factor, c.char_prob_neg_l2_factor, c.char_up_left_offset_l1_factor,
                              c.char_up_left_distance_regulation_l1_factor, c.char_corner_angle_cross_entropy_factor,
                              c.char_corner_distance_l1_factor, c.loss_factor, self.smooth_beta, scale)
-        if c.char_mask_focal_factor > 0 or c.char_prob_l1_factor > 0 or c.char_prob_wahr_factor > 0:
-            ex = PreciseLossExtraCfg(max(c.char_mask_focal_factor, 0.0), max(c.char_prob_l1_factor, 0.0),
-                                     max(c.char_prob_wahr_factor, 0.0), self.prob_smooth_beta, self.wahr_gamma,
-                                     self.focal_alpha, self.focal_gamma)
-            mask = precise_char_mask_feature if c.char_mask_focal_factor > 0 else None  # unused otherwise, as today
-            return ops.PreciseLossEx.apply(precise_char_prob_feature, mask, precise_char_up_left_corner_offset_feature,
-                                           precise_char_corner_angle_feature, precise_char_corner_distance_feature,
-                                           downsampled_char_prob_score_map, downsampled_char_mask,
-                                           downsampled_label_point_y, downsampled_label_point_x, char_up_left_offsets,
-                                           char_corner_angles, char_corner_distances, int(box.up), int(box.left), cfg, ex)
-        return ops.PreciseLoss.apply(precise_char_prob_feature, precise_char_up_left_corner_offset_feature,
+        ex = PreciseLossExtraCfg(max(c.char_mask_focal_factor, 0.0), max(c.char_prob_l1_factor, 0.0),
+                                 max(c.char_prob_wahr_factor, 0.0), self.prob_smooth_beta, self.wahr_gamma,
+                                 self.focal_alpha, self.focal_gamma)
+        mask = precise_char_mask_feature if c.char_mask_focal_factor > 0 else None  # unused otherwise
+        return ops.PreciseLoss.apply(precise_char_prob_feature, mask, precise_char_up_left_corner_offset_feature,
                                      precise_char_corner_angle_feature, precise_char_corner_distance_feature,
                                      downsampled_char_prob_score_map, downsampled_char_mask,
                                      downsampled_label_point_y, downsampled_label_point_x, char_up_left_offsets,
-                                     char_corner_angles, char_corner_distances, int(box.up), int(box.left), cfg)
+                                     char_corner_angles, char_corner_distances, int(box.up), int(box.left), cfg, ex)

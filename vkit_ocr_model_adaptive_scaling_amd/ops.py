@@ -2060,65 +2060,9 @@ class RoughLoss(Function):
 
 
 class PreciseLoss(Function):
-    """AdaptiveScalingPreciseLossFunction.__call__ (loss_function/adaptive_scaling.py:181-346), default-active terms."""
-
-    @staticmethod
-    def forward(ctx, prob, offset, angle, dist, gt_score, gt_mask, py, px, gt_off, gt_ang, gt_dist, up, left, cfg):
-        _require_cuda(prob, offset, angle, dist, gt_score, gt_mask, py, px, gt_off, gt_ang, gt_dist)
-        f = lambda t: t.contiguous().float()
-        prob, offset, angle, dist = f(prob), f(offset), f(angle), f(dist)
-        gt_score, gt_mask, gt_off, gt_ang, gt_dist = f(gt_score), f(gt_mask), f(gt_off), f(gt_ang), f(gt_dist)
-        py, px = py.contiguous().long(), px.contiguous().long()
-        _check_loss_maps('PreciseLoss', (prob, offset, angle, dist), (1, 2, 4, 4), gt_mask, gt_score, up, left)
-        B, _, H, W = prob.shape
-        _, CH, CW = gt_mask.shape
-        if py.dim() != 2 or py.shape[0] != B or px.shape != py.shape:
-            raise ValueError(f'PreciseLoss: label points must be (B={B}, P), got {tuple(py.shape)} / {tuple(px.shape)}')
-        P = py.shape[1]
-        for name, t, last in (('up_left_offsets', gt_off, 2), ('corner_angles', gt_ang, 4), ('corner_distances', gt_dist, 3)):
-            if tuple(t.shape) != (B, P, last):
-                raise ValueError(f'PreciseLoss: {name} must be ({B}, {P}, {last}), got {tuple(t.shape)}')
-        if P > 0:
-            # The reference's advanced indexing raises on out-of-range label points (and wraps negative ones); a corrupt
-            # batch must not train silently on the clamped pixels the kernel falls back to.  The range test runs on the
-            # device and its verdict travels to pinned host memory asynchronously: reading it here would stall the
-            # launch pipeline once per step, so it is examined at the NEXT loss call / check_deferred() (one step late).
-            check_deferred()
-            lim = torch.empty((1,), dtype=torch.int64, device=py.device)
-            check(lib.vkas_points_margin(_p(py), _p(px), B * P, H, W, _p(lim), _stream()), 'points_margin')
-            _defer_check(lim, f'PreciseLoss: label points outside the {H}x{W} map')
-        sums = torch.empty((8,), dtype=torch.float64, device=prob.device)
-        loss = torch.empty((), dtype=_FLOAT, device=prob.device)
-        check(lib.vkas_precise_loss_fwd(_p(prob), _p(offset), _p(angle), _p(dist), _p(gt_score), _p(gt_mask), _p(py),
-                                        _p(px), _p(gt_off), _p(gt_ang), _p(gt_dist), B, H, W, up, left, CH, CW, P,
-                                        ctypes.byref(cfg), _p(sums), _p(loss), _stream()), 'precise_loss_fwd')
-        ctx.save_for_backward(prob, offset, angle, dist, gt_score, gt_mask, py, px, gt_off, gt_ang, gt_dist, sums)
-        ctx.cfg = (up, left, cfg)
-        return loss
-
-    @staticmethod
-    def backward(ctx, dloss):
-        prob, offset, angle, dist, gt_score, gt_mask, py, px, gt_off, gt_ang, gt_dist, sums = ctx.saved_tensors
-        up, left, cfg = ctx.cfg
-        B, _, H, W = prob.shape
-        _, CH, CW = gt_mask.shape
-        P = py.shape[1]
-        dp, do, da, dd = (torch.empty_like(t) for t in (prob, offset, angle, dist))
-        dloss = dloss.contiguous().float()
-        check(lib.vkas_precise_loss_bwd(_p(prob), _p(offset), _p(angle), _p(dist), _p(gt_score), _p(gt_mask), _p(py),
-                                        _p(px), _p(gt_off), _p(gt_ang), _p(gt_dist), B, H, W, up, left, CH, CW, P,
-                                        ctypes.byref(cfg), _p(sums), _p(dloss), _p(dp), _p(do), _p(da), _p(dd),
-                                        _stream()), 'precise_loss_bwd')
-        # offset / angle / distance are read at the label points only (adaptive_scaling.py:235-262): their gradients are
-        # zero elsewhere, which the heads' backward exploits
-        for g in (do, da, dd):
-            point_sparse(g, py, px)
-        return (dp, do, da, dd) + (None,) * 10
-
-
-class PreciseLossEx(Function):
-    """PreciseLoss plus the terms that are off under the reference's default factors (loss_function/adaptive_scaling.py:
-    272-277 mask focal, :284-289 prob smooth-L1, :303-307 WAHR), switched on by ``ex`` (_lib.PreciseLossExtraCfg).
+    """AdaptiveScalingPreciseLossFunction.__call__ (loss_function/adaptive_scaling.py:181-346).  The terms that are off
+    under the reference's default factors (:272-277 mask focal, :284-289 prob smooth-L1, :303-307 WAHR) are switched on by
+    ``ex`` (_lib.PreciseLossExtraCfg).
     ``mask_feat`` (B, 1, H, W) mask logits may be None unless ``ex.mask_focal > 0``; it then receives a gradient."""
 
     @staticmethod
@@ -2126,7 +2070,7 @@ class PreciseLossEx(Function):
                 ex):
         _require_cuda(prob, mask_feat, offset, angle, dist, gt_score, gt_mask, py, px, gt_off, gt_ang, gt_dist)
         if ex.mask_focal > 0 and mask_feat is None:
-            raise ValueError('PreciseLossEx: the mask focal term needs the mask feature')
+            raise ValueError('PreciseLoss: the mask focal term needs the mask feature')
         f = lambda t: t.contiguous().float()
         prob, offset, angle, dist = f(prob), f(offset), f(angle), f(dist)
         mask_feat = f(mask_feat) if mask_feat is not None else None
@@ -2135,29 +2079,33 @@ class PreciseLossEx(Function):
         preds, channels = (prob, offset, angle, dist), (1, 2, 4, 4)
         if mask_feat is not None:
             preds, channels = preds + (mask_feat,), channels + (1,)
-        _check_loss_maps('PreciseLossEx', preds, channels, gt_mask, gt_score, up, left)
+        _check_loss_maps('PreciseLoss', preds, channels, gt_mask, gt_score, up, left)
         B, _, H, W = prob.shape
         _, CH, CW = gt_mask.shape
         if py.dim() != 2 or py.shape[0] != B or px.shape != py.shape:
-            raise ValueError(f'PreciseLossEx: label points must be (B={B}, P), got {tuple(py.shape)} / {tuple(px.shape)}')
+            raise ValueError(f'PreciseLoss: label points must be (B={B}, P), got {tuple(py.shape)} / {tuple(px.shape)}')
         P = py.shape[1]
         for name, t, last in (('up_left_offsets', gt_off, 2), ('corner_angles', gt_ang, 4), ('corner_distances', gt_dist, 3)):
             if tuple(t.shape) != (B, P, last):
-                raise ValueError(f'PreciseLossEx: {name} must be ({B}, {P}, {last}), got {tuple(t.shape)}')
+                raise ValueError(f'PreciseLoss: {name} must be ({B}, {P}, {last}), got {tuple(t.shape)}')
         if P > 0 and not torch.cuda.is_current_stream_capturing():
-            # the deferred label-point range check of PreciseLoss.forward.  Not while a HIP graph is being captured: its
-            # verdict travels through pinned host memory and an event, which a replay does not refresh, and querying
-            # events is not allowed during a capture.  The kernels clamp the coordinates, so nothing reads out of bounds.
+            # The reference's advanced indexing raises on out-of-range label points (and wraps negative ones); a corrupt
+            # batch must not train silently on the clamped pixels the kernel falls back to.  The range test runs on the
+            # device and its verdict travels to pinned host memory asynchronously: reading it here would stall the
+            # launch pipeline once per step, so it is examined at the NEXT loss call / check_deferred() (one step late).
+            # Not while a HIP graph is being captured: a replay does not refresh the pinned verdict or its event, and
+            # querying events is not allowed during a capture.  The kernels clamp the coordinates, so nothing reads out
+            # of bounds.
             check_deferred()
             lim = torch.empty((1,), dtype=torch.int64, device=py.device)
             check(lib.vkas_points_margin(_p(py), _p(px), B * P, H, W, _p(lim), _stream()), 'points_margin')
-            _defer_check(lim, f'PreciseLossEx: label points outside the {H}x{W} map')
-        sums = torch.empty((_lib.PRECISE_LOSS_EX_SUMS,), dtype=torch.float64, device=prob.device)
+            _defer_check(lim, f'PreciseLoss: label points outside the {H}x{W} map')
+        sums = torch.empty((_lib.PRECISE_LOSS_SUMS,), dtype=torch.float64, device=prob.device)
         loss = torch.empty((), dtype=_FLOAT, device=prob.device)
-        check(lib.vkas_precise_loss_ex_fwd(_p(prob), _p(offset), _p(angle), _p(dist), _p(gt_score), _p(gt_mask), _p(py),
-                                           _p(px), _p(gt_off), _p(gt_ang), _p(gt_dist), B, H, W, up, left, CH, CW, P,
-                                           ctypes.byref(cfg), _p(mask_feat), ctypes.byref(ex), _p(sums), _p(loss),
-                                           _stream()), 'precise_loss_ex_fwd')
+        check(lib.vkas_precise_loss_fwd(_p(prob), _p(offset), _p(angle), _p(dist), _p(gt_score), _p(gt_mask), _p(py),
+                                        _p(px), _p(gt_off), _p(gt_ang), _p(gt_dist), B, H, W, up, left, CH, CW, P,
+                                        ctypes.byref(cfg), _p(mask_feat), ctypes.byref(ex), _p(sums), _p(loss),
+                                        _stream()), 'precise_loss_fwd')
         ctx.save_for_backward(prob, mask_feat, offset, angle, dist, gt_score, gt_mask, py, px, gt_off, gt_ang, gt_dist, sums)
         ctx.cfg = (up, left, cfg, ex)
         return loss
@@ -2172,10 +2120,12 @@ class PreciseLossEx(Function):
         dp, do, da, dd = (torch.empty_like(t) for t in (prob, offset, angle, dist))
         dm = torch.empty_like(mask_feat) if mask_feat is not None and ex.mask_focal > 0 else None
         dloss = dloss.contiguous().float()
-        check(lib.vkas_precise_loss_ex_bwd(_p(prob), _p(offset), _p(angle), _p(dist), _p(gt_score), _p(gt_mask), _p(py),
-                                           _p(px), _p(gt_off), _p(gt_ang), _p(gt_dist), B, H, W, up, left, CH, CW, P,
-                                           ctypes.byref(cfg), _p(mask_feat), ctypes.byref(ex), _p(sums), _p(dloss),
-                                           _p(dp), _p(do), _p(da), _p(dd), _p(dm), _stream()), 'precise_loss_ex_bwd')
+        check(lib.vkas_precise_loss_bwd(_p(prob), _p(offset), _p(angle), _p(dist), _p(gt_score), _p(gt_mask), _p(py),
+                                        _p(px), _p(gt_off), _p(gt_ang), _p(gt_dist), B, H, W, up, left, CH, CW, P,
+                                        ctypes.byref(cfg), _p(mask_feat), ctypes.byref(ex), _p(sums), _p(dloss),
+                                        _p(dp), _p(do), _p(da), _p(dd), _p(dm), _stream()), 'precise_loss_bwd')
+        # offset / angle / distance are read at the label points only (adaptive_scaling.py:235-262): their gradients are
+        # zero elsewhere, which the heads' backward exploits
         for g in (do, da, dd):
             point_sparse(g, py, px)
         return (dp, dm, do, da, dd) + (None,) * 11
