@@ -615,6 +615,21 @@ int vkas_warp_pack_u8(const unsigned char* src, int Hs, int Ws, const long long*
 int vkas_warp_region_labels(const int* labels, int Hl, int Wl, int valid_h, int valid_w, int Hs, int Ws,
                             const long long* warps, const int* region_ids, int n, int fdf, int* out, int Hq, int Wq,
                             void* stream);
+/* Training crops from annotated pages (dataset/crops.py holds the rule and the host oracle crop_host).  The pages lie in one
+ * byte arena with the (S,4) int64 source table of vkas_resample_pack_u8_multi.  rows (B,16) int64, one per output image:
+ * source, ay, ax, myy, myx, mxy, mxx (Q16: the map of vkas_warp_pack_u8 for a destination at (0, 0) of H x W), log2n, the fp32
+ * bits (low 32) of three gains, three biases and the noise amplitude, the 64-bit noise key.  out (B,3,H,W) fp32: the
+ * geometric value v of a pixel and channel is that warp's uint8 (N x N bilinear sub-samples, a tap outside the page reading
+ * 0, one rounding); then, every product and sum rounded once, t = gain_c*v; t += bias_c; t += amp*r; out = t > 0 ? min(t, 255)
+ * : 0, with r = float(u >> 40) * 2^-23 - 1, u = mix((idx + 1) * 0x9E3779B97F4A7C15 + key), idx = (c*H + y)*W + x, mix the
+ * splitmix64 finaliser.  An image whose row has a source outside 0..S-1, a source entry with a side outside 1..8192, offset < 0
+ * or offset + 3*Hs*Ws > arena_bytes, |m| > 2^22 or |a| >= 2^40 is written as zeros; log2n is clamped to 0..3; taps are
+ * bounded by the source's sides: no table content makes the kernel touch memory outside its buffers.  One launch (none for
+ * B = 0), grid (ceil(W/64), ceil(H/16), B); every out element is written exactly once; capture-safe: no allocation, no
+ * synchronisation, no atomics.  B in 0..65535, H, W in 1..8192; tables 8-byte aligned; 16-byte stores when W % 4 == 0 and
+ * out is 16-byte aligned, plain stores otherwise. */
+int vkas_crop_warp_f32(const unsigned char* arena, long long arena_bytes, const long long* sources, int S,
+                       const long long* rows, int B, float* out, int H, int W, void* stream);
 
 /* ---- optimizer on the flat parameter / gradient buffers: train.py:468-478 ------------------------------ */
 /* sumsq (1 double, zeroed by the call) = sum g^2 */

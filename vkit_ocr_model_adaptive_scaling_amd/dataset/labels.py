@@ -216,6 +216,39 @@ class QuadSample:
     rng_state: Optional[Any] = None
 
 
+def collate_quad_pass(quads: Sequence, indices: Sequence[int], rng_states: Sequence, image_shape: Tuple[int, int],
+                      precise: bool, P: int, f: int, margin: int, rng_seed: int) -> Dict[str, Any]:
+    """One pass of a collated quad batch without its ``image``: the quad tables, for the precise pass the five label-point
+    arrays, and the batch-wide shape / core box / rng states.  ``quads[b]`` are the quadrilaterals of sample b in the pixels
+    of its (H, W) = ``image_shape`` model input, ``indices[b]`` the stream of its label-point draws.  Shared by
+    ``adaptive_scaling_quads_collate_fn`` and dataset/crops_batch.py::adaptive_scaling_pages_collate_fn."""
+    H, W = image_shape
+    if H % f or W % f:
+        raise ValueError(f'image sides {(H, W)} must be multiples of f = {f}')
+    h, w = H // f, W // f
+    if h <= 2 * margin + 1 or w <= 2 * margin + 1:
+        raise ValueError('margin leaves no core box')
+    box = Box(up=margin, down=h - margin - 1, left=margin, right=w - margin - 1)
+    tables = [quad_rows(q, h, w, f) for q in quads]
+    K = max(1, max(len(r) for r, _ in tables))
+    rows = np.zeros((len(tables), K, ROW_WORDS), dtype=np.int32)
+    for b, (r, _) in enumerate(tables):
+        rows[b, :len(r)] = r
+    out = {'char_quad_rows': torch.from_numpy(rows),
+           'char_quad_count': torch.tensor([len(r) for r, _ in tables], dtype=torch.int32)}
+    if precise:
+        pts = [label_points(q, ok, h, w, f, box, P, rng_seed, rng_stream=index)
+               for q, index, (_, ok) in zip(quads, indices, tables)]
+        for key, dtype in (('downsampled_label_point_y', np.int64), ('downsampled_label_point_x', np.int64),
+                           ('up_left_offsets', np.int64), ('corner_angles', np.float32),
+                           ('corner_distances', np.float32)):
+            out[key] = torch.from_numpy(np.stack([p[key].astype(dtype) for p in pts]))
+    out['downsampled_shape'] = (h, w)
+    out['downsampled_core_box'] = box
+    out['rng_states'] = list(rng_states)
+    return out
+
+
 def adaptive_scaling_quads_collate_fn(batch: Iterable[Tuple[QuadSample, QuadSample]], P: int, f: int = 2,
                                       margin: int = 10, rng_seed: int = 13371) -> Dict[str, Dict[str, Any]]:
     """``(rough QuadSample, precise QuadSample)`` pairs -> the collated batch of ``adaptive_scaling_dataset_collate_fn``
@@ -233,33 +266,12 @@ def adaptive_scaling_quads_collate_fn(batch: Iterable[Tuple[QuadSample, QuadSamp
         H, W = samples[0].image.shape[:2]
         if H % f or W % f:
             raise ValueError(f'image sides {(H, W)} must be multiples of f = {f}')
-        h, w = H // f, W // f
-        if h <= 2 * margin + 1 or w <= 2 * margin + 1:
-            raise ValueError('margin leaves no core box')
-        box = Box(up=margin, down=h - margin - 1, left=margin, right=w - margin - 1)
-        tables = []
         for s in samples:
             if s.image.shape != (H, W, 3) or s.image.dtype != np.uint8:
                 raise ValueError(f'images of a batch must all be {(H, W, 3)} uint8, got {s.image.shape} {s.image.dtype}')
-            tables.append(quad_rows(s.quads, h, w, f))
-        K = max(1, max(len(r) for r, _ in tables))
-        rows = np.zeros((len(samples), K, ROW_WORDS), dtype=np.int32)
-        for b, (r, _) in enumerate(tables):
-            rows[b, :len(r)] = r
-        out = {'image': torch.from_numpy(np.stack([s.image.transpose(2, 0, 1) for s in samples]).astype(np.float32)),
-               'char_quad_rows': torch.from_numpy(rows),
-               'char_quad_count': torch.tensor([len(r) for r, _ in tables], dtype=torch.int32)}
-        if precise:
-            pts = [label_points(s.quads, ok, h, w, f, box, P, rng_seed, rng_stream=s.index)
-                   for s, (_, ok) in zip(samples, tables)]
-            for key, dtype in (('downsampled_label_point_y', np.int64), ('downsampled_label_point_x', np.int64),
-                               ('up_left_offsets', np.int64), ('corner_angles', np.float32),
-                               ('corner_distances', np.float32)):
-                out[key] = torch.from_numpy(np.stack([p[key].astype(dtype) for p in pts]))
-        out['downsampled_shape'] = (h, w)
-        out['downsampled_core_box'] = box
-        out['rng_states'] = [s.rng_state for s in samples]
-        return out
+        rest = collate_quad_pass([s.quads for s in samples], [s.index for s in samples], [s.rng_state for s in samples],
+                                 (H, W), precise, P, f, margin, rng_seed)
+        return {'image': torch.from_numpy(np.stack([s.image.transpose(2, 0, 1) for s in samples]).astype(np.float32)), **rest}
 
     return {'rough': one_pass([r for r, _ in pairs], False), 'precise': one_pass([p for _, p in pairs], True)}
 

@@ -399,21 +399,8 @@ class AdaptiveScalingInferencing:
         16-byte aligned, and uploaded in one transfer.  -> the mats, the arena, and its (S, 4) int64 source table (byte
         offset, Hs, Ws, 0) on the host and on the device."""
         mats = [_as_mat(im) for im in images]
-        table = np.zeros((len(mats), 4), np.int64)
-        total = 0
-        for i, m in enumerate(mats):
-            if m.dtype != np.uint8:
-                raise ValueError(f'image {i}: a batch takes uint8 images, got {m.dtype}')
-            if min(m.shape[:2]) < 1 or max(m.shape[:2]) > SIDE_MAX:
-                raise ValueError(f'image {i} {m.shape[:2]}: the device resampler takes sides from 1 to {SIDE_MAX}')
-            table[i] = (total, m.shape[0], m.shape[1], 0)
-            total += -(-m.size // 16) * 16
-        host = torch.empty((total,), dtype=torch.uint8, pin_memory=True)
-        flat = host.numpy()
-        for m, (offset, _, _, _) in zip(mats, table.tolist()):
-            flat[offset:offset + m.size] = m.reshape(-1)
-        device = self.config.device
-        return mats, host.to(device, non_blocking=True), table, torch.from_numpy(table).to(device, non_blocking=True)
+        arena, table, d_table = ops.image_arena(mats, self.config.device)
+        return mats, arena, table, d_table
 
     def _multi_tables(self, rows: np.ndarray, source_shapes, page_shape, num_pages: int):
         """A multi-row table checked on the host (so the launches need no copy back) and uploaded with its page_start."""

@@ -2741,3 +2741,77 @@ def warp_region_labels(labels: torch.Tensor, valid_shape: Tuple[int, int], image
     check(lib.vkas_warp_region_labels(_p(labels), Hl, Wl, vh, vw, Hs, Ws, _p(table) if K else None, _p(ids) if K else None, K,
                                       fdf, _p(out), Hq, Wq, _stream()), 'warp_region_labels')
     return out
+
+
+_CROP_SIDE_MAX = 8192
+
+
+def image_arena(mats, device):
+    """(H, W, 3) uint8 arrays in ONE device byte arena: copied once into one pinned host buffer, every image start 16-byte
+    aligned, and uploaded in one transfer.  -> the arena (1-D uint8 on ``device``) and its (S, 4) int64 source table (byte
+    offset, Hs, Ws, 0) on the host and on the device - what ``resample_pack_u8_multi`` and ``crop_warp`` read."""
+    import numpy as np
+    table = np.zeros((len(mats), 4), np.int64)
+    total = 0
+    for i, m in enumerate(mats):
+        if m.dtype != np.uint8:
+            raise ValueError(f'image {i}: a batch takes uint8 images, got {m.dtype}')
+        if min(m.shape[:2]) < 1 or max(m.shape[:2]) > _CROP_SIDE_MAX:
+            raise ValueError(f'image {i} {m.shape[:2]}: the device resampler takes sides from 1 to {_CROP_SIDE_MAX}')
+        table[i] = (total, m.shape[0], m.shape[1], 0)
+        total += -(-m.size // 16) * 16
+    host = torch.empty((total,), dtype=torch.uint8, pin_memory=True)
+    flat = host.numpy()
+    for m, (offset, _, _, _) in zip(mats, table.tolist()):
+        flat[offset:offset + m.size] = m.reshape(-1)
+    return host.to(device, non_blocking=True), table, torch.from_numpy(table).to(device, non_blocking=True)
+
+
+def crop_warp(arena: torch.Tensor, sources, rows, size: Tuple[int, int], validate: bool = True,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Training crops of annotated pages: one affine map and one photometric jitter per output image, in one launch
+    (csrc/crops.hip; the rule and the oracle: dataset/crops.py::crop_host).  ``arena``: a 1-D uint8 device tensor that holds
+    the pages; ``sources`` (S,4) int64 rows (byte offset, Hs, Ws, 0) as ``image_arena`` builds them; ``rows`` (B,16) int64
+    crop rows - both host or device (as ``_pack_table`` takes them: host tables are always checked, device tables when
+    ``validate``, a synchronisation).  Returns the (B,3,H,W) float32 crops (``out`` if given), equal to ``crop_host`` bit for
+    bit: every element is written.  An unchecked row that cannot be trusted gives a zero image (see include/vkas.h).
+    Allocates only its output; with device tables and ``validate=False`` it never synchronises, so it can be captured into a
+    HIP graph."""
+    import numpy as np
+    from .dataset.crops import check_crop_rows
+    if arena.dim() != 1 or arena.dtype != torch.uint8:
+        raise ValueError(f'crop_warp: arena must be a 1-D uint8 tensor, got {arena.dtype} {tuple(arena.shape)}')
+    if arena.numel() < 1 or not arena.is_contiguous():
+        raise ValueError('crop_warp: arena must be contiguous and not empty')
+    try:
+        H, W = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f'crop_warp: size must be (height, width), got {size!r}') from None
+    if not (1 <= H <= _CROP_SIDE_MAX and 1 <= W <= _CROP_SIDE_MAX):
+        raise ValueError(f'crop_warp: size sides must be in [1, {_CROP_SIDE_MAX}], got {(H, W)}')
+    d_sources, h_sources = _pack_table('crop_warp', 'sources', sources, (None, 4), 'int64', arena.device, validate)
+    d_rows, h_rows = _pack_table('crop_warp', 'rows', rows, (None, 16), 'int64', arena.device, validate)
+    S, B = int(d_sources.shape[0]), int(d_rows.shape[0])
+    if S < 1:
+        raise ValueError('crop_warp: no sources')
+    if B > 65535:
+        raise ValueError(f'crop_warp: B = {B} above 65535')
+    if h_sources is not None:
+        t = h_sources
+        if ((t[:, 1:3] < 1) | (t[:, 1:3] > _CROP_SIDE_MAX)).any():
+            raise ValueError(f'crop_warp: source sides must be in [1, {_CROP_SIDE_MAX}]')
+        if ((t[:, 0] < 0) | (t[:, 0] + 3 * t[:, 1] * t[:, 2] > int(arena.numel()))).any():
+            raise ValueError(f'crop_warp: a source leaves the arena of {int(arena.numel())} bytes')
+        if h_rows is not None:
+            check_crop_rows(h_rows, t[:, 1:3])
+    elif h_rows is not None:
+        raise ValueError('crop_warp: host rows need a host source table (or validate=True) to be checked against')
+    if out is not None and (tuple(out.shape) != (B, 3, H, W) or out.dtype != torch.float32 or not out.is_contiguous() or
+                            out.device != arena.device):
+        raise ValueError(f'crop_warp: out must be a contiguous {(B, 3, H, W)} float32 tensor on {arena.device}')
+    _require_cuda(arena, out)
+    crops = out if out is not None else torch.empty((B, 3, H, W), dtype=torch.float32, device=arena.device)
+    if B:
+        check(lib.vkas_crop_warp_f32(_p(arena), int(arena.numel()), _p(d_sources), S, _p(d_rows), B, _p(crops), H, W,
+                                     _stream()), 'crop_warp')
+    return crops
