@@ -531,6 +531,34 @@ long long vkas_quad_match_workspace_bytes(int B, int M, int N, int max_pairs);
 int vkas_quad_match(const int* gt_rows, const int* gt_count, const int* pred_rows, const int* pred_count, int B, int M, int N,
                     double iou_thr, int max_pairs, void* workspace, size_t workspace_bytes, int* gt_match, int* pred_match,
                     double* gt_iou, long long* stats, int* rounds, void* stream);
+/* inferencing.match_rows on the device: quads (B,K,4,2) binary64 (y, x) corners, valid (B,K) uint8 or NULL -> rows (B,K,16)
+ * int32 as above.  Per quad: c16 = rint(c * 16) (half to even); the quad is valid iff its valid byte is non-zero, every
+ * |c16| <= 2^19 (NaN and inf fail) and the four int64 cross products of successive edges are positive; twice the area is
+ * the exact int64 shoelace sum; an invalid quad gets a zero row.  Equal to match_rows on every input.  One launch, no
+ * atomics, every row written exactly once.  B, K >= 0, B*K < 2^27; quads 8-byte and rows 16-byte aligned. */
+int vkas_quad_rows(const double* quads, const unsigned char* valid, int B, int K, int* rows, void* stream);
+/* Greedy non-maximum suppression of character quadrilaterals by IoU (inferencing/nms.py holds the rule - this project's own
+ * - and the host oracle nms_quads_host).  rows (B,K,16) int32 match rows, count (B) clamped to [0, K] on the device, probs
+ * (B,K) fp32.  A row takes part iff it lies within the count, its valid word is set and its prob is finite; every other row
+ * within the count passes through as kept.  j outranks i iff probs[j] > probs[i], or they are equal and j < i (fp32
+ * comparisons).  j is a neighbour of i iff both take part, j outranks i, their boxes overlap (inclusive) and the IoU of
+ * vkas_quad_match with i as the gt and j as the pred is >= iou_thr.  Going down the ranks a quad is kept iff none of its
+ * neighbours was kept; computed as rounds (an undecided quad is suppressed once a neighbour is kept, kept once all are
+ * suppressed; a round reads the states the previous round left).  Outputs: keep (B,K) uint8, 0 beyond the count;
+ * suppressor (B,K) int32 = the highest-ranked kept neighbour of a suppressed quad, else -1; stats (B,6) int64 = kept (rows
+ * with keep = 1), n (the clamped count), n_valid (rows that take part), pairs (box-overlapping pairs of them with j
+ * outranking i), candidates (those at or above iou_thr), status; rounds (B) int32, may be NULL = the rounds that decided a
+ * quad.  An image with more than max_pairs candidates keeps its true pairs and candidates and gets status = 1, keep = 1
+ * within the count, every suppressor -1, kept = n and rounds = 0: never a partial result.  Four launches on one stream (the
+ * pair, scan and fill passes of vkas_quad_match on one table, then the rounds); one integer atomic in LDS, no allocation,
+ * no synchronisation, every output element and every workspace word that is read is written by the call's own kernels:
+ * capture-safe and bit-identical from run to run.  Reads are bounded by K and stores by the buffers whatever the tables
+ * hold.  B in 0..65535, K in 1..8192 (beyond: an error, not a clamp), max_pairs >= 0, B*max_pairs < 2^31, iou_thr in
+ * (0, 1]; rows and workspace 16-byte aligned, workspace at least vkas_quad_nms_workspace_bytes (-1 on bad arguments). */
+long long vkas_quad_nms_workspace_bytes(int B, int K, int max_pairs);
+int vkas_quad_nms(const int* rows, const int* count, const float* probs, int B, int K, double iou_thr, int max_pairs,
+                  void* workspace, size_t workspace_bytes, unsigned char* keep, int* suppressor, long long* stats, int* rounds,
+                  void* stream);
 /* Text regions of the rough maps (the step between the passes, :190-279, restated on pixels).  mask (B,H,W) uint8 and height
  * (B,H,W) fp32 as vkas_rough_postprocess writes them.  A region is an 8-connected component of mask != 0; the regions of each
  * image are numbered 1..N by their first pixel in row-major order.  Outputs: count (B) = the true N of each image; labels

@@ -17,6 +17,11 @@
 //                          them, and an image with status set is skipped.
 //   qm_match_kernel        one workgroup per image, mutual-best rounds on integer atomicMax / atomicMin in LDS.
 //
+// The suppression of duplicate quads (vkas_quad_nms; inferencing/nms.py holds the rule and the oracle nms_quads_host) runs
+// the same three passes on one table against itself - qm_pair_kernel<.., SELF> and qm_scan_kernel<SELF>: the row that is
+// judged in the gt's place, the row that may suppress it in the pred's, pairs only where the pred outranks the gt - and
+// then qn_rounds_kernel, one workgroup per image.  qm_rows_kernel (vkas_quad_rows) is inferencing.match_rows on the device.
+//
 // The clip is Sutherland-Hodgman in binary64, every operation rounded once (qm_* helpers under contract(off): see labels.hip
 // for why __dmul_rn alone is not enough).  The two 8-vertex rings are indexed dynamically, so they live in per-thread LDS
 // slots, [ring][vertex][coordinate][thread]: consecutive lanes hit consecutive 8-byte banks, and nothing goes to scratch.
@@ -47,6 +52,7 @@ __device__ __forceinline__ double qm_div(double a, double b) { return a / b; }
 #pragma clang fp contract(fast)
 
 __device__ __forceinline__ int qm_clamp(int v, int hi) { return min(max(v, 0), hi); }
+__device__ __forceinline__ bool qm_finite_bits(unsigned b) { return (b & 0x7f800000u) != 0x7f800000u; }
 
 // The rule's IoU of the LDS rows g and p (four int4 each).  ring: this thread's slots, element (r, k, c) at
 // ring[((r * QM_RING + k) * 2 + c) * QM_THREADS].
@@ -134,7 +140,11 @@ struct QmLayout {
   int MT, NT, Mp;
 };
 
-template <bool FILL>
+// SELF: one table against itself for the suppression (gt = the row that is judged, pred = the row that may suppress it).  A
+// row takes part iff it is valid and its prob is finite, and a pair only where the pred outranks the gt (the higher float32
+// prob, then the lower index): the diagonal and one of (i, j), (j, i) drop out before the clip.  The prob bits travel in the
+// row's zero word in LDS.
+template <bool FILL, bool SELF>
 __global__ __launch_bounds__(QM_THREADS) void qm_pair_kernel(const int* __restrict__ gt_rows, const int* __restrict__ gt_count,
                                                               const int* __restrict__ pred_rows,
                                                               const int* __restrict__ pred_count, int M, int N, int Mp,
@@ -142,7 +152,8 @@ __global__ __launch_bounds__(QM_THREADS) void qm_pair_kernel(const int* __restri
                                                               int* __restrict__ tpre, int* __restrict__ tile_pairs,
                                                               const int* __restrict__ rowoff,
                                                               const long long* __restrict__ stats, int* __restrict__ cand_pred,
-                                                              unsigned long long* __restrict__ cand_iou, int max_pairs) {
+                                                              unsigned long long* __restrict__ cand_iou, int max_pairs,
+                                                              const float* __restrict__ probs) {
   __shared__ int4 s_rows[2 * QM_TILE * 4];
   __shared__ unsigned long long s_word[QM_TILE];
   __shared__ unsigned short s_list[QM_WAVES * QM_LIST];
@@ -167,12 +178,20 @@ __global__ __launch_bounds__(QM_THREADS) void qm_pair_kernel(const int* __restri
       const int i = tid + k * QM_THREADS, row = i >> 1, part = 2 * half + (i & 1);
       int4 v;
       bool keep;
+      int at;
       if (row < QM_TILE) {
-        v = reinterpret_cast<const int4*>(gt_rows)[((long)b * M + min(g0 + row, M - 1)) * 4 + part];
+        at = min(g0 + row, M - 1);
+        v = reinterpret_cast<const int4*>(gt_rows)[((long)b * M + at) * 4 + part];
         keep = g0 + row < ng;
       } else {
-        v = reinterpret_cast<const int4*>(pred_rows)[((long)b * N + min(p0 + row - QM_TILE, N - 1)) * 4 + part];
+        at = min(p0 + row - QM_TILE, N - 1);
+        v = reinterpret_cast<const int4*>(pred_rows)[((long)b * N + at) * 4 + part];
         keep = p0 + row - QM_TILE < np;
+      }
+      if (SELF && part == 3) {  // M == N: one table
+        const unsigned pb = __float_as_uint(probs[(long)b * M + at]);
+        v.z = (v.z != 0 && qm_finite_bits(pb)) ? 1 : 0;
+        v.w = (int)pb;
       }
       s_rows[row * 4 + part] = keep ? v : make_int4(0, 0, 0, 0);
     }
@@ -187,6 +206,7 @@ __global__ __launch_bounds__(QM_THREADS) void qm_pair_kernel(const int* __restri
 
   const int4 pbox = s_rows[(QM_TILE + lane) * 4 + 2];
   const bool pvalid = s_rows[(QM_TILE + lane) * 4 + 3].z != 0;
+  const float pprob = __int_as_float(s_rows[(QM_TILE + lane) * 4 + 3].w);  // SELF only
   int cnt = 0;
   for (int s = 0; s < QM_TILE / QM_WAVES; ++s) {
     const int gi = wave * (QM_TILE / QM_WAVES) + s;
@@ -197,6 +217,10 @@ __global__ __launch_bounds__(QM_THREADS) void qm_pair_kernel(const int* __restri
       const int4 gbox = s_rows[gi * 4 + 2];
       hit = pvalid && s_rows[gi * 4 + 3].z != 0 && gbox.x <= pbox.z && pbox.x <= gbox.z && gbox.y <= pbox.w &&
             pbox.y <= gbox.w;
+      if (SELF) {
+        const float gprob = __int_as_float(s_rows[gi * 4 + 3].w);
+        hit = hit && (pprob > gprob || (pprob == gprob && p0 + lane < g0 + gi));
+      }
     }
     const unsigned long long bits = __ballot(hit);
     if (hit) s_list[wave * QM_LIST + cnt + __popcll(bits & ((1ull << lane) - 1ull))] = (unsigned short)(gi * QM_TILE + lane);
@@ -226,7 +250,7 @@ __global__ __launch_bounds__(QM_THREADS) void qm_pair_kernel(const int* __restri
                         __popcll(s_word[gi] & ((1ull << pj) - 1ull));
       if (slot >= 0 && slot < max_pairs) {
         cand_pred[(long)b * max_pairs + slot] = p0 + pj;
-        cand_iou[(long)b * max_pairs + slot] = (unsigned long long)__double_as_longlong(iou);
+        if (!SELF) cand_iou[(long)b * max_pairs + slot] = (unsigned long long)__double_as_longlong(iou);
       }
     } else {
       atomicOr(&s_word[gi], 1ull << pj);
@@ -245,13 +269,15 @@ __device__ __forceinline__ int qm_wave_sum_i(int v) {
   return v;
 }
 
+// SELF (the suppression): stats = kept (written by the rounds), n = the clamped count, n_valid = the rows that take part.
+template <bool SELF>
 __global__ __launch_bounds__(QM_BLOCK) void qm_scan_kernel(const int* __restrict__ gt_rows, const int* __restrict__ gt_count,
                                                             const int* __restrict__ pred_rows,
                                                             const int* __restrict__ pred_count, int M, int N, int Mp, int NT,
                                                             int MT, const unsigned long long* __restrict__ words,
                                                             int* __restrict__ tpre, const int* __restrict__ tile_pairs,
                                                             int* __restrict__ rowoff, long long* __restrict__ stats,
-                                                            int max_pairs) {
+                                                            int max_pairs, const float* __restrict__ probs) {
   __shared__ int s_cnt[QM_MAX];
   __shared__ int s_wave[QM_BLOCK / 64];
   __shared__ int s_sum[3];
@@ -269,8 +295,14 @@ __global__ __launch_bounds__(QM_BLOCK) void qm_scan_kernel(const int* __restrict
     s_cnt[g] = run;
   }
   int n_gt = 0, n_pred = 0, pairs = 0;
-  for (int g = t; g < ng; g += QM_BLOCK) n_gt += gt_rows[((long)b * M + g) * 16 + 14] != 0;
-  for (int p = t; p < np; p += QM_BLOCK) n_pred += pred_rows[((long)b * N + p) * 16 + 14] != 0;
+  if (SELF) {
+    n_gt = t == 0 ? ng : 0;
+    for (int g = t; g < ng; g += QM_BLOCK)
+      n_pred += gt_rows[((long)b * M + g) * 16 + 14] != 0 && qm_finite_bits(__float_as_uint(probs[(long)b * M + g]));
+  } else {
+    for (int g = t; g < ng; g += QM_BLOCK) n_gt += gt_rows[((long)b * M + g) * 16 + 14] != 0;
+    for (int p = t; p < np; p += QM_BLOCK) n_pred += pred_rows[((long)b * N + p) * 16 + 14] != 0;
+  }
   for (int i = t; i < MT * NT; i += QM_BLOCK) pairs += tile_pairs[(long)b * MT * NT + i];  // <= M * N <= 2^26
   __syncthreads();
   n_gt = qm_wave_sum_i(n_gt);
@@ -410,9 +442,158 @@ __global__ __launch_bounds__(QM_BLOCK) void qm_match_kernel(const int* __restric
   }
 }
 
+// ---- suppression (inferencing/nms.py holds the rule and the host oracle nms_quads_host) -----------------------------
+
+constexpr unsigned char QN_UNDECIDED = 0, QN_KEPT = 1, QN_SUPPRESSED = 2, QN_APART = 3;  // APART: takes no part
+
+// The rounds of the suppression, one workgroup per image.  The CSR row of quad i lists the quads that outrank it and overlap
+// it at or above the threshold.  The state of every quad lives in LDS twice: a round reads the previous round's states
+// and writes the next ones, so what a round decides - and with it the count of rounds - does not depend on the order in
+// which threads run.  Thread t owns the quads t + 1024 k.  An undecided quad becomes suppressed once a neighbour is kept
+// and kept once all its neighbours are suppressed; the top-ranked undecided quad can always be decided, so the loop ends
+// within n rounds (the cap n + 1 bounds it whatever the tables hold).  The suppressor is read off the final states: the
+// highest-ranked kept neighbour.  One integer LDS atomic (the kept count); plain stores otherwise.
+__global__ __launch_bounds__(QM_BLOCK) void qn_rounds_kernel(const int* __restrict__ rows, const int* __restrict__ count,
+                                                              const float* __restrict__ probs, int K, int Kp,
+                                                              const int* __restrict__ rowoff,
+                                                              const int* __restrict__ cand, int max_pairs,
+                                                              unsigned char* __restrict__ keep, int* __restrict__ suppressor,
+                                                              long long* __restrict__ stats, int* __restrict__ rounds) {
+  __shared__ unsigned char s_state[2][QM_MAX];
+  __shared__ int s_any, s_kept;
+  const int t = threadIdx.x, b = blockIdx.x;
+  const int n = qm_clamp(count[b], K);
+  const int* off = rowoff + (long)b * (Kp + 1);
+  const int* cp = cand + (long)b * max_pairs;
+  const float* pr = probs + (long)b * K;
+  if (t == 0) s_kept = 0;
+  int done = 0;
+  if (stats[(long)b * QM_STATS + 5] != 0) {  // uniform over the workgroup: over capacity, nothing is suppressed
+    for (int i = t; i < K; i += QM_BLOCK) {
+      keep[(long)b * K + i] = i < n ? 1 : 0;
+      suppressor[(long)b * K + i] = -1;
+    }
+    __syncthreads();
+    if (t == 0) {
+      stats[(long)b * QM_STATS + 0] = n;
+      if (rounds) rounds[b] = 0;
+    }
+    return;
+  }
+  for (int i = t; i < K; i += QM_BLOCK) {
+    const bool part = i < n && rows[((long)b * K + i) * 16 + 14] != 0 && qm_finite_bits(__float_as_uint(pr[i]));
+    s_state[0][i] = part ? QN_UNDECIDED : QN_APART;
+  }
+  int cur = 0;
+  for (int round = 0; round < n + 1; ++round) {
+    if (t == 0) s_any = 0;
+    __syncthreads();
+    const unsigned char* prev = s_state[cur];
+    unsigned char* next = s_state[cur ^ 1];
+    for (int i = t; i < K; i += QM_BLOCK) {
+      unsigned char st = prev[i];
+      if (st == QN_UNDECIDED) {
+        const int lo = max(off[i], 0), hi = min(off[i + 1], max_pairs);
+        bool any_kept = false, all_suppressed = true;
+        for (int e = lo; e < hi; ++e) {
+          const int j = cp[e];
+          if ((unsigned)j >= (unsigned)K) continue;
+          const unsigned char sj = prev[j];
+          any_kept = any_kept || sj == QN_KEPT;
+          all_suppressed = all_suppressed && sj == QN_SUPPRESSED;
+        }
+        if (any_kept) st = QN_SUPPRESSED;
+        else if (all_suppressed) st = QN_KEPT;
+        if (st != QN_UNDECIDED) s_any = 1;
+      }
+      next[i] = st;
+    }
+    __syncthreads();
+    const int any = s_any;
+    __syncthreads();
+    if (!any) break;  // next equals prev
+    cur ^= 1;
+    ++done;
+  }
+  const unsigned char* fin = s_state[cur];
+  int kept = 0;
+  for (int i = t; i < K; i += QM_BLOCK) {
+    const unsigned char st = fin[i];
+    // an undecided quad can be left only by tables that are not this call's own: it is reported as kept
+    const int k = i < n && st != QN_SUPPRESSED ? 1 : 0;
+    int sup = -1;
+    if (st == QN_SUPPRESSED) {
+      const int lo = max(off[i], 0), hi = min(off[i + 1], max_pairs);
+      float best = 0.f;
+      for (int e = lo; e < hi; ++e) {  // ascending j: among equal probs the first one stays
+        const int j = cp[e];
+        if ((unsigned)j >= (unsigned)K || fin[j] != QN_KEPT) continue;
+        const float pj = pr[j];
+        if (sup < 0 || pj > best) {
+          best = pj;
+          sup = j;
+        }
+      }
+    }
+    keep[(long)b * K + i] = (unsigned char)k;
+    suppressor[(long)b * K + i] = sup;
+    kept += k;
+  }
+  kept = qm_wave_sum_i(kept);
+  if ((t & 63) == 0) atomicAdd(&s_kept, kept);
+  __syncthreads();
+  if (t == 0) {
+    stats[(long)b * QM_STATS + 0] = s_kept;
+    if (rounds) rounds[b] = done;
+  }
+}
+
+// inferencing.match_rows on the device: one thread per quad, four 16-byte stores.  Integer arithmetic is exact; the only
+// rounding is rint (half to even) of the exact product c * 16.
+__global__ __launch_bounds__(256) void qm_rows_kernel(const double* __restrict__ quads, const unsigned char* __restrict__ valid,
+                                                       long total, int* __restrict__ rows) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  bool ok = valid ? valid[i] != 0 : true;
+  double c16[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    c16[k] = __builtin_rint(quads[i * 8 + k] * 16.0);
+    ok = ok && __builtin_fabs(c16[k]) <= 524288.0;  // NaN and inf compare false
+  }
+  long cy[4], cx[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    cy[k] = ok ? (long)c16[2 * k] : 0;
+    cx[k] = ok ? (long)c16[2 * k + 1] : 0;
+  }
+  long area2 = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int k1 = (k + 1) & 3, k2 = (k + 2) & 3;
+    const long ey = cy[k1] - cy[k], ex = cx[k1] - cx[k], ny = cy[k2] - cy[k1], nx = cx[k2] - cx[k1];
+    ok = ok && ex * ny - ey * nx > 0;
+    area2 += cx[k] * cy[k1] - cx[k1] * cy[k];
+  }
+  int4 r0 = make_int4(0, 0, 0, 0), r1 = r0, r2 = r0, r3 = r0;
+  if (ok) {
+    r0 = make_int4((int)cy[0], (int)cx[0], (int)cy[1], (int)cx[1]);
+    r1 = make_int4((int)cy[2], (int)cx[2], (int)cy[3], (int)cx[3]);
+    r2 = make_int4((int)min(min(cy[0], cy[1]), min(cy[2], cy[3])), (int)min(min(cx[0], cx[1]), min(cx[2], cx[3])),
+                   (int)max(max(cy[0], cy[1]), max(cy[2], cy[3])), (int)max(max(cx[0], cx[1]), max(cx[2], cx[3])));
+    r3 = make_int4((int)(unsigned)((unsigned long long)area2 & 0xffffffffull), (int)(unsigned)((unsigned long long)area2 >> 32),
+                   1, 0);
+  }
+  int4* out = reinterpret_cast<int4*>(rows) + i * 4;
+  out[0] = r0;
+  out[1] = r1;
+  out[2] = r2;
+  out[3] = r3;
+}
+
 size_t qm_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
-QmLayout qm_layout(int B, int M, int N, int max_pairs) {
+QmLayout qm_layout(int B, int M, int N, int max_pairs, bool with_iou = true) {
   QmLayout l;
   l.MT = (int)vkas_cdiv(M, QM_TILE);
   l.NT = (int)vkas_cdiv(N, QM_TILE);
@@ -420,7 +601,7 @@ QmLayout qm_layout(int B, int M, int N, int max_pairs) {
   const size_t tiles = (size_t)B * l.NT * l.Mp;
   l.words = 0;
   l.cand_iou = qm_align(l.words + tiles * sizeof(unsigned long long));
-  l.tpre = qm_align(l.cand_iou + (size_t)B * max_pairs * sizeof(unsigned long long));
+  l.tpre = qm_align(l.cand_iou + (with_iou ? (size_t)B * max_pairs * sizeof(unsigned long long) : 0));
   l.rowoff = qm_align(l.tpre + tiles * sizeof(int));
   l.tile_pairs = qm_align(l.rowoff + (size_t)B * (l.Mp + 1) * sizeof(int));
   l.cand_pred = qm_align(l.tile_pairs + (size_t)B * l.MT * l.NT * sizeof(int));
@@ -481,17 +662,73 @@ extern "C" int vkas_quad_match(const int* gt_rows, const int* gt_count, const in
   int* cand_pred = reinterpret_cast<int*>(ws + l.cand_pred);
   hipStream_t s = vkas_stream(stream);
   const dim3 grid((unsigned)l.NT, (unsigned)l.MT, (unsigned)B);
-  qm_pair_kernel<false><<<grid, QM_THREADS, 0, s>>>(gt_rows, gt_count, pred_rows, pred_count, M, N, l.Mp, l.NT, iou_thr,
-                                                     words, tpre, tile_pairs, rowoff, stats, cand_pred, cand_iou, max_pairs);
+  qm_pair_kernel<false, false><<<grid, QM_THREADS, 0, s>>>(gt_rows, gt_count, pred_rows, pred_count, M, N, l.Mp, l.NT,
+                                                            iou_thr, words, tpre, tile_pairs, rowoff, stats, cand_pred,
+                                                            cand_iou, max_pairs, nullptr);
   VKAS_LAUNCH_CHECK("quad_match pairs");
-  qm_scan_kernel<<<B, QM_BLOCK, 0, s>>>(gt_rows, gt_count, pred_rows, pred_count, M, N, l.Mp, l.NT, l.MT, words, tpre,
-                                        tile_pairs, rowoff, stats, max_pairs);
+  qm_scan_kernel<false><<<B, QM_BLOCK, 0, s>>>(gt_rows, gt_count, pred_rows, pred_count, M, N, l.Mp, l.NT, l.MT, words, tpre,
+                                               tile_pairs, rowoff, stats, max_pairs, nullptr);
   VKAS_LAUNCH_CHECK("quad_match scan");
-  qm_pair_kernel<true><<<grid, QM_THREADS, 0, s>>>(gt_rows, gt_count, pred_rows, pred_count, M, N, l.Mp, l.NT, iou_thr, words,
-                                                    tpre, tile_pairs, rowoff, stats, cand_pred, cand_iou, max_pairs);
+  qm_pair_kernel<true, false><<<grid, QM_THREADS, 0, s>>>(gt_rows, gt_count, pred_rows, pred_count, M, N, l.Mp, l.NT,
+                                                           iou_thr, words, tpre, tile_pairs, rowoff, stats, cand_pred,
+                                                           cand_iou, max_pairs, nullptr);
   VKAS_LAUNCH_CHECK("quad_match fill");
   qm_match_kernel<<<B, QM_BLOCK, lds, s>>>(gt_count, pred_count, M, N, l.Mp, rowoff, cand_pred, cand_iou, max_pairs, gt_match,
                                            pred_match, gt_iou, stats, rounds);
   VKAS_LAUNCH_CHECK("quad_match rounds");
+  return VKAS_OK;
+}
+
+extern "C" int vkas_quad_rows(const double* quads, const unsigned char* valid, int B, int K, int* rows, void* stream) {
+  VKAS_CHECK(B >= 0 && K >= 0 && (long)B * K < (1L << 27), "vkas_quad_rows: bad B=%d, K=%d (B*K below 2^27)", B, K);
+  if ((long)B * K == 0) return VKAS_OK;
+  VKAS_CHECK(quads && rows, "vkas_quad_rows: null pointer");
+  VKAS_CHECK((((uintptr_t)quads) & 7u) == 0 && vkas_aligned16(rows),
+             "vkas_quad_rows: quads must be 8-byte aligned and rows 16-byte aligned");
+  const long total = (long)B * K;
+  qm_rows_kernel<<<(unsigned)vkas_cdiv(total, 256), 256, 0, vkas_stream(stream)>>>(quads, valid, total, rows);
+  VKAS_LAUNCH_CHECK("quad_rows");
+  return VKAS_OK;
+}
+
+extern "C" long long vkas_quad_nms_workspace_bytes(int B, int K, int max_pairs) {
+  if (qm_check_dims("vkas_quad_nms_workspace_bytes", B, K, K, max_pairs) != VKAS_OK) return -1;
+  return (long long)qm_layout(B, K, K, max_pairs, false).bytes;
+}
+
+extern "C" int vkas_quad_nms(const int* rows, const int* count, const float* probs, int B, int K, double iou_thr,
+                             int max_pairs, void* workspace, size_t workspace_bytes, unsigned char* keep, int* suppressor,
+                             long long* stats, int* rounds, void* stream) {
+  const int rc = qm_check_dims("vkas_quad_nms", B, K, K, max_pairs);
+  if (rc != VKAS_OK) return rc;
+  VKAS_CHECK(iou_thr > 0.0 && iou_thr <= 1.0, "vkas_quad_nms: iou_thr = %g must lie in (0, 1]", iou_thr);
+  if (B == 0) return VKAS_OK;
+  VKAS_CHECK(rows && count && probs && workspace && keep && suppressor && stats, "vkas_quad_nms: null pointer");
+  VKAS_CHECK(vkas_aligned16(rows) && vkas_aligned16(workspace),
+             "vkas_quad_nms: the row table and the workspace must be 16-byte aligned");
+  VKAS_CHECK((((uintptr_t)probs) & 3u) == 0 && (((uintptr_t)suppressor) & 3u) == 0 && (((uintptr_t)stats) & 7u) == 0,
+             "vkas_quad_nms: probs and suppressor must be 4-byte aligned, stats 8-byte aligned");
+  const QmLayout l = qm_layout(B, K, K, max_pairs, false);
+  VKAS_CHECK(workspace_bytes >= l.bytes, "vkas_quad_nms: workspace of %zu bytes, %zu needed", workspace_bytes, l.bytes);
+  char* ws = static_cast<char*>(workspace);
+  unsigned long long* words = reinterpret_cast<unsigned long long*>(ws + l.words);
+  int* tpre = reinterpret_cast<int*>(ws + l.tpre);
+  int* rowoff = reinterpret_cast<int*>(ws + l.rowoff);
+  int* tile_pairs = reinterpret_cast<int*>(ws + l.tile_pairs);
+  int* cand = reinterpret_cast<int*>(ws + l.cand_pred);
+  hipStream_t s = vkas_stream(stream);
+  const dim3 grid((unsigned)l.NT, (unsigned)l.MT, (unsigned)B);
+  qm_pair_kernel<false, true><<<grid, QM_THREADS, 0, s>>>(rows, count, rows, count, K, K, l.Mp, l.NT, iou_thr, words, tpre,
+                                                           tile_pairs, rowoff, stats, cand, nullptr, max_pairs, probs);
+  VKAS_LAUNCH_CHECK("quad_nms pairs");
+  qm_scan_kernel<true><<<B, QM_BLOCK, 0, s>>>(rows, count, rows, count, K, K, l.Mp, l.NT, l.MT, words, tpre, tile_pairs,
+                                              rowoff, stats, max_pairs, probs);
+  VKAS_LAUNCH_CHECK("quad_nms scan");
+  qm_pair_kernel<true, true><<<grid, QM_THREADS, 0, s>>>(rows, count, rows, count, K, K, l.Mp, l.NT, iou_thr, words, tpre,
+                                                          tile_pairs, rowoff, stats, cand, nullptr, max_pairs, probs);
+  VKAS_LAUNCH_CHECK("quad_nms fill");
+  qn_rounds_kernel<<<B, QM_BLOCK, 0, s>>>(rows, count, probs, K, l.Mp, rowoff, cand, max_pairs, keep, suppressor, stats,
+                                          rounds);
+  VKAS_LAUNCH_CHECK("quad_nms rounds");
   return VKAS_OK;
 }

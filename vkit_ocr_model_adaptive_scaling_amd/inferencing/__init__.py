@@ -17,4 +17,6 @@ from .packing import (SIDE_MAX, axis_weights, check_placements, pack_region_labe
                       check_multi_rows, pack_region_labels_multi_host, resample_pack_multi_host, stack_regions_pages)
 from .evaluation import (DetectionScore, QuadMatchResult, evaluate_quads, evaluate_quads_host, evaluation_tables,
                          match_quads_host, match_rows, quad_iou_host, result_quads)
+from .nms import (QuadNmsResult, filter_result, greedy_suppression, nms_pairs, nms_quads, nms_quads_host,
+                  nms_quads_lists_host, nms_tables, suppress_results)
 from .orient import (orient_regions, oriented_rects, region_directions, region_extents_host, region_moments_host, warp_row)

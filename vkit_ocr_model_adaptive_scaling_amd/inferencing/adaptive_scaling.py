@@ -44,6 +44,7 @@ from .regions import region_scales
 from .packing import (SIDE_MAX, check_multi_rows, check_warps, region_crops, remap_polygons, remap_polygons_affine,
                       stack_regions, stack_regions_pages)
 from .orient import orient_regions, region_directions, warp_row
+from .nms import suppress_results
 from .. import ops
 from .._lib import lib, check
 from ..model import AdaptiveScaling, AdaptiveScalingConfig
@@ -103,6 +104,11 @@ class AdaptiveScalingInferencingConfig:
     # Off: every result is bit for bit what it is without the feature.
     precise_text_region_orient: bool = False
     precise_text_region_flattener_typical_long_side_ratio_min: float = 3.0
+    # Suppression of duplicate characters (inferencing/nms.py), read by infer and infer_batch: after the quads are mapped back
+    # into the image, the characters of one image - all regions together - go through one greedy suppression at this IoU
+    # threshold (in (0, 1]).  0 = off: every result is bit for bit what it is without the feature, with no extra launch or
+    # copy.
+    precise_char_nms_iou_thr: float = 0.0
 
 
 @attrs.define
@@ -177,6 +183,10 @@ class AdaptiveScalingInferencingResult:
     # infer_batch: the shared page each placement lies on (empty from infer, which has one page).  There ``page_shape`` /
     # ``page`` / ``region_labels`` are those of the image's first placement's page, which other images share
     placement_pages: np.ndarray = attrs.field(factory=lambda: np.zeros((0,), np.int32))  # (M,) int32
+    # config.precise_char_nms_iou_thr: the characters the suppression removed from the lists above, and its status - 0, or 2
+    # for an image with more characters than the suppression takes (8192), which is left as it is
+    num_suppressed: int = 0
+    nms_status: int = 0
 
 
 @attrs.define
@@ -659,6 +669,8 @@ class AdaptiveScalingInferencing:
             polygons=polygons)
         if orient:
             result.oriented, result.warps, result.warp_regions = oriented, warps, warp_ids
+        if c.precise_char_nms_iou_thr:
+            result = suppress_results([result], c.precise_char_nms_iou_thr, c.device)[0]
         return result
 
     def infer_batch(self, images: Sequence, return_pages: bool = False,
@@ -759,6 +771,8 @@ class AdaptiveScalingInferencing:
                 page=pages[page] if return_pages and len(mine) else None,
                 region_labels=region_labels[page] if return_labels and len(mine) else None, points=points, probs=probs,
                 polygons=polygons, placement_pages=placement_pages))
+        if c.precise_char_nms_iou_thr:
+            results = suppress_results(results, c.precise_char_nms_iou_thr, c.device)  # one call for all images
         return AdaptiveScalingInferencingBatchResult(
             results=results, page_shapes=page_shapes, rows=rows, pages=pages if return_pages else None,
             region_labels=region_labels if return_labels else None)

@@ -2348,6 +2348,81 @@ def match_quads(gt_rows: torch.Tensor, gt_count: torch.Tensor, pred_rows: torch.
     return gt_match, pred_match, gt_iou, stats
 
 
+def quad_rows(quads: torch.Tensor, valid: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``inferencing.match_rows`` on the device (csrc/quadmatch.hip): ``quads`` (B, K, 4, 2) float64 ``(y, x)`` corners and an
+    optional ``valid`` (B, K) uint8 on the device -> (B, K, 16) int32 match rows, equal to the host's on every input (an
+    invalid quad gets a zero row).  One launch; never synchronises, so it can be captured into a HIP graph."""
+    if quads.dim() != 4 or tuple(quads.shape[2:]) != (4, 2):
+        raise ValueError(f'quad_rows: quads must be (B, K, 4, 2), got {tuple(quads.shape)}')
+    if quads.dtype != torch.float64:
+        raise ValueError(f'quad_rows: quads must be float64, got {quads.dtype}')
+    B, K = int(quads.shape[0]), int(quads.shape[1])
+    if B * K >= 1 << 27:
+        raise ValueError(f'quad_rows: B*K = {B * K} must stay below 2^27')
+    if valid is not None and (tuple(valid.shape) != (B, K) or valid.dtype != torch.uint8):
+        raise ValueError(f'quad_rows: valid must be a {(B, K)} uint8 tensor, got {tuple(valid.shape)} {valid.dtype}')
+    tensors = (quads,) + (() if valid is None else (valid,))
+    _require_cuda(*tensors)
+    if any(t.device != quads.device for t in tensors):
+        raise ValueError('quad_rows: all tensors must be on one device')
+    quads = quads.contiguous()
+    valid = None if valid is None else valid.contiguous()
+    rows = torch.empty((B, K, 16), dtype=torch.int32, device=quads.device)
+    if B * K:
+        check(lib.vkas_quad_rows(_p(quads), _p(valid), B, K, _p(rows), _stream()), 'quad_rows')
+    return rows
+
+
+def nms_quads(rows: torch.Tensor, count: torch.Tensor, probs: torch.Tensor, iou_thr: float = 0.5,
+              max_pairs: Optional[int] = None, rounds: Optional[torch.Tensor] = None):
+    """Greedy non-maximum suppression of character quadrilaterals by IoU on the device (csrc/quadmatch.hip; the rule and the
+    host oracle ``nms_quads_host``: inferencing/nms.py).  ``rows`` (B, K, 16) int32 match rows (``ops.quad_rows``), ``count``
+    (B,) int32, ``probs`` (B, K) float32, all on the device; K at most 8192.  ``max_pairs`` is the capacity for stored
+    candidates (outranking pairs with iou >= ``iou_thr``) per image, 4 * K by default.  Returns ``(keep, suppressor, stats)`` -
+    (B, K) uint8 (0 beyond the count), (B, K) int32 (the highest-ranked kept neighbour of a suppressed quad, else -1),
+    (B, 6) int64 ``kept, n, n_valid, pairs, candidates, status``.  An image with more candidates than ``max_pairs`` keeps its
+    true ``pairs`` and ``candidates`` and gets ``status = 1``, every quad within the count kept and every suppressor -1.
+    ``rounds``, if given, is a (B,) int32 device tensor that receives the rounds of each image.  Four launches; never
+    synchronises, so it can be captured into a HIP graph."""
+    if rows.dim() != 3 or rows.shape[2] != 16:
+        raise ValueError(f'nms_quads: rows must be (B, K, 16), got {tuple(rows.shape)}')
+    B, K, _ = (int(v) for v in rows.shape)
+    if tuple(count.shape) != (B,) or tuple(probs.shape) != (B, K):
+        raise ValueError(f'nms_quads: count must be {(B,)} and probs {(B, K)}, got {tuple(count.shape)} and {tuple(probs.shape)}')
+    if rows.dtype != torch.int32 or count.dtype != torch.int32 or probs.dtype != torch.float32:
+        raise ValueError(f'nms_quads: rows and count must be int32 and probs float32, got {rows.dtype}, {count.dtype}, '
+                         f'{probs.dtype}')
+    if not 1 <= K <= 8192:
+        raise ValueError(f'nms_quads: K = {K} must lie in 1..8192')
+    if B > 65535:
+        raise ValueError(f'nms_quads: B = {B} above 65535')
+    iou_thr = float(iou_thr)
+    if not (iou_thr > 0.0 and iou_thr <= 1.0):
+        raise ValueError(f'nms_quads: iou_thr must lie in (0, 1], got {iou_thr}')
+    max_pairs = 4 * K if max_pairs is None else int(max_pairs)
+    if max_pairs < 0 or B * max_pairs >= 1 << 31:
+        raise ValueError(f'nms_quads: max_pairs = {max_pairs} must be >= 0 and B*max_pairs below 2^31')
+    if rounds is not None and (tuple(rounds.shape) != (B,) or rounds.dtype != torch.int32 or not rounds.is_contiguous()):
+        raise ValueError(f'nms_quads: rounds must be a contiguous ({B},) int32 tensor')
+    tensors = (rows, count, probs) + (() if rounds is None else (rounds,))
+    _require_cuda(*tensors)
+    if any(t.device != rows.device for t in tensors):
+        raise ValueError('nms_quads: all tensors must be on one device')
+    rows, count, probs = rows.contiguous(), count.contiguous(), probs.contiguous()
+    dev = rows.device
+    keep = torch.empty((B, K), dtype=torch.uint8, device=dev)
+    suppressor = torch.empty((B, K), dtype=torch.int32, device=dev)
+    stats = torch.empty((B, 6), dtype=torch.int64, device=dev)
+    if B:
+        nbytes = lib.vkas_quad_nms_workspace_bytes(B, K, max_pairs)
+        if nbytes < 0:
+            check(-1, 'nms_quads')
+        ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+        check(lib.vkas_quad_nms(_p(rows), _p(count), _p(probs), B, K, iou_thr, max_pairs, _p(ws), ws.numel(), _p(keep),
+                                _p(suppressor), _p(stats), _p(rounds), _stream()), 'nms_quads')
+    return keep, suppressor, stats
+
+
 def text_regions(mask: torch.Tensor, height: torch.Tensor, max_regions: int):
     """Text regions of the rough maps and the median character height of each (the step between the two passes,
     inferencing/adaptive_scaling.py:190-279 restated on pixels, csrc/regions.hip).  mask (B,H,W) uint8 and height (B,H,W)
