@@ -531,6 +531,37 @@ long long vkas_quad_match_workspace_bytes(int B, int M, int N, int max_pairs);
 int vkas_quad_match(const int* gt_rows, const int* gt_count, const int* pred_rows, const int* pred_count, int B, int M, int N,
                     double iou_thr, int max_pairs, void* workspace, size_t workspace_bytes, int* gt_match, int* pred_match,
                     double* gt_iou, long long* stats, int* rounds, void* stream);
+/* Ranked matching of character quadrilaterals at T IoU thresholds with don't-care annotations, the device half of average
+ * precision (inferencing/ranking.py holds the rule - this project's own - in its module docstring, and the host oracles
+ * match_quads_ranked_host / match_quads_ranked_rounds_host).  gt_rows (B,M,16), pred_rows (B,N,16) match rows and counts as
+ * for vkas_quad_match; gt_care (B,M) uint8, 0 = don't care, NULL = every annotation is a care one; probs (B,N) fp32;
+ * iou_thrs = T binary64 values IN HOST MEMORY, strictly ascending in (0, 1], checked on the host; cover_thr in (0, 1].  A
+ * pred takes part iff it lies within the count, its valid word is set and its prob is finite; a gt iff it lies within the
+ * count and its valid word is set.  q outranks p iff probs[q] > probs[p], or they are equal and q < p (fp32 comparisons).
+ * For a box-overlapping pair one clip of p against g (that of vkas_quad_match) gives inter2 and iou; p is covered iff
+ * inter2 >= cover_thr * area2_p (one rounding, inclusive) for some don't-care g; the candidates at threshold t are the (care
+ * gt, pred) pairs with iou >= iou_thrs[t].  Per threshold, independently, going down the ranks a pred takes the free
+ * candidate with the highest iou (then the lowest gt): TP = 1 if it took one, else IGNORED = 3 if covered, else FP = 2;
+ * ABSENT = 0 takes no part.  Computed as rounds: an undecided pred is decided unless a higher-ranked undecided pred shares a
+ * free candidate with it; a round reads what the previous one left.  Outputs: pred_match (B,T,N) int32 gt index or -1;
+ * pred_state (B,T,N) uint8; gt_match (B,T,M) int32; pred_iou (B,T,N) binary64, 0 unless TP; covered (B,N) uint8; stats
+ * (B,T,8) int64 = tp, fp, ignored, n_gt (care gts), n_pred (preds taking part), pairs (care box pairs), candidates (at
+ * iou_thrs[t]), status; dc_stats (B,3) int64 = n_dc, dc_pairs, n_covered; rounds (B,T) int32, may be NULL = the rounds that
+ * decided a pred.  An image with more than max_pairs candidates at iou_thrs[0] keeps its true pairs and candidates (at every
+ * threshold) and gets status = 1, every state 0, every match -1, tp = fp = ignored = 0 and rounds = 0: never a partial
+ * result; covered and dc_stats are true all the same.  Four launches on one stream (the pair, scan and fill passes of
+ * vkas_quad_match at iou_thrs[0], then B*T workgroups of rounds over the one candidate list); integer atomics in LDS only,
+ * no allocation, no synchronisation, every output element and every workspace word that is read is written by the call's
+ * own kernels: capture-safe and bit-identical from run to run; reads are bounded by the tables and stores by the buffers
+ * whatever the tables hold.  B in 0..65535, M and N in 1..8192, T in 1..16, B*T <= 65535 (beyond: an error, not a clamp),
+ * max_pairs >= 0, B*max_pairs < 2^31; tables and workspace 16-byte aligned, pred_iou, stats and dc_stats 8-byte aligned,
+ * workspace at least vkas_quad_match_ranked_workspace_bytes (-1 on bad arguments). */
+long long vkas_quad_match_ranked_workspace_bytes(int B, int M, int N, int T, int max_pairs);
+int vkas_quad_match_ranked(const int* gt_rows, const int* gt_count, const unsigned char* gt_care, const int* pred_rows,
+                           const int* pred_count, const float* probs, int B, int M, int N, const double* iou_thrs, int T,
+                           double cover_thr, int max_pairs, void* workspace, size_t workspace_bytes, int* pred_match,
+                           unsigned char* pred_state, int* gt_match, double* pred_iou, unsigned char* covered,
+                           long long* stats, long long* dc_stats, int* rounds, void* stream);
 /* inferencing.match_rows on the device: quads (B,K,4,2) binary64 (y, x) corners, valid (B,K) uint8 or NULL -> rows (B,K,16)
  * int32 as above.  Per quad: c16 = rint(c * 16) (half to even); the quad is valid iff its valid byte is non-zero, every
  * |c16| <= 2^19 (NaN and inf fail) and the four int64 cross products of successive edges are positive; twice the area is

@@ -189,6 +189,9 @@ _SIGS = {
                                      _P]),
     'vkas_quad_match_workspace_bytes': (c_longlong, [c_int, c_int, c_int, c_int]),
     'vkas_quad_match': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_double, c_int, _P, c_size_t, _P, _P, _P, _P, _P, _P]),
+    'vkas_quad_match_ranked_workspace_bytes': (c_longlong, [c_int, c_int, c_int, c_int, c_int]),
+    'vkas_quad_match_ranked': (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_int, c_double, c_int, _P, c_size_t,
+                                       _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'vkas_quad_rows': (c_int, [_P, _P, c_int, c_int, _P, _P]),
     'vkas_quad_nms_workspace_bytes': (c_longlong, [c_int, c_int, c_int]),
     'vkas_quad_nms': (c_int, [_P, _P, _P, c_int, c_int, c_double, c_int, _P, c_size_t, _P, _P, _P, _P, _P]),

@@ -19,4 +19,8 @@ from .evaluation import (DetectionScore, QuadMatchResult, evaluate_quads, evalua
                          match_quads_host, match_rows, quad_iou_host, result_quads)
 from .nms import (QuadNmsResult, filter_result, greedy_suppression, nms_pairs, nms_quads, nms_quads_host,
                   nms_quads_lists_host, nms_tables, suppress_results)
+from .ranking import (OperatingPoint, PRCurve, RankedMatchResult, RankedPairs, RankedScore, average_precision_host,
+                      evaluate_quads_ranked, evaluate_quads_ranked_host, match_quads_ranked_host,
+                      match_quads_ranked_rounds_host, quad_inter2_host, ranked_matching, ranked_matching_rounds, ranked_pairs,
+                      ranked_score)
 from .orient import (orient_regions, oriented_rects, region_directions, region_extents_host, region_moments_host, warp_row)

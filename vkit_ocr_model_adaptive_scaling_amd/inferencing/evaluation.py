@@ -49,8 +49,9 @@ Per image: ``gt_match`` (M,) int32 pred index or -1, ``pred_match`` (N,) int32, 
 unmatched), ``tp``, ``n_gt`` / ``n_pred`` (the valid rows within the count), ``pairs`` (box-overlapping valid pairs),
 ``candidates`` (those at or above iou_thr).  fp = n_pred - tp, fn = n_gt - tp.
 
-Out of scope: don't-care annotations, many-to-one matching, average precision over a score sweep (a caller sweeps
-``score_thr`` itself), text-line or word level scoring."""
+Average precision over the scores, several IoU thresholds at once and don't-care annotations: inferencing/ranking.py.
+
+Out of scope: many-to-one matching, text-line or word level scoring."""
 from typing import List, Optional, Sequence, Tuple
 
 import attrs

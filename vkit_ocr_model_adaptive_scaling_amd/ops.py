@@ -2348,6 +2348,73 @@ def match_quads(gt_rows: torch.Tensor, gt_count: torch.Tensor, pred_rows: torch.
     return gt_match, pred_match, gt_iou, stats
 
 
+def match_quads_ranked(gt_rows: torch.Tensor, gt_count: torch.Tensor, gt_care: Optional[torch.Tensor],
+                       pred_rows: torch.Tensor, pred_count: torch.Tensor, probs: torch.Tensor, iou_thrs,
+                       cover_thr: float = 0.5, max_pairs: Optional[int] = None, rounds: Optional[torch.Tensor] = None):
+    """Predicted character quadrilaterals matched to annotated ones in score order at T IoU thresholds, with don't-care
+    annotations, on the device (csrc/quadmatch.hip; the rule and the host oracles: inferencing/ranking.py).  ``gt_rows``
+    (B, M, 16) / ``gt_count`` (B,) and ``pred_rows`` (B, N, 16) / ``pred_count`` (B,): int32 match rows and counts;
+    ``gt_care`` (B, M) uint8 with 0 = don't care, or None = every annotation counts; ``probs`` (B, N) float32; all on the
+    device.  ``iou_thrs``: T host floats, strictly ascending in (0, 1], T at most 16; ``cover_thr`` in (0, 1].  ``max_pairs``
+    is the capacity for stored candidates (care pairs with iou >= ``iou_thrs[0]``) per image, 4 * max(M, N) by default.
+    Returns ``(pred_match (B, T, N) int32, pred_state (B, T, N) uint8, gt_match (B, T, M) int32, pred_iou (B, T, N) float64,
+    covered (B, N) uint8, stats (B, T, 8) int64, dc_stats (B, 3) int64)`` with states 0 ABSENT, 1 TP, 2 FP, 3 IGNORED,
+    ``stats`` = tp, fp, ignored, n_gt, n_pred, pairs, candidates, status and ``dc_stats`` = n_dc, dc_pairs, n_covered.  An
+    image over the capacity keeps its true counts and gets ``status = 1``, every state 0 and every match -1.  ``rounds``, if
+    given, is a (B, T) int32 device tensor that receives the rounds.  Four launches; never synchronises, so it can be captured
+    into a HIP graph."""
+    what = 'match_quads_ranked'
+    for name, t, other in (('gt', gt_rows, gt_count), ('pred', pred_rows, pred_count)):
+        if t.dim() != 3 or t.shape[2] != 16:
+            raise ValueError(f'{what}: {name}_rows must be (B, K, 16), got {tuple(t.shape)}')
+        if tuple(other.shape) != (t.shape[0],):
+            raise ValueError(f'{what}: {name}_count must be {(t.shape[0],)}, got {tuple(other.shape)}')
+        if t.dtype != torch.int32 or other.dtype != torch.int32:
+            raise ValueError(f'{what}: {name}_rows and {name}_count must be int32, got {t.dtype} and {other.dtype}')
+    B, M, _ = (int(v) for v in gt_rows.shape)
+    N = int(pred_rows.shape[1])
+    if pred_rows.shape[0] != B:
+        raise ValueError(f'{what}: {B} images of annotations against {pred_rows.shape[0]} of predictions')
+    if tuple(probs.shape) != (B, N) or probs.dtype != torch.float32:
+        raise ValueError(f'{what}: probs must be a {(B, N)} float32 tensor, got {tuple(probs.shape)} {probs.dtype}')
+    if gt_care is not None and (tuple(gt_care.shape) != (B, M) or gt_care.dtype != torch.uint8):
+        raise ValueError(f'{what}: gt_care must be a {(B, M)} uint8 tensor, got {tuple(gt_care.shape)} {gt_care.dtype}')
+    if not (1 <= M <= 8192 and 1 <= N <= 8192):
+        raise ValueError(f'{what}: M = {M} and N = {N} must lie in 1..8192')
+    from .inferencing.ranking import check_thresholds  # the rule's own check, stated once
+    thrs, cover_thr = check_thresholds(iou_thrs, cover_thr)
+    T = len(thrs)
+    if B * T > 65535:
+        raise ValueError(f'{what}: B*T = {B * T} above 65535')
+    max_pairs = 4 * max(M, N) if max_pairs is None else int(max_pairs)
+    if max_pairs < 0 or B * max_pairs >= 1 << 31:
+        raise ValueError(f'{what}: max_pairs = {max_pairs} must be >= 0 and B*max_pairs below 2^31')
+    if rounds is not None and (tuple(rounds.shape) != (B, T) or rounds.dtype != torch.int32 or not rounds.is_contiguous()):
+        raise ValueError(f'{what}: rounds must be a contiguous ({B}, {T}) int32 tensor')
+    tensors = (gt_rows, gt_count, pred_rows, pred_count, probs) + tuple(t for t in (gt_care, rounds) if t is not None)
+    _require_cuda(*tensors)
+    if any(t.device != gt_rows.device for t in tensors):
+        raise ValueError(f'{what}: all tensors must be on one device')
+    gt_rows, gt_count, pred_rows, pred_count, probs = (t.contiguous() for t in (gt_rows, gt_count, pred_rows, pred_count, probs))
+    gt_care = None if gt_care is None else gt_care.contiguous()
+    dev = gt_rows.device
+    new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+    pred_match, pred_state = new((B, T, N), torch.int32), new((B, T, N), torch.uint8)
+    gt_match, pred_iou = new((B, T, M), torch.int32), new((B, T, N), torch.float64)
+    covered, stats, dc_stats = new((B, N), torch.uint8), new((B, T, 8), torch.int64), new((B, 3), torch.int64)
+    if B:
+        nbytes = lib.vkas_quad_match_ranked_workspace_bytes(B, M, N, T, max_pairs)
+        if nbytes < 0:
+            check(-1, what)
+        ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+        host_thrs = (ctypes.c_double * T)(*thrs)  # read by the launcher before it returns
+        check(lib.vkas_quad_match_ranked(_p(gt_rows), _p(gt_count), _p(gt_care), _p(pred_rows), _p(pred_count), _p(probs), B, M,
+                                         N, ctypes.cast(host_thrs, ctypes.c_void_p), T, cover_thr, max_pairs, _p(ws),
+                                         ws.numel(), _p(pred_match), _p(pred_state), _p(gt_match), _p(pred_iou), _p(covered),
+                                         _p(stats), _p(dc_stats), _p(rounds), _stream()), what)
+    return pred_match, pred_state, gt_match, pred_iou, covered, stats, dc_stats
+
+
 def quad_rows(quads: torch.Tensor, valid: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``inferencing.match_rows`` on the device (csrc/quadmatch.hip): ``quads`` (B, K, 4, 2) float64 ``(y, x)`` corners and an
     optional ``valid`` (B, K) uint8 on the device -> (B, K, 16) int32 match rows, equal to the host's on every input (an
