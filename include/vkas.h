@@ -100,7 +100,9 @@ int vkas_pack_conv_weight(const float* w, void* out, int N, int C, int KH, int K
                           int dtype, void* stream);
 /* the same for one of several convolutions that share their input and are packed side by side (the heads of a pass,
  * adaptive_scaling.py:150-152,163-170): fills output channels [n_off, n_off + Np) of an operand with Nt output channels
- * in total; mode 0 (forward) or 1 (dgrad). */
+ * in total; mode 0 (forward), 1 (dgrad) or 3: the rows image (KH, Nt, KW, Cp) - per kernel row ky a 1 x KW convolution whose
+ * output channel ky * Nt + n is kernel row ky of output channel n (the operand of the heads' forward at the neck's height,
+ * vkas_head_rows_fwd). */
 int vkas_pack_conv_weight_slice(const float* w, void* out, int N, int C, int KH, int KW, int Np, int Cp, int mode,
                                 int n_off, int Nt, int dtype, void* stream);
 /* gw (Np, KH, KW, Cp) fp32 [wgrad output] -> grad (N,C,KH,KW) fp32, grad += (accumulate != 0) or = */
@@ -271,6 +273,16 @@ int vkas_pack_head_params(const float* gamma, const float* beta, const float* wp
  * bias, written by a VKAS_EPI_NONE launch; hd->proj (n_heads, M, 8) and hd->stats (n_heads, M, 2; NULL = not kept) as
  * VKAS_EPI_HEAD writes them. */
 int vkas_head_tail_fwd(const void* z, long ldz, const vkas_head_desc* hd, long M, int dtype, void* stream);
+/* Forward of the x2 bilinear heads at the neck's height (upernext.py:237-244 followed by :215-223), z = b + conv3x3(U x) with
+ * U = Uy (x) Ux: X1 = Ux x (vkas_resize2x_x_fwd); T (B, h, W2, 3 Nt) = the 1x3 row convolution of X1 with the mode-3 weight
+ * image, column ky * Nt + n (vkas_conv_gemm_fwd with KH = 1, KW = 3, pad 1: the pad applies along x only, Hout = Hin; 16-bit
+ * row-slab kernel, W2 % 256 == 0); this call forms z[r] = bias + sum_ky (Uy T_ky)[r + ky - 1] (tap rows outside [0, 2h) are the
+ * convolution's zero padding) and runs the head tail on it.  z (B, 2h, W2, Nt) dense, or NULL together with hd->stats
+ * (inference); hd->n0 count from column 0 of the Nt; hd->proj (n_heads, M, 8), hd->stats (n_heads, M, 2), M = B 2h W2, as
+ * VKAS_EPI_HEAD writes them; pw <= 256.  seg_rows: source rows a workgroup walks down, 0 = the built-in rule; the results
+ * do not depend on it.  Fixed summation order, no atomics: two launches give the same bits. */
+int vkas_head_rows_fwd(const void* T, const float* bias, const vkas_head_desc* hd, void* z, int B, int h, int W2, int Nt,
+                       int seg_rows, int dtype, void* stream);
 /* backward of the fused tail for all heads of the launch at once: z / dz are the shared (M, sum np) buffers (strides ldz,
  * lddz), hd the descriptor used in the forward (params, stats; proj unused), dproj[h] the (M, 8) fp32 gradients of head
  * h's projection outputs -> dz and dparams[n_heads][6*pw + 8] (same layout as the packed parameters). */
@@ -291,6 +303,9 @@ size_t vkas_scale_res_bwd_ws_bytes(long M, int Cp);
    where the exact quotient is an integer).  accumulate != 0: y += resize(x) (top-down add). */
 int vkas_resize_fwd(const void* x, long ldx, void* y, long ldy, int B, int Hin, int Win, int Hout, int Wout,
                     int Cp, int mode, int accumulate, int dtype, void* stream);
+/* y (B, H, 2 Win, Cp) = the x2 bilinear upsample of x (B, H, Win, Cp) along x only, with vkas_resize_fwd's arithmetic per
+ * output (one rounded product, one fused multiply-add, one rounding to `dtype`); Win > 1 */
+int vkas_resize2x_x_fwd(const void* x, long ldx, void* y, long ldy, int B, int H, int Win, int Cp, int dtype, void* stream);
 /* dx (+)= resize^T(dy) */
 int vkas_resize_bwd(const void* dy, long lddy, void* dx, long lddx, int B, int Hin, int Win, int Hout, int Wout,
                     int Cp, int mode, int accumulate, int dtype, void* stream);
@@ -436,6 +451,10 @@ int vkas_points_gather_rows(const void* z, long ldz, int c0, int Ns, const float
  * activation operand of a 1x1 weight-gradient GEMM whose result has the 3x3 convolution's packed (N, ky, kx, Cp) layout. */
 int vkas_points_gather_patches(const void* x, long ldx, int Cp, int B, int H, int W, const int* pix, long Mp, void* xs,
                                int dtype, void* stream);
+/* the same patches of the x2 bilinear upsample of x (B, h, w, Cp) without materialising it: pix are pixels of the 2h x 2w map
+ * (vkas_points_prepare with H = 2h, W = 2w); bit for bit what vkas_points_gather_patches reads from vkas_resize_fwd's output */
+int vkas_points_gather_patches_up2(const void* x, long ldx, int Cp, int B, int h, int w, const int* pix, long Mp, void* xs,
+                                   int dtype, void* stream);
 /* D (Mp, 3, 3, Cp) fp32: D[i][ky][kx] is the input-gradient contribution of point i to pixel p_i + (ky-1, kx-1).  Adds them onto
  * dx (B,H,W,Cp; ld lddx): every touched pixel is summed in fp32 by one workgroup and written once.  Only the owners' rows of D
  * (pix[i] >= 0) are read: the rows of duplicates and of padding may hold anything. */

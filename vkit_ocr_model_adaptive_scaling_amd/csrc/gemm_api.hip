@@ -39,7 +39,8 @@ int vkas_check_geom(const char* who, const void* x, const vkas_conv_geom* g, int
   VKAS_CHECK(g->Cp > 0 && g->Cp % 8 == 0, "%s: Cp=%d must be a positive multiple of 8", who, g->Cp);
   VKAS_CHECK(g->ldx >= g->Cp && g->ldx % 8 == 0, "%s: ldx=%d must be >= Cp and a multiple of 8", who, g->ldx);
   VKAS_CHECK(g->KH > 0 && g->KW > 0 && g->stride > 0 && g->pad >= 0, "%s: bad kernel geometry", who);
-  VKAS_CHECK((g->Hin + 2 * g->pad - g->KH) / g->stride + 1 == g->Hout &&
+  const int pad_y = g->KH == 1 && g->KW == 3 ? 0 : g->pad;  // the 1x3 row convolution pads along x only
+  VKAS_CHECK((g->Hin + 2 * pad_y - g->KH) / g->stride + 1 == g->Hout &&
                  (g->Win + 2 * g->pad - g->KW) / g->stride + 1 == g->Wout,
              "%s: output size %dx%d inconsistent with input %dx%d k=%dx%d s=%d p=%d", who, g->Hout, g->Wout, g->Hin,
              g->Win, g->KH, g->KW, g->stride, g->pad);
@@ -95,6 +96,9 @@ extern "C" int vkas_conv_gemm_fwd(const void* x, const vkas_conv_geom* g, const 
   if (epi->mode == VKAS_EPI_HEAD)
     VKAS_CHECK((dtype == VKAS_BF16 || dtype == VKAS_F16) && !force_simple() && (long)g->B * g->Hout * g->Wout >= 16384,
                "vkas_conv_gemm_fwd: the fused head epilogue exists for the 16-bit MFMA kernels (M >= 16384) only");
+  if (g->KH == 1 && g->KW == 3)
+    VKAS_CHECK((dtype == VKAS_BF16 || dtype == VKAS_F16) && !force_simple() && epi->mode == VKAS_EPI_NONE,
+               "vkas_conv_gemm_fwd: the 1x3 row convolution exists for the 16-bit MFMA kernels with the plain epilogue only");
   if (dtype == VKAS_BF16 && !force_simple()) return vkas_gemm_nt_mfma_bf16(x, g, Bw, Np, epi, vkas_stream(stream));
   if (dtype == VKAS_F16 && !force_simple()) return vkas_gemm_nt_mfma_f16(x, g, Bw, Np, epi, vkas_stream(stream));
   return vkas_gemm_nt_simple(x, g, Bw, Np, epi, dtype, vkas_stream(stream));
@@ -117,7 +121,8 @@ extern "C" int vkas_conv_gemm_plan(int wgrad, const vkas_conv_geom* g, int Np, l
     const vkas_nt_plan p = vkas_plan_nt(*g, Np, head_width, sw ? *sw : *vkas_gemm_env_switches());
     const long tiles = p.grid_m * p.grid_n;
     o = {vkas_nt_kernel_id(p), p.family, p.bn, p.ring, p.buf, p.head, 0, 0, 0, p.grid_m, p.grid_n, tiles, 1, 0, p.a_bytes, p.b_bytes, (unsigned)tiles, ""};
-    if (p.family == VKAS_NT_SLAB) snprintf(o.name, sizeof(o.name), "conv3x3_slab_mfma_kernel<%d,%d>", p.bn / 32, (int)p.head);
+    if (p.family == VKAS_NT_SLAB && p.kh == 1) snprintf(o.name, sizeof(o.name), "conv1x3_slab_mfma_kernel<%d>", p.bn / 32);
+    else if (p.family == VKAS_NT_SLAB) snprintf(o.name, sizeof(o.name), "conv3x3_slab_mfma_kernel<%d,%d>", p.bn / 32, (int)p.head);
     else if (p.family == VKAS_NT_RING) snprintf(o.name, sizeof(o.name), "gemm_nt_ring_kernel<%d>", p.ring);
     else snprintf(o.name, sizeof(o.name), "gemm_nt_mfma_kernel<%s,4,%d>", p.family == VKAS_NT_REG128 ? "2,2" : "4,2", p.bn / 32);
   }
@@ -142,6 +147,7 @@ static int conv_gemm_wgrad(const char* who, const void* x, const vkas_conv_geom*
   if (rc) return rc;
   VKAS_CHECK(dy && vkas_aligned16(dy) && lddy >= Np && lddy % 8 == 0, "%s: bad dy (lddy=%ld)", who, lddy);
   VKAS_CHECK(gw, "%s: null gw", who);
+  VKAS_CHECK(!(g->KH == 1 && g->KW == 3), "%s: the 1x3 row convolution has no weight-gradient kernel", who);
   if (dtype == VKAS_BF16 && !force_simple())
     return vkas_gemm_tn_mfma_bf16(x, g, dy, lddy, Np, gw, gb, x_gelu, vkas_stream(stream));
   if (dtype == VKAS_F16 && !force_simple())

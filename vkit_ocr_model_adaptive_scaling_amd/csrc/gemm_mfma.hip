@@ -695,7 +695,9 @@ constexpr int SLAB = 264 * BK;  // rows 0..255 tile pixels, 256 / 257 left / rig
 typedef __attribute__((address_space(3))) elem_t lds_elem;
 typedef __attribute__((address_space(3))) elem8 lds_elem8;
 
-template <int TN, bool HEAD, int BNT>
+// KH = 3: the 3x3 convolution.  KH = 1: a 1x3 convolution along image rows (zero padded along x only) - the steps are the
+// channel blocks alone, the slab is the tile's own image row, the weights are [n][kx][c] with K = 3 Cp.
+template <int TN, bool HEAD, int BNT, int KH = 3>
 __device__ __forceinline__ void conv3x3_slab_body(const elem_t* __restrict__ x, const vkas_conv_geom& g,
                                                   const elem_t* __restrict__ Bw, int Np, long M, int K,
                                                   const vkas_epilogue& e, unsigned a_bytes, unsigned b_bytes,
@@ -707,6 +709,8 @@ __device__ __forceinline__ void conv3x3_slab_body(const elem_t* __restrict__ x, 
   constexpr int NBQ = (NWI + 7) / 8;         // ... per wave (waves >= RAG issue one less when NWI % 8 != 0)
   constexpr int RAG = NWI % 8;
   constexpr unsigned OOB = 0xFFFFFFF0u;
+  constexpr int YO = KH == 3 ? 1 : 0;  // image rows between the tile's row and the slab of ky = 0
+  static_assert(KH == 3 || (KH == 1 && !HEAD), "3x3, or 1x3 rows with the plain epilogue");
   static_assert(TM * 16 * (BN + 4) * 4 + (7 * 224 + 8) * 4 <= (2 * SLAB + 3 * BT) * 2, "epilogue staging must fit");
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -729,7 +733,7 @@ __device__ __forceinline__ void conv3x3_slab_body(const elem_t* __restrict__ x, 
   const unsigned row_pitch = (unsigned)W * (unsigned)g.ldx * 2u;  // bytes between image rows
   // one base offset per operand; the per-instruction offsets are scalar multiples added at the point of use (the
   // kernel lives at the VGPR limit: keeping 4 + 4 hoisted copies spills, and a scratch reload drains the DMA queue)
-  const unsigned a_base = ((unsigned)((bimg * H + oy - 1) * W + ox0 + wave * 8 + lr) * (unsigned)g.ldx + (unsigned)(cl * 8)) * 2u;
+  const unsigned a_base = ((unsigned)((bimg * H + oy - YO) * W + ox0 + wave * 8 + lr) * (unsigned)g.ldx + (unsigned)(cl * 8)) * 2u;
   const unsigned a_qstep = 64u * (unsigned)g.ldx * 2u;  // 64 slab rows further
   // halo: lanes 0, 1 of wave w carry chunks 2w, 2w+1 of the 16 halo chunks (row 256: pixel ox0-1, row 257: ox0+256)
   const int hc = wave * 2 + (lane & 1);
@@ -737,7 +741,7 @@ __device__ __forceinline__ void conv3x3_slab_body(const elem_t* __restrict__ x, 
   const int hcl = (hc & 7) ^ hrow;
   const int hpix = hrow == 0 ? ox0 - 1 : ox0 + BM;
   const bool h_ok = (unsigned)hpix < (unsigned)W;
-  const unsigned h_off = ((unsigned)((bimg * H + oy - 1) * W + hpix) * (unsigned)g.ldx + (unsigned)(hcl * 8)) * 2u;
+  const unsigned h_off = ((unsigned)((bimg * H + oy - YO) * W + hpix) * (unsigned)g.ldx + (unsigned)(hcl * 8)) * 2u;
   const int b_row = wave * 8 + lr;                       // row of this lane in its first weight instruction
   const int b_rows = (n_end - n0 < BN) ? n_end - n0 : BN;  // valid rows of the weight tile
   const unsigned b_base = ((unsigned)(n0 + b_row) * (unsigned)K + (unsigned)(cl * 8)) * 2u;
@@ -748,7 +752,7 @@ __device__ __forceinline__ void conv3x3_slab_body(const elem_t* __restrict__ x, 
 
   // slab part `part` (0, 1: wave instructions {0,1} / {2,3} of the tile rows; 2: halo) of step (ky, cb) -> slab sb
   auto issue_a = [&](int part, int ky, int cb, int sb) {
-    const bool row_ok = (unsigned)(oy - 1 + ky) < (unsigned)H;
+    const bool row_ok = KH == 1 || (unsigned)(oy - 1 + ky) < (unsigned)H;
     const unsigned step_off = (unsigned)ky * row_pitch + (unsigned)cb * 128u;
     lds_elem* dst = lds + sb * SLAB;
     if (part < 2) {
@@ -801,7 +805,7 @@ __device__ __forceinline__ void conv3x3_slab_body(const elem_t* __restrict__ x, 
   }
 
   const int NCB = (Cp + 63) >> 6;
-  const int NS = 3 * NCB;  // steps (ky, cb); three kx sub-steps each
+  const int NS = KH * NCB;  // steps (ky, cb); three kx sub-steps each
   issue_a(0, 0, 0, 0);
   issue_a(1, 0, 0, 0);
   issue_a(2, 0, 0, 0);
@@ -833,7 +837,7 @@ __device__ __forceinline__ void conv3x3_slab_body(const elem_t* __restrict__ x, 
     // With ky outermost (round 1) those uses were a third of the K loop apart and the row had left the 4 MB L2 in
     // between: rocprofv3 showed 13.3 GB per dgrad launch against ~5 GB of operands.
     int ky1 = ky + 1, cb1 = cb;
-    if (ky1 == 3) { ky1 = 0; cb1 = cb + 1; }
+    if (ky1 == KH) { ky1 = 0; cb1 = cb + 1; }
     const lds_elem* As = lds + sb * SLAB;
     auto sub = [&](auto kxc) {
       constexpr int kx = decltype(kxc)::value;
@@ -953,6 +957,21 @@ __global__ __launch_bounds__(512) void conv3x3_slab_mfma_kernel(const elem_t* __
     }
   }
   conv3x3_slab_body<TN, HEAD, BN>(x, g, Bw, Np, M, K, e, a_bytes, b_bytes, (lds_elem*)lds, tile, ntile_n);
+}
+
+// The 1x3 row form of the body above, plain epilogue: T = conv1x3(X1) of the heads' forward at the neck's height.
+template <int TN>
+__global__ __launch_bounds__(512) void conv1x3_slab_mfma_kernel(const elem_t* __restrict__ x, vkas_conv_geom g,
+                                                                const elem_t* __restrict__ Bw, int Np, long M, int K,
+                                                                vkas_epilogue e, unsigned a_bytes, unsigned b_bytes) {
+  constexpr int BN = 32 * TN;
+  __shared__ __attribute__((aligned(1024))) elem_t lds[2 * SLAB + 3 * BN * BK];
+  const unsigned ntile_n = (unsigned)((Np + BN - 1) / BN);
+  const unsigned total = gridDim.x;
+  const unsigned xcd = blockIdx.x & 7u, slot8 = blockIdx.x >> 3;
+  const unsigned q8 = total >> 3, r8 = total & 7u;
+  const unsigned tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + slot8;
+  conv3x3_slab_body<TN, false, BN, 1>(x, g, Bw, Np, M, K, e, a_bytes, b_bytes, (lds_elem*)lds, tile, ntile_n);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1634,6 +1653,18 @@ int VKAS_MFMA_FN(vkas_gemm_nt_mfma)(const void* x, const vkas_conv_geom* g, cons
   case nt_case(VKAS_NT_TILE256, TNV, false, false): VKAS_GO(512, gemm_nt_mfma_kernel<4, 2, 4, TNV, false, false>) \
   case nt_case(VKAS_NT_SLAB, TNV, true, true): VKAS_GO(512, conv3x3_slab_mfma_kernel<TNV, true>)                \
   case nt_case(VKAS_NT_SLAB, TNV, true, false): VKAS_GO(512, conv3x3_slab_mfma_kernel<TNV, false>)
+  if (p.kh == 1) {  // the 1x3 row convolution exists on the row slab only
+    VKAS_CHECK(p.family == VKAS_NT_SLAB && !head, "gemm_nt_mfma: a 1x3 row convolution needs stride 1, pad 1, rows of whole 256-pixel "
+               "tiles, operands below 4 GiB and a plain epilogue");
+    switch (p.bn / 32) {
+      case 4: VKAS_GO(512, conv1x3_slab_mfma_kernel<4>)
+      case 6: VKAS_GO(512, conv1x3_slab_mfma_kernel<6>)
+      case 7: VKAS_GO(512, conv1x3_slab_mfma_kernel<7>)
+      default: VKAS_CHECK(false, "gemm_nt_mfma: no 1x3 row kernel for N extent %d", p.bn);
+    }
+    VKAS_LAUNCH_CHECK("conv1x3_slab_mfma");
+    return VKAS_OK;
+  }
   switch (nt_case(p.family, p.family == VKAS_NT_RING ? p.ring : p.bn / 32, p.buf, p.head)) {
     VKAS_TILE(4) VKAS_TILE(6) VKAS_TILE(7)
     case nt_case(VKAS_NT_REG128, 4, true, false): VKAS_GO(256, gemm_nt_mfma_kernel<2, 2, 4, 4, true, false>)

@@ -13,6 +13,7 @@ struct vkas_nt_plan {
   vkas_nt_family family;  // register-staged 128x128 | gemm_nt_ring_kernel | 256-row 8-wave tile | conv3x3_slab_mfma_kernel
   int bn;                 // N extent of the tile: 128 / 192 / 224
   int ring;               // ring depth 2 / 3 / 4 (VKAS_NT_RING), else 0
+  int kh;                 // 1: the 1x3 row convolution (row slab only; any other family: no kernel), else 3
   bool buf, head;         // operands addressed with 32-bit buffer offsets; fused head epilogue
   long a_bytes, b_bytes;  // bytes spanned by x and Bw
   long grid_m, grid_n;    // the grid is grid_m x (a fused-head launch: the number of heads, else grid_n) workgroups
@@ -47,6 +48,6 @@ vkas_tn_plan vkas_plan_tn(const vkas_conv_geom& g, int Np, long lddy, int flags,
 
 // the values of vkas_conv_gemm_kernel_id (include/vkas.h)
 inline int vkas_nt_kernel_id(const vkas_nt_plan& p) {
-  return p.family == VKAS_NT_SLAB ? 1000 + p.bn / 32 : (p.family == VKAS_NT_RING ? 10 + p.ring : (p.family == VKAS_NT_REG128 ? 1 : p.bn));
+  return p.family == VKAS_NT_SLAB ? (p.kh == 1 ? 1100 : 1000) + p.bn / 32 : (p.family == VKAS_NT_RING ? 10 + p.ring : (p.family == VKAS_NT_REG128 ? 1 : p.bn));
 }
 inline int vkas_tn_kernel_id(const vkas_tn_plan& p) { return p.family == VKAS_TN_SLAB ? 2000 + p.tile / 16 : p.tile; }

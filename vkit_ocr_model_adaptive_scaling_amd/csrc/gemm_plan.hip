@@ -56,6 +56,22 @@ vkas_nt_plan vkas_plan_nt(const vkas_conv_geom& g, int Np, int head_width, const
   p.a_bytes = vkas_span_bytes((long)g.B * g.Hin * g.Win, g.ldx, g.Cp);
   p.b_bytes = (long)Np * K * 2;
   const bool fits = vkas_fits_buffer(p.a_bytes) && vkas_fits_buffer(p.b_bytes);
+  p.kh = 3;
+  if (g.KH == 1 && g.KW == 3) {
+    // 1x3 along image rows (pad applies to x alone): conv1x3_slab_mfma_kernel, 256-row tiles whatever M is; the family says
+    // whether the geometry is one the kernel takes
+    p.kh = 1;
+    // N extent: 224 or 192, whichever pads less; the 128-column tile only for launches it holds in one tile (it pads the
+    // precise heads' N = 2 328 least, but ran them in 5.87 ms against 5.30 ms with 224 columns); VKAS_NT_TILE overrides
+    const int f = sw.nt_tile;
+    p.bn = f == 128 || f == 192 || f == 224 ? f : (Np <= 128 ? 128 : (padded(Np, 192) < padded(Np, 224) ? 192 : 224));
+    p.grid_n = cdiv(Np, p.bn);
+    p.grid_m = M / 256;
+    const bool rows = g.stride == 1 && g.pad == 1 && g.Hout == g.Hin && g.Wout == g.Win && g.Win % 256 == 0;
+    p.family = rows && fits && !p.head ? VKAS_NT_SLAB : VKAS_NT_TILE256;
+    p.buf = true;
+    return p;
+  }
   // one 256-row tile per head: the narrowest N extent that holds the widest head
   const int choice = p.head ? (head_width <= 128 ? 128 : (head_width <= 192 ? 192 : 224)) : vkas_nt_tile_rule(M, Np, sw);
   p.bn = choice == 1 ? 128 : choice;

@@ -373,6 +373,172 @@ __global__ __launch_bounds__(256) void head_tail_fwd_kernel(const T* __restrict_
   }
 }
 
+// Heads' forward at the neck's height: T (B, h, W2, 3 Nt) = the 1x3 row convolution of Ux x, column ky * Nt + n, holds per
+// kernel row ky the convolution's sums BEFORE the y half of the x2 bilinear upsample.  This pass applies that half and the 3x3's
+// sum over ky, z[r] = bias + sum_ky (Uy T_ky)[r + ky - 1] (a tap row outside [0, 2h) is the convolution's zero padding, not a
+// clamped row), stores z as the fused epilogue does and runs the same tail on the unrounded sums (LayerNorm statistics from
+// E[z^2] - mean^2, polynomial GELU, projection; pad columns are exact zeros).  A lane group (32 lanes, one 8-channel vector
+// each) keeps its column and head and walks down the source rows of a segment: the output rows 2i, 2i + 1 read the T rows
+// i - 1, i, i + 1, held as a rolling window with the row after them already requested, so a T element crosses the vector-memory
+// path once per segment (+ 3 rows at its ends).  Fixed order: bias, then ky ascending, each blend one rounded product and one
+// fmaf (the arithmetic of resize2x_fwd_kernel along y); no atomics.
+struct HeadRowsArgs {
+  int n_heads, pw;
+  int n0[4], np[4], c[4], oc[4];
+};
+__device__ __forceinline__ float blend2(float a, float b, float w) { return fmaf(b, w, __fmul_rn(a, 1.f - w)); }
+
+template <typename T, int NH>
+__global__ __launch_bounds__(256) void head_rows_fwd_kernel(const T* __restrict__ Tt, const float* __restrict__ bias,
+                                                            const float* __restrict__ params, T* __restrict__ z,
+                                                            float* __restrict__ stats, float* __restrict__ proj, HeadRowsArgs a,
+                                                            int h, int W2, int Nt, int seg, int nseg, long M, int ocm) {
+  constexpr int G = 32, GW = G * 8;
+  constexpr int CPB = 256 / G / NH;  // pixel columns per workgroup
+  const int gl = threadIdx.x & (G - 1);
+  const int grp = threadIdx.x / G;
+  const int head = grp % NH, cl = grp / NH;
+  const bool hok = head < a.n_heads;
+  const int pw = a.pw, PS = 6 * pw + 8;
+  const int C = hok ? a.c[head] : 1, np = hok ? a.np[head] : 0, n0 = hok ? a.n0[head] : 0;
+  const bool vok = hok && gl < (np >> 3);
+  // gamma | beta | Wproj[4] of every head, each GW floats and zero beyond pw, then bproj: full-wave 16-byte reads (see the
+  // backward kernel above)
+  __shared__ __attribute__((aligned(16))) float sp[NH * (6 * GW + 8)];
+  for (int i = threadIdx.x; i < NH * (6 * GW + 8); i += 256) {
+    const int hh = i / (6 * GW + 8), r = i - hh * (6 * GW + 8);
+    float v = 0.f;
+    if (hh < a.n_heads) {
+      if (r < 6 * GW) {
+        const int k = r / GW, j = r - k * GW;
+        if (j < pw) v = params[(long)hh * PS + k * pw + j];
+      } else {
+        v = params[(long)hh * PS + 6 * pw + (r - 6 * GW)];
+      }
+    }
+    sp[i] = v;
+  }
+  __syncthreads();
+  const float* hp = sp + head * (6 * GW + 8);
+  const int cblocks = (W2 + CPB - 1) / CPB;
+  long bx = blockIdx.x;
+  const int cbk = (int)(bx % cblocks);
+  bx /= cblocks;
+  const int sgi = (int)(bx % nseg);
+  const long b = bx / nseg;
+  const int X = cbk * CPB + cl;
+  const bool xok = X < W2;
+  const int i0 = sgi * seg, i1 = i0 + seg < h ? i0 + seg : h;
+  float bs[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) bs[c] = 0.f;
+  if (vok) load8(bias + n0 + gl * 8, bs);
+  const long ldT = 3L * Nt;
+  // unconditional loads from clamped addresses (column clamped into the row, a lane beyond the head's width reads the head's
+  // first slice, a row beyond the image its last row); what must not be used is zeroed or skipped afterwards
+  const T* tcol = Tt + ((long)b * h * W2 + (xok ? X : W2 - 1)) * ldT + n0 + (vok ? gl : 0) * 8;
+  const long rowT = (long)W2 * ldT;
+  Raw8<T> win[4][3];  // rows i - 1, i, i + 1, i + 2 (rotating), per ky
+  auto fetch = [&](Raw8<T> (&r)[3], int i) {
+    const int ic = i < 0 ? 0 : (i > h - 1 ? h - 1 : i);
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) r[ky].load(tcol + ic * rowT + ky * Nt);
+  };
+  fetch(win[0], i0 - 1);
+  fetch(win[1], i0);
+  fetch(win[2], i0 + 1);
+  T* zcol = z ? z + n0 + gl * 8 : nullptr;
+  auto tail = [&](float (&v)[8], int r) {
+    const long m = ((long)b * 2 * h + r) * W2 + X;
+    float s = 0.f, q = 0.f;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      s += v[c];
+      q = fmaf(v[c], v[c], q);
+    }
+    s = group_sum<G>(s);
+    q = group_sum<G>(q);
+    const float mean = s / (float)C;
+    q = fmaxf(q - s * mean, 0.f);  // sum of squared deviations
+    const float rstd = rsqrtf(q / (float)C + 1e-6f);
+    if (zcol && xok && vok) store8(zcol + m * Nt, v);
+    int lo = gl * 8;
+    asm volatile("" : "+v"(lo));  // keeps the parameter reads in the loop
+    float gm[8], bt[8];
+    load8(hp + lo, gm);
+    load8(hp + GW + lo, bt);
+    f32x2 act[4];
+    const f32x2 rs2 = pk_splat(rstd), mu2 = pk_splat(mean);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const f32x2 t = (f32x2{v[2 * c], v[2 * c + 1]} - mu2) * rs2;
+      act[c] = gelu2_t<T>(pk_fma(t, f32x2{gm[2 * c], gm[2 * c + 1]}, f32x2{bt[2 * c], bt[2 * c + 1]}));  // pad: gamma = beta = 0
+    }
+    float pr[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int qq = 0; qq < 4; ++qq) {
+      if (qq >= ocm) break;  // launch-uniform: the widest projection of the pass (a narrower head's further rows are zero)
+      float w[8];
+      load8(hp + (2 + qq) * GW + lo, w);
+      f32x2 p2 = {0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < 4; ++c) p2 = pk_fma(act[c], f32x2{w[2 * c], w[2 * c + 1]}, p2);
+      pr[qq] = group_sum<G>(p2.x + p2.y);
+    }
+    if (gl == 0 && hok && xok) {
+      const float4 bp = *reinterpret_cast<const float4*>(hp + 6 * GW);
+      float* po = proj + ((long)head * M + m) * 8;
+      *reinterpret_cast<float4*>(po) = make_float4(pr[0] + bp.x, pr[1] + bp.y, pr[2] + bp.z, pr[3] + bp.w);
+      *reinterpret_cast<float4*>(po + 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (stats) {
+        float* st = stats + ((long)head * M + m) * 2;
+        st[0] = mean;
+        st[1] = rstd;
+      }
+    }
+  };
+  auto rows = [&](Raw8<T> (&P)[3], Raw8<T> (&Cc)[3], Raw8<T> (&N)[3], int i) {
+    float p0[8], p1[8], c0[8], c1[8], c2[8], q0[8], q1[8], q2[8];
+    P[0].unpack(p0); P[1].unpack(p1);
+    Cc[0].unpack(c0); Cc[1].unpack(c1); Cc[2].unpack(c2);
+    N[0].unpack(q0); N[1].unpack(q1); N[2].unpack(q2);
+    const bool top = i == 0, bot = i + 1 >= h;  // workgroup-uniform
+    float v[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {  // output row 2i: tap rows 2i - 1, 2i, 2i + 1
+      float t = bs[c];
+      if (!top) t += blend2(p0[c], c0[c], 0.25f);
+      t += top ? blend2(c1[c], q1[c], 0.f) : blend2(p1[c], c1[c], 0.75f);
+      t += blend2(c2[c], q2[c], 0.25f);
+      v[c] = vok ? t : 0.f;
+    }
+    tail(v, 2 * i);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {  // output row 2i + 1: tap rows 2i, 2i + 1, 2i + 2
+      float t = bs[c];
+      t += top ? blend2(c0[c], q0[c], 0.f) : blend2(p0[c], c0[c], 0.75f);
+      t += blend2(c1[c], q1[c], 0.25f);
+      if (!bot) t += blend2(c2[c], q2[c], 0.75f);
+      v[c] = vok ? t : 0.f;
+    }
+    tail(v, 2 * i + 1);
+  };
+  // the window rotates through four register sets: four source rows per trip keep every index a compile-time constant
+  for (int i = i0; i < i1; i += 4) {
+    fetch(win[3], i + 2);
+    rows(win[0], win[1], win[2], i);
+    if (i + 1 >= i1) break;
+    fetch(win[0], i + 3);
+    rows(win[1], win[2], win[3], i + 1);
+    if (i + 2 >= i1) break;
+    fetch(win[1], i + 4);
+    rows(win[2], win[3], win[0], i + 2);
+    if (i + 3 >= i1) break;
+    fetch(win[2], i + 5);
+    rows(win[3], win[0], win[1], i + 3);
+  }
+}
+
 static inline int ht_lanes(int pw) { return pw <= 256 ? 32 : 64; }
 static inline long ht_rows_per_block(long M, int G) {
   long r = vkas_cdiv(M > 0 ? M : 1, 1024);
@@ -438,6 +604,60 @@ extern "C" int vkas_head_tail_fwd(const void* z, long ldz, const vkas_head_desc*
   })
 #undef VKAS_HF
   VKAS_LAUNCH_CHECK("head_tail_fwd");
+  return VKAS_OK;
+}
+
+extern "C" int vkas_head_rows_fwd(const void* Tt, const float* bias, const vkas_head_desc* hd, void* z, int B, int h, int W2,
+                                  int Nt, int seg_rows, int dtype, void* stream) {
+  VKAS_CHECK(Tt && bias && hd && hd->params && hd->proj, "vkas_head_rows_fwd: null pointer");
+  const int pw = hd->pw, nh = hd->n_heads;
+  VKAS_CHECK(nh >= 1 && nh <= 4 && pw % 8 == 0 && pw >= 8 && pw <= 256, "vkas_head_rows_fwd: bad descriptor (pw <= 256)");
+  VKAS_CHECK(B >= 0 && h > 0 && W2 > 0 && Nt > 0 && Nt % 8 == 0 && seg_rows >= 0, "vkas_head_rows_fwd: bad sizes");
+  VKAS_CHECK((hd->stats != nullptr) == (z != nullptr), "vkas_head_rows_fwd: z and the statistics are kept or dropped together");
+  HeadRowsArgs a;
+  a.n_heads = nh;
+  a.pw = pw;
+  int ocm = 1;
+  for (int k = 0; k < 4; ++k) {
+    a.n0[k] = k < nh ? hd->n0[k] : 0;
+    a.np[k] = k < nh ? hd->np[k] : 0;
+    a.c[k] = k < nh ? hd->c[k] : 1;
+    a.oc[k] = k < nh ? hd->oc[k] : 0;
+    if (k < nh) {
+      VKAS_CHECK(a.np[k] % 8 == 0 && a.np[k] > 0 && a.np[k] <= pw && a.c[k] > 0 && a.c[k] <= a.np[k] && a.n0[k] % 8 == 0 &&
+                     a.n0[k] >= 0 && a.n0[k] + a.np[k] <= Nt && a.oc[k] >= 1 && a.oc[k] <= 4,
+                 "vkas_head_rows_fwd: bad head %d", k);
+      ocm = a.oc[k] > ocm ? a.oc[k] : ocm;
+    }
+  }
+  VKAS_CHECK(vkas_aligned16(Tt) && vkas_aligned16(bias) && vkas_aligned16(z) && vkas_aligned16(hd->params) && vkas_aligned16(hd->proj),
+             "vkas_head_rows_fwd: misaligned pointer");
+  if (B == 0) return VKAS_OK;
+  const int NH = nh == 1 ? 1 : (nh == 2 ? 2 : 4);
+  const int cpb = 256 / 32 / NH;
+  // segments of source rows: 32, shorter while the launch has fewer than ~4096 workgroups, never below 8 (three extra rows each)
+  int seg = seg_rows > 0 ? (seg_rows < h ? seg_rows : h) : (h < 32 ? h : 32);
+  const long cols = (long)B * vkas_cdiv(W2, cpb);
+  while (seg_rows == 0 && seg > 8 && cols * vkas_cdiv(h, seg) < 4096) seg = (seg + 1) / 2;
+  const int nseg = (int)vkas_cdiv(h, seg);
+  const long blocks = cols * nseg;
+  VKAS_CHECK(blocks < (1L << 31), "vkas_head_rows_fwd: too many workgroups");
+  const long M = (long)B * 2 * h * W2;
+  hipStream_t st = vkas_stream(stream);
+#define VKAS_HR(NHV)                                                                                                          \
+  head_rows_fwd_kernel<T, NHV><<<(unsigned)blocks, 256, 0, st>>>((const T*)Tt, bias, hd->params, (T*)z, hd->stats, hd->proj, a, h, \
+                                                                 W2, Nt, seg, nseg, M, ocm)
+  if (dtype == VKAS_BF16) {
+    typedef bf16_t T;
+    if (NH == 1) VKAS_HR(1); else if (NH == 2) VKAS_HR(2); else VKAS_HR(4);
+  } else if (dtype == VKAS_F16) {
+    typedef f16_t T;
+    if (NH == 1) VKAS_HR(1); else if (NH == 2) VKAS_HR(2); else VKAS_HR(4);
+  } else {
+    VKAS_CHECK(false, "vkas_head_rows_fwd: 16-bit storage only");
+  }
+#undef VKAS_HR
+  VKAS_LAUNCH_CHECK("head_rows_fwd");
   return VKAS_OK;
 }
 

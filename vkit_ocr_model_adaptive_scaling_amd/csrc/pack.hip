@@ -24,6 +24,12 @@ __device__ __forceinline__ float pack_conv_elem(const float* __restrict__ w, lon
     kx = KW - 1 - (int)(r % KW); r /= KW;
     ky = KH - 1 - (int)(r % KH); r /= KH;
     c = (int)r;
+  } else if (mode == 3) {  // [ky][n][kx][c]: per kernel row a 1 x KW convolution with output channel ky * Nt + n
+    c = (int)(r % Cp); r /= Cp;
+    kx = (int)(r % KW); r /= KW;
+    ky = (int)(r % KH); r /= KH;
+    n = (int)r;
+    o = (((long)ky * Nt + n_off + n) * KW + kx) * Cp + c;
   } else {  // [(ky,kx,c)][n]
     n = (int)(r % Np); r /= Np;
     c = (int)(r % Cp); r /= Cp;
@@ -283,7 +289,7 @@ extern "C" int vkas_pack_conv_weight_slice(const float* w, void* out, int N, int
   VKAS_CHECK(w && out, "vkas_pack_conv_weight_slice: null pointer");
   VKAS_CHECK(N > 0 && C > 0 && KH > 0 && KW > 0 && Np >= N && Cp >= C && Np % 8 == 0 && Cp % 8 == 0,
              "vkas_pack_conv_weight_slice: bad dims N=%d C=%d Np=%d Cp=%d", N, C, Np, Cp);
-  VKAS_CHECK(mode == 0 || mode == 1, "vkas_pack_conv_weight_slice: mode must be 0 (forward) or 1 (dgrad)");
+  VKAS_CHECK(mode == 0 || mode == 1 || mode == 3, "vkas_pack_conv_weight_slice: mode must be 0 (forward), 1 (dgrad) or 3 (rows)");
   VKAS_CHECK(n_off >= 0 && n_off % 8 == 0 && Nt % 8 == 0 && n_off + Np <= Nt, "vkas_pack_conv_weight_slice: bad slice %d + %d of %d",
              n_off, Np, Nt);
   const long total = (long)Np * KH * KW * Cp;

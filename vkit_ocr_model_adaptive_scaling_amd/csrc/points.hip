@@ -102,6 +102,51 @@ __global__ __launch_bounds__(64) void points_gather_patches_kernel(const T* __re
   }
 }
 
+// The same patches of U x (U: x2 bilinear, align_corners=False, clamped) built from x (B,h,w,Cp) itself, pix being pixels of the
+// 2h x 2w map: every patch pixel is computed with the products and sums of resize2x_fwd_kernel and rounded once to the storage
+// type, i.e. bit for bit what gathering from the materialised upsample gives.
+__device__ __forceinline__ float pt_lerp2(float a, float b, float w) { return fmaf(b, w, __fmul_rn(a, 1.f - w)); }
+// source indices and the weight of the second one for destination o of a x2 axis of n sources (the generic index function)
+__device__ __forceinline__ void pt_up2(int o, int n, int& ia, int& ib, float& w) {
+  const int i = o >> 1;
+  if (o & 1) { ia = i; ib = i + 1 < n ? i + 1 : n - 1; w = 0.25f; }
+  else if (i == 0) { ia = 0; ib = n > 1 ? 1 : 0; w = 0.f; }
+  else { ia = i - 1; ib = i; w = 0.75f; }
+}
+template <typename T>
+__global__ __launch_bounds__(64) void points_gather_patches_up2_kernel(const T* __restrict__ x, long ldx, int Cp, int h, int w,
+                                                                       const int* __restrict__ pix, T* __restrict__ xs) {
+  const long i = blockIdx.x;
+  const int p = pix[i];
+  const float zero8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const int vpt = Cp >> 3, H = 2 * h, W = 2 * w;
+  const long q = p >= 0 ? p : 0;
+  const int xx = (int)(q % W), yy = (int)((q / W) % H);
+  const long bimg = q / ((long)W * H);
+  for (int v = threadIdx.x; v < 9 * vpt; v += 64) {
+    const int t = v / vpt, cv = v - t * vpt;
+    const int Y = yy + t / 3 - 1, X = xx + t % 3 - 1;
+    const bool ok = p >= 0 && (unsigned)Y < (unsigned)H && (unsigned)X < (unsigned)W;  // zero padding of the conv
+    if (ok) {
+      int ya, yb, xa, xb;
+      float wy, wx;
+      pt_up2(Y, h, ya, yb, wy);
+      pt_up2(X, w, xa, xb, wx);
+      const T* xb0 = x + bimg * h * w * ldx + cv * 8;
+      float a00[8], a01[8], a10[8], a11[8], r[8];
+      load8(xb0 + ((long)ya * w + xa) * ldx, a00);
+      load8(xb0 + ((long)ya * w + xb) * ldx, a01);
+      load8(xb0 + ((long)yb * w + xa) * ldx, a10);
+      load8(xb0 + ((long)yb * w + xb) * ldx, a11);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) r[k] = pt_lerp2(pt_lerp2(a00[k], a01[k], wx), pt_lerp2(a10[k], a11[k], wx), wy);
+      store8(xs + (i * 9 + t) * Cp + cv * 8, r);
+    } else {
+      store8(xs + (i * 9 + t) * Cp + cv * 8, zero8);
+    }
+  }
+}
+
 // D[i][t][:] (t = ky*3 + kx) belongs to pixel pixel(i) + (ky-1, kx-1).  Several (point, tap) pairs can land on one pixel: the
 // first contributor in tap order owns it, sums all of them in fp32 and adds the sum onto dx once.
 template <typename T>
@@ -316,6 +361,20 @@ extern "C" int vkas_points_gather_patches(const void* x, long ldx, int Cp, int B
     points_gather_patches_kernel<T><<<(unsigned)Mp, 64, 0, st>>>((const T*)x, ldx, Cp, H, W, pix, (T*)xs);
   })
   VKAS_LAUNCH_CHECK("points_gather_patches");
+  return VKAS_OK;
+}
+
+extern "C" int vkas_points_gather_patches_up2(const void* x, long ldx, int Cp, int B, int h, int w, const int* pix, long Mp,
+                                              void* xs, int dtype, void* stream) {
+  VKAS_CHECK(x && pix && xs, "vkas_points_gather_patches_up2: null pointer");
+  VKAS_CHECK(Cp > 0 && Cp % 8 == 0 && ldx >= Cp && ldx % 8 == 0 && B > 0 && h > 1 && w > 1 && Mp > 0 && vkas_aligned16(x) &&
+                 vkas_aligned16(xs) && 4L * B * h * w < PT_EMPTY,
+             "vkas_points_gather_patches_up2: bad sizes Cp=%d ldx=%ld", Cp, ldx);
+  hipStream_t st = vkas_stream(stream);
+  VKAS_DISPATCH_DTYPE(dtype, "vkas_points_gather_patches_up2", {
+    points_gather_patches_up2_kernel<T><<<(unsigned)Mp, 64, 0, st>>>((const T*)x, ldx, Cp, h, w, pix, (T*)xs);
+  })
+  VKAS_LAUNCH_CHECK("points_gather_patches_up2");
   return VKAS_OK;
 }
 

@@ -311,6 +311,39 @@ __global__ __launch_bounds__(256) void resize2x_fwd_kernel(const T* __restrict__
   }
 }
 
+// The same along x only: y (B, H, 2 Win) = Ux x, the input of the heads' 1x3 row convolution (the y half of the upsample is
+// applied to that convolution's output).  Per output the x arithmetic of the kernel above - one rounded product, one fmaf - and
+// one rounding to the storage type.  A thread owns one source pixel vector and writes its two destinations.
+template <typename T>
+__global__ __launch_bounds__(256) void resize2x_x_fwd_kernel(const T* __restrict__ x, long ldx, T* __restrict__ y, long ldy,
+                                                             int Win, int nvec) {
+  const int idx = blockIdx.y * 256 + threadIdx.x;
+  const int j = idx / nvec;
+  const int v = idx - j * nvec;
+  if (j >= Win) return;
+  const long row = xcd_row(blockIdx.x, gridDim.x);  // b * H + i
+  const int jm = j > 0 ? j - 1 : 0, jp = j + 1 < Win ? j + 1 : Win - 1;
+  const T* xr = x + row * Win * ldx + v * 8;
+  float n[3][8];
+  {
+    Raw8<T> raw[3];
+    raw[0].load(xr + (long)jm * ldx);
+    raw[1].load(xr + (long)j * ldx);
+    raw[2].load(xr + (long)jp * ldx);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) raw[c].unpack(n[c]);
+  }
+  float o0[8], o1[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    o0[k] = lerp2(n[0][k], j == 0 ? n[2][k] : n[1][k], j == 0 ? 0.f : 0.75f);
+    o1[k] = lerp2(n[1][k], n[2][k], 0.25f);
+  }
+  T* dst = y + (row * 2 * Win + 2 * j) * ldy + v * 8;
+  store8(dst, o0);
+  store8(dst + ldy, o1);
+}
+
 // Backward of the same: source pixel (i, j) collects destinations 2i-1 .. 2i+2 x 2j-1 .. 2j+2 (those inside the map) with
 // the forward's weights - taken from the same index function, ascending, zero weights skipped: the sums of
 // resize_bwd_kernel bit for bit, without its range search.  (A 2 x 2 source block per thread - 9 loads per source pixel
@@ -554,6 +587,20 @@ extern "C" int vkas_resize_fwd(const void* x, long ldx, void* y, long ldy, int B
                                                                mode, accumulate);
   })
   VKAS_LAUNCH_CHECK("resize_fwd");
+  return VKAS_OK;
+}
+
+extern "C" int vkas_resize2x_x_fwd(const void* x, long ldx, void* y, long ldy, int B, int H, int Win, int Cp, int dtype,
+                                   void* stream) {
+  int rc = rs_check("vkas_resize2x_x_fwd", x, ldx, y, ldy, B, H, Win, H, 2 * Win, Cp);
+  if (rc) return rc;
+  if (B == 0) return VKAS_OK;
+  VKAS_CHECK(Win > 1 && (long)B * H < (1L << 31) && vkas_cdiv((long)Win * (Cp / 8), 256) <= 65535, "vkas_resize2x_x_fwd: bad sizes");
+  dim3 grid((unsigned)((long)B * H), (unsigned)vkas_cdiv((long)Win * (Cp / 8), 256));
+  VKAS_DISPATCH_DTYPE(dtype, "vkas_resize2x_x_fwd", {
+    resize2x_x_fwd_kernel<T><<<grid, 256, 0, vkas_stream(stream)>>>((const T*)x, ldx, (T*)y, ldy, Win, Cp / 8);
+  })
+  VKAS_LAUNCH_CHECK("resize2x_x_fwd");
   return VKAS_OK;
 }
 

@@ -937,7 +937,8 @@ def _cached_pack_multi(params: Sequence[torch.Tensor], key, build):
 
 def pack_head_weights(ws: Sequence[torch.Tensor], nps: Sequence[int], Cp: int, mode: int, dtype: torch.dtype) -> torch.Tensor:
     """The heads' 3x3 weights packed side by side (head h = output channels [n0_h, n0_h + np_h)) as one GEMM operand:
-    mode 0 forward (Nt, 3, 3, Cp), mode 1 dgrad (Cp, 3, 3, Nt).  Replaces F.pad + torch.cat of the parameters."""
+    mode 0 forward (Nt, 3, 3, Cp), mode 1 dgrad (Cp, 3, 3, Nt), mode 3 rows (3, Nt, 3, Cp): per kernel row a 1x3 convolution,
+    output channel ky * Nt + n (the forward at the neck's height).  Replaces F.pad + torch.cat of the parameters."""
     Nt = sum(nps)
 
     def build():
@@ -1066,6 +1067,16 @@ def _points_prepare(py: torch.Tensor, px: torch.Tensor, B: int, H: int, W: int):
     pmap, pix = scratch[:M], scratch[M:]
     check(lib.vkas_points_prepare(_p(py), _p(px), B, P, H, W, _p(pmap), _p(pix), Mp, _stream()), 'points_prepare')
     return scratch, pmap, pix, Mp
+
+
+def _points_gather_patches_up2(x_low: torch.Tensor, pix: torch.Tensor, Mp: int) -> torch.Tensor:
+    """the same patches of the x2 bilinear upsample of x_low (B,h,w,Cp), built from x_low itself (bit-identical); pix are
+    pixels of the 2h x 2w map"""
+    B, h, w, Cp = x_low.shape
+    xs = new_act(1, 1, Mp, 9 * Cp, x_low)
+    check(lib.vkas_points_gather_patches_up2(_p(x_low), act_ld(x_low), Cp, B, h, w, _p(pix), Mp, _p(xs), _dt(x_low), _stream()),
+          'points_gather_patches_up2')
+    return xs
 
 
 def _points_gather_patches(x: torch.Tensor, pix: torch.Tensor, Mp: int) -> torch.Tensor:
@@ -1287,6 +1298,11 @@ class HeadsFused(Function):
         x, z, stats, hp = saved[:4]
         pw, n_heads = ctx.pw, ctx.heads.n
         heads = ctx.heads.from_saved(saved[4:4 + 6 * n_heads])
+        # no_up (UpHeadsFused, forward at the neck's height): the upsample was never materialised and slot 0 holds the neck
+        # feature.  x then stands for the upsample's shape and type only (no memory behind it) until a path below reads it.
+        no_up = getattr(ctx, 'no_up', False)
+        if no_up:
+            x = x[:, :1, :1, :].expand(x.shape[0], 2 * x.shape[1], 2 * x.shape[2], x.shape[3])
         B, H, W, Cp = x.shape
         Nt, M, K, dev = heads.Nt, B * H * W, 9 * Cp, x.device
         dparams = torch.empty((n_heads, 6 * pw + 8), dtype=_FLOAT, device=dev)
@@ -1318,6 +1334,8 @@ class HeadsFused(Function):
         elif u1 == u0 and dx is not None:
             dx.zero_()
         if u1 > u0:
+            if no_up:  # a marked dense head keeps the convolution kernels at 2h x 2w: they read the upsample itself
+                x = resize_fwd(x_low, (H, W), 0)
             _heads_dense_upres(heads, u0, u1, pw, hp, x, z, stats, dps, dparams, gwp, gbp, dx_pts)
         if e1 > e0:
             _heads_dense_lowres(heads, e0, e1, pw, hp, x, z, stats, dps, dparams, gwp, gbp, x_low, dx)
@@ -1333,7 +1351,8 @@ class HeadsFused(Function):
                   'points_gather_rows')
             if pts_low and e1 == e0:
                 dx.zero_()
-            _heads_points_grads(heads, s0, s1, pw, hp, lambda: _points_gather_patches(x, pix, Mp), zs, stats_s,
+            patches = (lambda: _points_gather_patches_up2(x_low, pix, Mp)) if no_up else (lambda: _points_gather_patches(x, pix, Mp))
+            _heads_points_grads(heads, s0, s1, pw, hp, patches, zs, stats_s,
                                 [dproj_s.data_ptr() + j * Mp * 32 for j in range(s1 - s0)], pix, pmap, py.numel(), dparams,
                                 gwp[offs[s0] * K:offs[s1] * K], gbp[offs[s0]:offs[s1]], False, dx if pts_low else dx_pts, pts_low)
         if low and dx is not None and not pts_low:
@@ -1350,6 +1369,7 @@ class HeadsFused(Function):
 
 
 _HEAD_BWD_UPRES = os.environ.get('VKAS_HEAD_BWD_UPRES') is not None  # A/B switch: head backward at the upsampled resolution
+_HEAD_FWD_UPRES = os.environ.get('VKAS_HEAD_FWD_UPRES') is not None  # A/B switch: head forward at the upsampled resolution
 
 
 class UpHeadsFused(Function):
@@ -1359,6 +1379,13 @@ class UpHeadsFused(Function):
     h x w x N), the input gradient is E (M/4 x 9N) . W (9N x C) - of the neck feature directly - and the weight gradient
     E^T . x: a quarter of the products of the two convolutions at 2h x 2w, neither dx at 2h x 2w nor its U^T pass.  Same sums,
     other order; E is rounded to the storage type once.  VKAS_HEAD_BWD_UPRES=1 keeps Resize + HeadsFused (model side).
+
+    Forward at the neck's height (rows_route; VKAS_HEAD_FWD_UPRES=1 keeps the two launches above): U = Uy (x) Ux and Uy commutes
+    with what acts on columns and channels, so X1 = Ux x (B,h,2w,C), T = conv1x3(X1) with 3 Nt output channels (kernel row ky in
+    columns ky * Nt + n: half the products of the 3x3 at 2h x 2w, on the row-slab kernel) and z[r] = b + sum_ky (Uy T_ky)[r + ky
+    - 1] formed by the pass that runs the head tail (vkas_head_rows_fwd).  U x is not materialised; T (1.5 x z, rounded to the
+    storage type once) lives inside the forward only.  z, the statistics and the maps are stored as before: backward unchanged,
+    the label-point patches are built from x (vkas_points_gather_patches_up2).
 
     inputs: x (B,h,w,Cp) 16-bit with h, w > 1, keep, with_up, then the parameters of HeadsFused; outputs as HeadsFused at
     (2h, 2w)."""
@@ -1374,10 +1401,55 @@ class UpHeadsFused(Function):
         (HeadsAtPoints) reads it; the gradient it receives goes through U^T onto dx in backward."""
         _require_cuda(x, params[0])
         x = as_act(x)
-        up = resize_fwd(x, (2 * x.shape[1], 2 * x.shape[2]), 0)
         ctx.with_up = with_up
+        if UpHeadsFused.rows_route(x, with_up, params):
+            return UpHeadsFused._forward_rows(ctx, x, keep, params)
+        up = resize_fwd(x, (2 * x.shape[1], 2 * x.shape[2]), 0)
         outs = HeadsFused._forward(ctx, up, x, keep, params)
         return (*outs, up) if with_up else outs
+
+    @staticmethod
+    def rows_route(x, with_up: bool, params) -> bool:
+        """16-bit, rows of whole 256-pixel tiles at 2w (the row-slab kernel's condition on X1), heads the row pass holds in a
+        lane group (the widths the fused epilogue takes), operands within 32-bit byte offsets, no upsample asked for"""
+        B, h, w, Cp = x.shape
+        wmax = max(rup8(g.numel()) for g in params[2::6])
+        Nt = sum(rup8(g.numel()) for g in params[2::6])
+        return (not _HEAD_FWD_UPRES and not with_up and x.dtype in _MFMA_DTYPES and (2 * w) % 256 == 0 and wmax <= 224
+                and B * h * 2 * w * Cp * 2 < 0xFFFFFFF0 and 9 * Nt * Cp * 2 < 0xFFFFFFF0)
+
+    @staticmethod
+    def _forward_rows(ctx, x, keep: bool, params):
+        B, h, w, Cp = x.shape
+        H, W = 2 * h, 2 * w
+        heads = _HeadSet(params, Cp)
+        n_heads, Nt, C = heads.n, heads.Nt, heads.C
+        M, wmax, dev, es = B * H * W, max(heads.nps), x.device, x.element_size()
+        pw = 128 if wmax <= 128 else (192 if wmax <= 192 else 224)  # as HeadsFused: backward reads the same parameter block
+        hp = heads.packed_params(pw)
+        b_cat = heads.bias()
+        x1 = new_act(B, h, W, Cp, x)
+        _timed('resize2x_x_fwd_kernel', x, 0.0, B * h * W, Cp, 0,
+               lambda: check(lib.vkas_resize2x_x_fwd(_p(x), act_ld(x), _p(x1), Cp, B, h, w, Cp, _dt(x), _stream()), 'resize2x_x_fwd'),
+               3.0 * B * h * w * Cp * es)
+        T = new_act(B, h, W, 3 * Nt, x)
+        geom = _geom(B, h, W, h, W, Cp, Cp, 1, 3, 1, 1)
+        conv_gemm(x1, geom, heads.weights(3, x.dtype), 3 * Nt, T, _lib.EPI_NONE, nk=(3 * sum(heads.cs), C * 3))
+        del x1
+        z = new_act(B, H, W, Nt, x) if keep else None
+        stats = torch.empty((n_heads, M, 2), dtype=_FLOAT, device=dev) if keep else None
+        proj = torch.empty((n_heads, B, H, W, 8), dtype=_FLOAT, device=dev)
+        head = heads.desc(0, n_heads, pw, hp.data_ptr(), stats.data_ptr() if keep else None, proj.data_ptr())
+        # per output element: 3 blends (2 operations each) and their sums, then the tail's ~27 + 6 per projected channel
+        _timed('head_rows_fwd_kernel', x, float(M) * sum(heads.cs) * (9 + 21 + 2 * max(heads.ocs)), M, Nt, 0,
+               lambda: check(lib.vkas_head_rows_fwd(_p(T), _p(b_cat), ctypes.byref(head), _p(z), B, h, W, Nt, 0, _dt(x), _stream()),
+                             'head_rows_fwd'),
+               float(M) * (1.5 * Nt * es + (Nt * es if keep else 0) + n_heads * (40 if keep else 32)))
+        del T
+        if keep:
+            ctx.save_for_backward(x, z, stats, hp, *heads.saved(), x)
+        ctx.heads, ctx.pw, ctx.low, ctx.no_up = heads, pw, True, True
+        return tuple(proj[k] for k in range(n_heads))
 
     @staticmethod
     def backward(ctx, *gs):
