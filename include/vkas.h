@@ -609,6 +609,28 @@ long long vkas_quad_nms_workspace_bytes(int B, int K, int max_pairs);
 int vkas_quad_nms(const int* rows, const int* count, const float* probs, int B, int K, double iou_thr, int max_pairs,
                   void* workspace, size_t workspace_bytes, unsigned char* keep, int* suppressor, long long* stats, int* rounds,
                   void* stream);
+/* Grouping character quadrilaterals into text lines (inferencing/lines.py holds the rule - this project's own, all integer -
+ * and the host oracle quad_lines_host).  rows (B,K,16) int32 match rows, count (B) clamped to [0, K] on the device; gap_q4
+ * and cross_q4 in 1..4096, ratio_q4 in 16..256 (Q4).  A row takes part iff it lies within the count and its valid word is
+ * set.  Per quad, in int64: s = P0+P1+P2+P3, v = (P3+P2)-(P0+P1), u = (P1+P2)-(P0+P3), vv = v.v.  i and j are linked iff
+ * both take part and, with d = s_j - s_i, for a in {i, j}: 8|d.v_a| <= cross_q4 vv_a and 8|d_y v_a,x - d_x v_a,y| <= gap_q4
+ * vv_a; 256 vv_i <= ratio_q4^2 vv_j and the same swapped; v_i.v_j > 0.  A line is a connected component of the links; lines
+ * are numbered from 0 by their smallest member.  Per line U = the sum of u over its members, (0, 16) if that is (0, 0);
+ * the members are listed in ascending (s.U, index); a = P.U and b = P_y U_x - P_x U_y over all corners of all members give
+ * the extent.  Outputs: line (B,K) int32 = the line number, -1 for a row that takes no part or lies beyond the count; order
+ * (B,K) int32 = the member indices line after line in reading order, -1 beyond the n_part entries; table (B,K,8) int64 rows
+ * start, size, U_y, U_x, a_min, a_max, b_min, b_max for lines 0..L-1 and zero rows after them (K rows is the exact worst
+ * case: no overflow path); stats (B,4) int64 = n (the clamped count), n_part, links (pairs i < j), lines.  Eight launches
+ * on one stream (init, the pair tiles with an atomicMin union-find on a global parent array, flatten, line numbers, sums,
+ * starts, extents, ranks); integer atomics only (32-bit minima on the parents, 64-bit adds, minima and maxima on the
+ * table), no floating point, no allocation, no synchronisation, every output element and every workspace word that is
+ * read is written by the call's own kernels: capture-safe and bit-identical from run to run.  Reads are bounded by K and
+ * stores by the buffers whatever the tables hold.  B in 0..65535, K in 1..8192 (beyond: an error, not a clamp); rows and
+ * workspace 16-byte aligned, table and stats 8-byte aligned, workspace at least vkas_quad_lines_workspace_bytes (-1 on bad
+ * arguments). */
+long long vkas_quad_lines_workspace_bytes(int B, int K);
+int vkas_quad_lines(const int* rows, const int* count, int B, int K, int gap_q4, int cross_q4, int ratio_q4, void* workspace,
+                    size_t workspace_bytes, int* line, int* order, long long* table, long long* stats, void* stream);
 /* Text regions of the rough maps (the step between the passes, :190-279, restated on pixels).  mask (B,H,W) uint8 and height
  * (B,H,W) fp32 as vkas_rough_postprocess writes them.  A region is an 8-connected component of mask != 0; the regions of each
  * image are numbered 1..N by their first pixel in row-major order.  Outputs: count (B) = the true N of each image; labels

@@ -19,6 +19,8 @@ from .evaluation import (DetectionScore, QuadMatchResult, evaluate_quads, evalua
                          match_quads_host, match_rows, quad_iou_host, result_quads)
 from .nms import (QuadNmsResult, filter_result, greedy_suppression, nms_pairs, nms_quads, nms_quads_host,
                   nms_quads_lists_host, nms_tables, suppress_results)
+from .lines import (QuadLinesResult, group_results, line_params, line_quads, link_pairs, quad_frames, quad_lines,
+                    quad_lines_host, quad_lines_lists_host)
 from .ranking import (OperatingPoint, PRCurve, RankedMatchResult, RankedPairs, RankedScore, average_precision_host,
                       evaluate_quads_ranked, evaluate_quads_ranked_host, match_quads_ranked_host,
                       match_quads_ranked_rounds_host, quad_inter2_host, ranked_matching, ranked_matching_rounds, ranked_pairs,

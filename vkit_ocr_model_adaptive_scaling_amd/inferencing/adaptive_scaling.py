@@ -45,6 +45,7 @@ from .packing import (SIDE_MAX, check_multi_rows, check_warps, region_crops, rem
                       stack_regions, stack_regions_pages)
 from .orient import orient_regions, region_directions, warp_row
 from .nms import suppress_results
+from .lines import group_results
 from .. import ops
 from .._lib import lib, check
 from ..model import AdaptiveScaling, AdaptiveScalingConfig
@@ -109,6 +110,14 @@ class AdaptiveScalingInferencingConfig:
     # threshold (in (0, 1]).  0 = off: every result is bit for bit what it is without the feature, with no extra launch or
     # copy.
     precise_char_nms_iou_thr: float = 0.0
+    # Text lines (inferencing/lines.py), read by infer and infer_batch: after the suppression step (if any), the characters of
+    # one image - in ``result_quads`` order, all regions together - are grouped into lines in reading order, one device call
+    # for all images.  ``gap`` (along the line), ``cross`` (across it) and ``height_ratio`` are in character heights.  Off:
+    # every result is bit for bit what it is without the feature, with no extra launch or copy.
+    precise_char_lines: bool = False
+    precise_char_line_gap: float = 1.5
+    precise_char_line_cross: float = 0.5
+    precise_char_line_height_ratio: float = 2.0
 
 
 @attrs.define
@@ -187,6 +196,13 @@ class AdaptiveScalingInferencingResult:
     # for an image with more characters than the suppression takes (8192), which is left as it is
     num_suppressed: int = 0
     nms_status: int = 0
+    # config.precise_char_lines: the line of each character in ``result_quads`` order (-1 for an invalid quad), the characters
+    # of each line in reading order, the lines' oriented rectangles in image pixels (``line_quads``), and the status - 0, or
+    # 2 for an image with more characters than the grouping takes (8192), which gets no lines
+    char_lines: np.ndarray = attrs.field(factory=lambda: np.zeros((0,), np.int32))         # (n,) int32
+    line_chars: list = attrs.field(factory=list)                                          # L int32 index arrays
+    line_polygons: np.ndarray = attrs.field(factory=lambda: np.zeros((0, 4, 2), np.float64))  # (L, 4, 2) float64 (y, x)
+    lines_status: int = 0
 
 
 @attrs.define
@@ -671,6 +687,9 @@ class AdaptiveScalingInferencing:
             result.oriented, result.warps, result.warp_regions = oriented, warps, warp_ids
         if c.precise_char_nms_iou_thr:
             result = suppress_results([result], c.precise_char_nms_iou_thr, c.device)[0]
+        if c.precise_char_lines:
+            result = group_results([result], c.precise_char_line_gap, c.precise_char_line_cross,
+                                   c.precise_char_line_height_ratio, c.device)[0]
         return result
 
     def infer_batch(self, images: Sequence, return_pages: bool = False,
@@ -773,6 +792,9 @@ class AdaptiveScalingInferencing:
                 polygons=polygons, placement_pages=placement_pages))
         if c.precise_char_nms_iou_thr:
             results = suppress_results(results, c.precise_char_nms_iou_thr, c.device)  # one call for all images
+        if c.precise_char_lines:
+            results = group_results(results, c.precise_char_line_gap, c.precise_char_line_cross,
+                                    c.precise_char_line_height_ratio, c.device)  # one call for all images
         return AdaptiveScalingInferencingBatchResult(
             results=results, page_shapes=page_shapes, rows=rows, pages=pages if return_pages else None,
             region_labels=region_labels if return_labels else None)

@@ -2562,6 +2562,47 @@ def nms_quads(rows: torch.Tensor, count: torch.Tensor, probs: torch.Tensor, iou_
     return keep, suppressor, stats
 
 
+def quad_lines(rows: torch.Tensor, count: torch.Tensor, gap: float = 1.5, cross: float = 0.5, height_ratio: float = 2.0):
+    """Grouping of character quadrilaterals into text lines on the device (csrc/quadlines.hip; the rule and the host oracle
+    ``quad_lines_host``: inferencing/lines.py).  ``rows`` (B, K, 16) int32 match rows (``ops.quad_rows``), ``count`` (B,) int32,
+    both on the device; K at most 8192.  ``gap``, ``cross`` and ``height_ratio`` are in character heights and become Q4
+    integers by ``rint(x * 16)``: 1..4096, 1..4096 and 16..256.  Returns ``(line, order, table, stats)`` - (B, K) int32 (the
+    line of each quad, -1 for one that takes no part), (B, K) int32 (the member indices line after line in reading order,
+    then -1), (B, K, 8) int64 rows ``start, size, U_y, U_x, a_min, a_max, b_min, b_max`` (zero from the image's line count
+    on), (B, 4) int64 ``n, n_part, links, lines``.  K table rows is the exact worst case: there is no overflow path.  Eight
+    launches; never synchronises, so it can be captured into a HIP graph."""
+    if rows.dim() != 3 or rows.shape[2] != 16:
+        raise ValueError(f'quad_lines: rows must be (B, K, 16), got {tuple(rows.shape)}')
+    B, K, _ = (int(v) for v in rows.shape)
+    if tuple(count.shape) != (B,):
+        raise ValueError(f'quad_lines: count must be {(B,)}, got {tuple(count.shape)}')
+    if rows.dtype != torch.int32 or count.dtype != torch.int32:
+        raise ValueError(f'quad_lines: rows and count must be int32, got {rows.dtype} and {count.dtype}')
+    if not 1 <= K <= 8192:
+        raise ValueError(f'quad_lines: K = {K} must lie in 1..8192')
+    if B > 65535:
+        raise ValueError(f'quad_lines: B = {B} above 65535')
+    from .inferencing.lines import line_params  # the rule's own check, stated once
+    gap_q4, cross_q4, ratio_q4 = line_params(gap, cross, height_ratio)
+    _require_cuda(rows, count)
+    if count.device != rows.device:
+        raise ValueError('quad_lines: all tensors must be on one device')
+    rows, count = rows.contiguous(), count.contiguous()
+    dev = rows.device
+    line = torch.empty((B, K), dtype=torch.int32, device=dev)
+    order = torch.empty((B, K), dtype=torch.int32, device=dev)
+    table = torch.empty((B, K, 8), dtype=torch.int64, device=dev)
+    stats = torch.empty((B, 4), dtype=torch.int64, device=dev)
+    if B:
+        nbytes = lib.vkas_quad_lines_workspace_bytes(B, K)
+        if nbytes < 0:
+            check(-1, 'quad_lines')
+        ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+        check(lib.vkas_quad_lines(_p(rows), _p(count), B, K, gap_q4, cross_q4, ratio_q4, _p(ws), ws.numel(), _p(line),
+                                  _p(order), _p(table), _p(stats), _stream()), 'quad_lines')
+    return line, order, table, stats
+
+
 def text_regions(mask: torch.Tensor, height: torch.Tensor, max_regions: int):
     """Text regions of the rough maps and the median character height of each (the step between the two passes,
     inferencing/adaptive_scaling.py:190-279 restated on pixels, csrc/regions.hip).  mask (B,H,W) uint8 and height (B,H,W)
