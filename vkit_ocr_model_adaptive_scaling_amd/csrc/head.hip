@@ -377,166 +377,337 @@ __global__ __launch_bounds__(256) void head_tail_fwd_kernel(const T* __restrict_
 // kernel row ky the convolution's sums BEFORE the y half of the x2 bilinear upsample.  This pass applies that half and the 3x3's
 // sum over ky, z[r] = bias + sum_ky (Uy T_ky)[r + ky - 1] (a tap row outside [0, 2h) is the convolution's zero padding, not a
 // clamped row), stores z as the fused epilogue does and runs the same tail on the unrounded sums (LayerNorm statistics from
-// E[z^2] - mean^2, polynomial GELU, projection; pad columns are exact zeros).  A lane group (32 lanes, one 8-channel vector
-// each) keeps its column and head and walks down the source rows of a segment: the output rows 2i, 2i + 1 read the T rows
-// i - 1, i, i + 1, held as a rolling window with the row after them already requested, so a T element crosses the vector-memory
-// path once per segment (+ 3 rows at its ends).  Fixed order: bias, then ky ascending, each blend one rounded product and one
-// fmaf (the arithmetic of resize2x_fwd_kernel along y); no atomics.
+// E[z^2] - mean^2, polynomial GELU, projection; pad columns are exact zeros).
+// Eight lanes hold one (pixel, head): lane l owns the 8-channel vectors l, l + 8, l + 16, l + 24 of the head (every load or store
+// of a group is one 128-byte run), a wave holds eight consecutive pixel columns of ONE head, so the vectors walked (nv) and the
+// projection rows (oc) are wave-uniform, and a workgroup NH heads x 32 / NH columns.  The group streams down the source rows of
+// a segment.  Source row j gives, per channel,
+//             z[2j-2]  z[2j-1]  z[2j]  z[2j+1]  z[2j+2]  z[2j+3]
+//   T0[j]        -        -      .25     .75      .75      .25
+//   T1[j]        -       .25     .75     .75      .25       -
+//   T2[j]       .25      .75     .75     .25       -        -
+// (at the image's top and bottom the clamped blend has weight 1 and the tap row outside is dropped: workgroup-uniform weights).
+// When row j arrives, z[2j-2] and z[2j-1] are completed and go through the tail together (the parameters are read from LDS once
+// for both); then z[2j] and z[2j+1] start as fp32 partial sums from bias, the raw T0 / T1 of row j - 1 and row j.  Row j + 1 is
+// requested before the tail.  Fixed order of every sum: bias, then the contributions in ascending source row and ky, each one
+// fma (packed fp32); no atomics, two launches give the same bits.  A segment start costs one warm-up row (T0 / T1 of row i0 - 1).
 struct HeadRowsArgs {
   int n_heads, pw;
   int n0[4], np[4], c[4], oc[4];
 };
-__device__ __forceinline__ float blend2(float a, float b, float w) { return fmaf(b, w, __fmul_rn(a, 1.f - w)); }
+__device__ __forceinline__ int pick4(const int (&v)[4], int k) { return k == 0 ? v[0] : (k == 1 ? v[1] : (k == 2 ? v[2] : v[3])); }
+template <typename T> __device__ __forceinline__ void unpack2(const Raw8<T>& r, f32x2 (&u)[4]) {
+  float x[8];
+  r.unpack(x);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) u[c] = f32x2{x[2 * c], x[2 * c + 1]};
+}
 
-template <typename T, int NH>
-__global__ __launch_bounds__(256) void head_rows_fwd_kernel(const T* __restrict__ Tt, const float* __restrict__ bias,
-                                                            const float* __restrict__ params, T* __restrict__ z,
-                                                            float* __restrict__ stats, float* __restrict__ proj, HeadRowsArgs a,
-                                                            int h, int W2, int Nt, int seg, int nseg, long M, int ocm) {
-  constexpr int G = 32, GW = G * 8;
-  constexpr int CPB = 256 / G / NH;  // pixel columns per workgroup
-  const int gl = threadIdx.x & (G - 1);
-  const int grp = threadIdx.x / G;
-  const int head = grp % NH, cl = grp / NH;
-  const bool hok = head < a.n_heads;
+// NV: upper bound of the 8-channel vectors per lane (3: heads up to 192 padded columns, 4: up to 256)
+template <typename T, int NH, int NV>
+__global__ __launch_bounds__(256, 2) void head_rows_fwd_kernel(const T* __restrict__ Tt, const float* __restrict__ bias,
+                                                               const float* __restrict__ params, T* __restrict__ z,
+                                                               float* __restrict__ stats, float* __restrict__ proj,
+                                                               HeadRowsArgs a, int h, int W2, int Nt, int seg, int nseg, long M) {
+  constexpr int G = 8, GW = 256, HS = 7 * GW + 8;
+  constexpr int CPB = 32 / NH;  // pixel columns per workgroup
   const int pw = a.pw, PS = 6 * pw + 8;
-  const int C = hok ? a.c[head] : 1, np = hok ? a.np[head] : 0, n0 = hok ? a.n0[head] : 0;
-  const bool vok = hok && gl < (np >> 3);
-  // gamma | beta | Wproj[4] of every head, each GW floats and zero beyond pw, then bproj: full-wave 16-byte reads (see the
-  // backward kernel above)
-  __shared__ __attribute__((aligned(16))) float sp[NH * (6 * GW + 8)];
-  for (int i = threadIdx.x; i < NH * (6 * GW + 8); i += 256) {
-    const int hh = i / (6 * GW + 8), r = i - hh * (6 * GW + 8);
+  // gamma | beta | Wproj[4] | conv bias of every head, each GW floats and zero beyond the head's width, then bproj
+  __shared__ __attribute__((aligned(16))) float sp[NH * HS];
+  for (int i = threadIdx.x; i < NH * HS; i += 256) {
+    const int hh = i / HS, r = i - hh * HS;
     float v = 0.f;
     if (hh < a.n_heads) {
       if (r < 6 * GW) {
         const int k = r / GW, j = r - k * GW;
         if (j < pw) v = params[(long)hh * PS + k * pw + j];
+      } else if (r < 7 * GW) {
+        const int j = r - 6 * GW;
+        if (j < pick4(a.np, hh)) v = bias[pick4(a.n0, hh) + j];
       } else {
-        v = params[(long)hh * PS + 6 * pw + (r - 6 * GW)];
+        v = params[(long)hh * PS + 6 * pw + (r - 7 * GW)];
       }
     }
     sp[i] = v;
   }
   __syncthreads();
-  const float* hp = sp + head * (6 * GW + 8);
+  const int lane = threadIdx.x & 63, gl = lane & (G - 1);
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  // the heads rotate over a workgroup's waves from one workgroup to the next: a wave's cost follows its head's width and
+  // projection rows, and wave k of every workgroup may land on the same SIMD
+  const int head = (wave + (int)(blockIdx.x % NH)) % NH, cw = wave / NH;
+  if (head >= a.n_heads) return;  // wave-uniform; no barrier follows
   const int cblocks = (W2 + CPB - 1) / CPB;
   long bx = blockIdx.x;
   const int cbk = (int)(bx % cblocks);
   bx /= cblocks;
   const int sgi = (int)(bx % nseg);
   const long b = bx / nseg;
-  const int X = cbk * CPB + cl;
+  const int X0 = cbk * CPB + cw * 8;
+  if (X0 >= W2) return;
+  const int X = X0 + (lane >> 3);
   const bool xok = X < W2;
+  const int C = pick4(a.c, head), np = pick4(a.np, head), n0 = pick4(a.n0, head), oc = pick4(a.oc, head);
+  const int nvec = np >> 3, nv = (nvec + 7) >> 3;  // nv <= NV: the launcher's choice of NV
+  const float* hp = sp + head * HS;
   const int i0 = sgi * seg, i1 = i0 + seg < h ? i0 + seg : h;
-  float bs[8];
-#pragma unroll
-  for (int c = 0; c < 8; ++c) bs[c] = 0.f;
-  if (vok) load8(bias + n0 + gl * 8, bs);
   const long ldT = 3L * Nt;
-  // unconditional loads from clamped addresses (column clamped into the row, a lane beyond the head's width reads the head's
-  // first slice, a row beyond the image its last row); what must not be used is zeroed or skipped afterwards
-  const T* tcol = Tt + ((long)b * h * W2 + (xok ? X : W2 - 1)) * ldT + n0 + (vok ? gl : 0) * 8;
+  // unconditional loads from clamped addresses (column clamped into the row, a vector beyond the head's width reads the head's
+  // first one, a row beyond the image its last row); what must not be used is zeroed or skipped afterwards
+  // Every address is a wave-uniform 64-bit base (image, row, ky, head) plus a 32-bit lane offset inside one row of T or z
+  // (the launcher checks that a row fits): one offset register per vector instead of a pointer per load
   const long rowT = (long)W2 * ldT;
-  Raw8<T> win[4][3];  // rows i - 1, i, i + 1, i + 2 (rotating), per ky
-  auto fetch = [&](Raw8<T> (&r)[3], int i) {
+  const T* timg = Tt + (long)b * h * rowT + n0;
+  bool ok[NV];
+  unsigned offT[NV], offZ[NV];
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    ok[v] = gl + 8 * v < nvec;
+    offT[v] = (unsigned)(xok ? X : W2 - 1) * (unsigned)ldT + (ok[v] ? (gl + 8 * v) * 8 : 0);
+    offZ[v] = (unsigned)(xok ? X : 0) * (unsigned)Nt + (ok[v] ? (gl + 8 * v) * 8 : 0);
+  }
+  T* zimg = z ? z + (long)b * 2 * h * W2 * Nt + n0 : nullptr;
+  const float fC = (float)C;
+  const f32x2 q25 = pk_splat(0.25f), q75 = pk_splat(0.75f);
+  f32x2 E[NV][4], O[NV][4];  // partial sums of the even and the odd output row in flight
+#pragma unroll
+  for (int v = 0; v < NV; ++v)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) E[v][c] = O[v][c] = pk_splat(0.f);
+  Raw8<T> w0[NV][3], w1[NV][3];  // rows j and j + 1, alternating
+  // T0 / T1 of row j - 1 wait in LDS, 16 bytes per lane, vector and ky, each lane reading what it wrote: beside the rows in
+  // flight, the partial sums and the tail's temporaries they do not fit the 256 registers of two waves per SIMD at NV = 4
+  typedef decltype(w0[0][0].a) raw_t;
+  __shared__ __attribute__((aligned(16))) raw_t prev[2 * NV][256];
+  auto fetch = [&](Raw8<T> (&r)[NV][3], int i, int nky) {
     const int ic = i < 0 ? 0 : (i > h - 1 ? h - 1 : i);
+    const T* rp = timg + ic * rowT;
 #pragma unroll
-    for (int ky = 0; ky < 3; ++ky) r[ky].load(tcol + ic * rowT + ky * Nt);
+    for (int v = 0; v < NV; ++v) {
+      if (v >= nv) break;
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky)
+        if (ky < nky) r[v][ky].load(rp + ky * Nt + offT[v]);
+    }
   };
-  fetch(win[0], i0 - 1);
-  fetch(win[1], i0);
-  fetch(win[2], i0 + 1);
-  T* zcol = z ? z + n0 + gl * 8 : nullptr;
-  auto tail = [&](float (&v)[8], int r) {
-    const long m = ((long)b * 2 * h + r) * W2 + X;
-    float s = 0.f, q = 0.f;
+  auto keep = [&](Raw8<T> (&r)[NV][3]) {
 #pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      s += v[c];
-      q = fmaf(v[c], v[c], q);
+    for (int v = 0; v < NV; ++v) {
+      if (v >= nv) break;
+      prev[2 * v][threadIdx.x] = r[v][0].a;
+      prev[2 * v + 1][threadIdx.x] = r[v][1].a;
     }
-    s = group_sum<G>(s);
-    q = group_sum<G>(q);
-    const float mean = s / (float)C;
-    q = fmaxf(q - s * mean, 0.f);  // sum of squared deviations
-    const float rstd = rsqrtf(q / (float)C + 1e-6f);
-    if (zcol && xok && vok) store8(zcol + m * Nt, v);
-    int lo = gl * 8;
-    asm volatile("" : "+v"(lo));  // keeps the parameter reads in the loop
-    float gm[8], bt[8];
-    load8(hp + lo, gm);
-    load8(hp + GW + lo, bt);
-    f32x2 act[4];
-    const f32x2 rs2 = pk_splat(rstd), mu2 = pk_splat(mean);
+  };
+  // one source row: returns true after the segment's last output rows
+  auto step = [&](Raw8<T> (&Cu)[NV][3], Raw8<T> (&Nx)[NV][3], int j) -> bool {
+    const bool have = j < h;  // j == i1 == h: the rows in flight are complete as they stand
+    if (j + 1 <= i1 && j + 1 < h) fetch(Nx, j + 1, 3);
+    if (j > i0) {
+      // output rows 2j - 2 (E) and 2j - 1 (O): last contributions, statistics, z
+      T* zE = zimg + (long)(2 * j - 2) * W2 * Nt;
+      T* zO = zE + (long)W2 * Nt;
+      f32x2 sE = pk_splat(0.f), qE = sE, sO = sE, qO = sE;
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const f32x2 t = (f32x2{v[2 * c], v[2 * c + 1]} - mu2) * rs2;
-      act[c] = gelu2_t<T>(pk_fma(t, f32x2{gm[2 * c], gm[2 * c + 1]}, f32x2{bt[2 * c], bt[2 * c + 1]}));  // pad: gamma = beta = 0
-    }
-    float pr[4] = {0.f, 0.f, 0.f, 0.f};
+      for (int v = 0; v < NV; ++v) {
+        if (v >= nv) break;
+        if (have) {
+          f32x2 u1[4], u2[4];
+          unpack2(Cu[v][1], u1);
+          unpack2(Cu[v][2], u2);
 #pragma unroll
-    for (int qq = 0; qq < 4; ++qq) {
-      if (qq >= ocm) break;  // launch-uniform: the widest projection of the pass (a narrower head's further rows are zero)
-      float w[8];
-      load8(hp + (2 + qq) * GW + lo, w);
-      f32x2 p2 = {0.f, 0.f};
+          for (int c = 0; c < 4; ++c) {
+            E[v][c] = pk_fma(u2[c], q25, E[v][c]);
+            O[v][c] = pk_fma(u1[c], q25, O[v][c]);
+            O[v][c] = pk_fma(u2[c], q75, O[v][c]);
+          }
+        }
+        if (v == nv - 1) {  // the only vector step with lanes beyond the head's width
 #pragma unroll
-      for (int c = 0; c < 4; ++c) p2 = pk_fma(act[c], f32x2{w[2 * c], w[2 * c + 1]}, p2);
-      pr[qq] = group_sum<G>(p2.x + p2.y);
-    }
-    if (gl == 0 && hok && xok) {
-      const float4 bp = *reinterpret_cast<const float4*>(hp + 6 * GW);
-      float* po = proj + ((long)head * M + m) * 8;
-      *reinterpret_cast<float4*>(po) = make_float4(pr[0] + bp.x, pr[1] + bp.y, pr[2] + bp.z, pr[3] + bp.w);
-      *reinterpret_cast<float4*>(po + 4) = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (stats) {
-        float* st = stats + ((long)head * M + m) * 2;
-        st[0] = mean;
-        st[1] = rstd;
+          for (int c = 0; c < 4; ++c) {
+            E[v][c] = ok[v] ? E[v][c] : pk_splat(0.f);
+            O[v][c] = ok[v] ? O[v][c] : pk_splat(0.f);
+          }
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          sE = sE + E[v][c];
+          qE = pk_fma(E[v][c], E[v][c], qE);
+          sO = sO + O[v][c];
+          qO = pk_fma(O[v][c], O[v][c], qO);
+        }
+        if (zimg && xok && ok[v]) {
+          float x[8];
+#pragma unroll
+          for (int c = 0; c < 4; ++c) { x[2 * c] = E[v][c].x; x[2 * c + 1] = E[v][c].y; }
+          store8(zE + offZ[v], x);
+#pragma unroll
+          for (int c = 0; c < 4; ++c) { x[2 * c] = O[v][c].x; x[2 * c + 1] = O[v][c].y; }
+          store8(zO + offZ[v], x);
+        }
+      }
+      const float s_e = group_sum<G>(sE.x + sE.y), s_o = group_sum<G>(sO.x + sO.y);
+      float q_e = group_sum<G>(qE.x + qE.y), q_o = group_sum<G>(qO.x + qO.y);
+      const float meanE = s_e / fC, meanO = s_o / fC;
+      q_e = fmaxf(q_e - s_e * meanE, 0.f);  // sum of squared deviations
+      q_o = fmaxf(q_o - s_o * meanO, 0.f);
+      const float rstdE = rsqrtf(q_e / fC + 1e-6f), rstdO = rsqrtf(q_o / fC + 1e-6f);
+      const f32x2 muE = pk_splat(meanE), muO = pk_splat(meanO), rsE = pk_splat(rstdE), rsO = pk_splat(rstdO);
+      f32x2 prE[4], prO[4];
+#pragma unroll
+      for (int qq = 0; qq < 4; ++qq) prE[qq] = prO[qq] = pk_splat(0.f);
+#pragma unroll
+      for (int v = 0; v < NV; ++v) {
+        if (v >= nv) break;
+        int lo = (gl + 8 * v) * 8;
+        asm volatile("" : "+v"(lo));  // keeps the parameter reads in the loop
+        // four channels at a time, fenced: gamma, beta, two activations per row and one weight quad are all that is live
+        // beside the rows themselves (the whole vector at once does not fit the 256 registers at NV = 4)
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf) {
+          float gm[4], bt[4];
+          load4(hp + lo + 4 * hf, gm);
+          load4(hp + GW + lo + 4 * hf, bt);
+          // the head's own projection rows (wave-uniform), requested before the activations so that their LDS latency passes
+          // behind the GELU arithmetic
+          float w[4][4];
+#pragma unroll
+          for (int qq = 0; qq < 4; ++qq)
+            if (qq < oc) load4(hp + (2 + qq) * GW + lo + 4 * hf, w[qq]);
+          f32x2 aE[2], aO[2];
+#pragma unroll
+          for (int c = 0; c < 2; ++c) {  // pad and masked channels: z = gamma = beta = 0
+            const f32x2 g2 = {gm[2 * c], gm[2 * c + 1]}, b2 = {bt[2 * c], bt[2 * c + 1]};
+            aE[c] = gelu2_t<T>(pk_fma((E[v][2 * hf + c] - muE) * rsE, g2, b2));
+            aO[c] = gelu2_t<T>(pk_fma((O[v][2 * hf + c] - muO) * rsO, g2, b2));
+          }
+#pragma unroll
+          for (int qq = 0; qq < 4; ++qq) {
+            if (qq >= oc) break;
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+              const f32x2 wc = {w[qq][2 * c], w[qq][2 * c + 1]};
+              prE[qq] = pk_fma(aE[c], wc, prE[qq]);
+              prO[qq] = pk_fma(aO[c], wc, prO[qq]);
+            }
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      float pe[4] = {0.f, 0.f, 0.f, 0.f}, po[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int qq = 0; qq < 4; ++qq) {
+        if (qq >= oc) break;
+        pe[qq] = group_sum<G>(prE[qq].x + prE[qq].y);
+        po[qq] = group_sum<G>(prO[qq].x + prO[qq].y);
+      }
+      const float4 bp = *reinterpret_cast<const float4*>(hp + 7 * GW);  // zero beyond oc; read by the full wave
+      if (gl == 0 && xok) {
+        const long mE = ((long)b * 2 * h + 2 * j - 2) * W2 + X, mO = mE + W2;
+        float* pE = proj + ((long)head * M + mE) * 8;
+        float* pO = proj + ((long)head * M + mO) * 8;
+        *reinterpret_cast<float4*>(pE) = make_float4(pe[0] + bp.x, pe[1] + bp.y, pe[2] + bp.z, pe[3] + bp.w);
+        *reinterpret_cast<float4*>(pE + 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+        *reinterpret_cast<float4*>(pO) = make_float4(po[0] + bp.x, po[1] + bp.y, po[2] + bp.z, po[3] + bp.w);
+        *reinterpret_cast<float4*>(pO + 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (stats) {
+          *reinterpret_cast<float2*>(stats + ((long)head * M + mE) * 2) = make_float2(meanE, rstdE);
+          *reinterpret_cast<float2*>(stats + ((long)head * M + mO) * 2) = make_float2(meanO, rstdO);
+        }
       }
     }
-  };
-  auto rows = [&](Raw8<T> (&P)[3], Raw8<T> (&Cc)[3], Raw8<T> (&N)[3], int i) {
-    float p0[8], p1[8], c0[8], c1[8], c2[8], q0[8], q1[8], q2[8];
-    P[0].unpack(p0); P[1].unpack(p1);
-    Cc[0].unpack(c0); Cc[1].unpack(c1); Cc[2].unpack(c2);
-    N[0].unpack(q0); N[1].unpack(q1); N[2].unpack(q2);
-    const bool top = i == 0, bot = i + 1 >= h;  // workgroup-uniform
-    float v[8];
+    if (j >= i1) return true;
+    // output rows 2j and 2j + 1 start: bias, row j - 1 (T0, T1), row j (T0, T1, T2); row j + 1 completes them
+    const bool top = j == 0, bot = j + 1 >= h;  // workgroup-uniform
+    const f32x2 wE0 = pk_splat(top ? 0.f : 0.25f), wE1 = pk_splat(top ? 1.f : 0.75f), wE2 = pk_splat(bot ? 1.f : 0.75f);
+    const f32x2 wO0 = pk_splat(top ? 1.f : 0.75f), wO1 = pk_splat(bot ? 1.f : 0.75f), wO2 = pk_splat(bot ? 0.f : 0.25f);
 #pragma unroll
-    for (int c = 0; c < 8; ++c) {  // output row 2i: tap rows 2i - 1, 2i, 2i + 1
-      float t = bs[c];
-      if (!top) t += blend2(p0[c], c0[c], 0.25f);
-      t += top ? blend2(c1[c], q1[c], 0.f) : blend2(p1[c], c1[c], 0.75f);
-      t += blend2(c2[c], q2[c], 0.25f);
-      v[c] = vok ? t : 0.f;
-    }
-    tail(v, 2 * i);
+    for (int v = 0; v < NV; ++v) {
+      if (v >= nv) break;
+      int lo = (gl + 8 * v) * 8;
+      asm volatile("" : "+v"(lo));
+      float bs[8];
+      load8(hp + 6 * GW + lo, bs);
+      f32x2 e[4], o[4];
 #pragma unroll
-    for (int c = 0; c < 8; ++c) {  // output row 2i + 1: tap rows 2i, 2i + 1, 2i + 2
-      float t = bs[c];
-      t += top ? blend2(c0[c], q0[c], 0.f) : blend2(p0[c], c0[c], 0.75f);
-      t += blend2(c1[c], q1[c], 0.25f);
-      if (!bot) t += blend2(c2[c], q2[c], 0.75f);
-      v[c] = vok ? t : 0.f;
+      for (int c = 0; c < 4; ++c) e[c] = o[c] = f32x2{bs[2 * c], bs[2 * c + 1]};
+      // one ky at a time, fenced: eight converted values are live at once.  The asm barrier stops the compiler from carrying
+      // the fp32 form of T1 / T2, converted for the completion above, across the tail: twice the registers of the raw row
+      if (!top) {
+        Raw8<T> pr;
+        f32x2 p[4];
+        pr.a = prev[2 * v][threadIdx.x];
+        unpack2(pr, p);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          e[c] = pk_fma(p[c], q75, e[c]);
+          o[c] = pk_fma(p[c], q25, o[c]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        pr.a = prev[2 * v + 1][threadIdx.x];
+        unpack2(pr, p);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) e[c] = pk_fma(p[c], q25, e[c]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      asm volatile("" : "+v"(Cu[v][1].a), "+v"(Cu[v][2].a));
+      f32x2 u[4];
+      unpack2(Cu[v][0], u);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        e[c] = pk_fma(u[c], wE0, e[c]);
+        o[c] = pk_fma(u[c], wO0, o[c]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      unpack2(Cu[v][1], u);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        e[c] = pk_fma(u[c], wE1, e[c]);
+        o[c] = pk_fma(u[c], wO1, o[c]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      unpack2(Cu[v][2], u);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        E[v][c] = pk_fma(u[c], wE2, e[c]);
+        O[v][c] = pk_fma(u[c], wO2, o[c]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
     }
-    tail(v, 2 * i + 1);
+    keep(Cu);
+    return false;
   };
-  // the window rotates through four register sets: four source rows per trip keep every index a compile-time constant
-  for (int i = i0; i < i1; i += 4) {
-    fetch(win[3], i + 2);
-    rows(win[0], win[1], win[2], i);
-    if (i + 1 >= i1) break;
-    fetch(win[0], i + 3);
-    rows(win[1], win[2], win[3], i + 1);
-    if (i + 2 >= i1) break;
-    fetch(win[1], i + 4);
-    rows(win[2], win[3], win[0], i + 2);
-    if (i + 3 >= i1) break;
-    fetch(win[2], i + 5);
-    rows(win[3], win[0], win[1], i + 3);
+  if (i0 > 0) {  // the warm-up row of a segment inside the image
+    fetch(w1, i0 - 1, 2);
+    keep(w1);
   }
+  fetch(w0, i0, 3);
+  // two register sets alternate: two source rows per trip keep every index a compile-time constant
+  for (int j = i0;; j += 2) {
+    if (step(w0, w1, j)) break;
+    if (step(w1, w0, j + 1)) break;
+  }
+}
+
+// Segment length of the row pass, by the criterion of cs_seg_rows (upconv_adj.hip): the fewest row steps per CU slot (a segment
+// walks its rows and one warm-up row) among the lengths that fill the slots - two workgroups on each of the 256 CUs - four times
+// over.  One workgroup per slot leaves every SIMD with the cost of its slowest wave until the launch ends: at B = 8, h = 256,
+// W2 = 512 the precise set takes 2.80 ms in segments of 256 rows (one round), 2.64 at 128, 2.50 at 64, 2.46 at 32 and 2.50 at
+// 16, the rough set 1.36 / 0.94 / 0.94 / 0.95 / 0.97 ms (profiles/head_rows_groups.log).
+static inline int hr_seg_rows(long cols, int h) {
+  const long slots = 4 * 2 * 256;
+  long best = h, best_cost = -1;
+  bool best_full = false;
+  for (long seg = h; seg >= 1; --seg) {
+    const long nseg = vkas_cdiv(h, seg);
+    if (vkas_cdiv(h, nseg) != seg) continue;  // the same cut with a shorter last segment
+    const long wgs = cols * nseg;
+    const long cost = vkas_cdiv(wgs, slots) * (seg + 1);
+    const bool full = wgs >= slots;
+    if (best_cost < 0 || (full && !best_full) || (full == best_full && cost < best_cost)) {
+      best = seg; best_cost = cost; best_full = full;
+    }
+  }
+  return (int)best;
 }
 
 static inline int ht_lanes(int pw) { return pw <= 256 ? 32 : 64; }
@@ -613,11 +784,12 @@ extern "C" int vkas_head_rows_fwd(const void* Tt, const float* bias, const vkas_
   const int pw = hd->pw, nh = hd->n_heads;
   VKAS_CHECK(nh >= 1 && nh <= 4 && pw % 8 == 0 && pw >= 8 && pw <= 256, "vkas_head_rows_fwd: bad descriptor (pw <= 256)");
   VKAS_CHECK(B >= 0 && h > 0 && W2 > 0 && Nt > 0 && Nt % 8 == 0 && seg_rows >= 0, "vkas_head_rows_fwd: bad sizes");
+  VKAS_CHECK(3L * Nt * W2 < (1L << 30), "vkas_head_rows_fwd: a row of T beyond 2^31 bytes (32-bit lane offsets)");
   VKAS_CHECK((hd->stats != nullptr) == (z != nullptr), "vkas_head_rows_fwd: z and the statistics are kept or dropped together");
   HeadRowsArgs a;
   a.n_heads = nh;
   a.pw = pw;
-  int ocm = 1;
+  int npm = 8;
   for (int k = 0; k < 4; ++k) {
     a.n0[k] = k < nh ? hd->n0[k] : 0;
     a.np[k] = k < nh ? hd->np[k] : 0;
@@ -627,26 +799,30 @@ extern "C" int vkas_head_rows_fwd(const void* Tt, const float* bias, const vkas_
       VKAS_CHECK(a.np[k] % 8 == 0 && a.np[k] > 0 && a.np[k] <= pw && a.c[k] > 0 && a.c[k] <= a.np[k] && a.n0[k] % 8 == 0 &&
                      a.n0[k] >= 0 && a.n0[k] + a.np[k] <= Nt && a.oc[k] >= 1 && a.oc[k] <= 4,
                  "vkas_head_rows_fwd: bad head %d", k);
-      ocm = a.oc[k] > ocm ? a.oc[k] : ocm;
+      npm = a.np[k] > npm ? a.np[k] : npm;
     }
   }
   VKAS_CHECK(vkas_aligned16(Tt) && vkas_aligned16(bias) && vkas_aligned16(z) && vkas_aligned16(hd->params) && vkas_aligned16(hd->proj),
              "vkas_head_rows_fwd: misaligned pointer");
   if (B == 0) return VKAS_OK;
   const int NH = nh == 1 ? 1 : (nh == 2 ? 2 : 4);
-  const int cpb = 256 / 32 / NH;
-  // segments of source rows: 32, shorter while the launch has fewer than ~4096 workgroups, never below 8 (three extra rows each)
-  int seg = seg_rows > 0 ? (seg_rows < h ? seg_rows : h) : (h < 32 ? h : 32);
+  const int cpb = 32 / NH;
   const long cols = (long)B * vkas_cdiv(W2, cpb);
-  while (seg_rows == 0 && seg > 8 && cols * vkas_cdiv(h, seg) < 4096) seg = (seg + 1) / 2;
+  const int seg = seg_rows > 0 ? (seg_rows < h ? seg_rows : h) : hr_seg_rows(cols, h);
   const int nseg = (int)vkas_cdiv(h, seg);
   const long blocks = cols * nseg;
   VKAS_CHECK(blocks < (1L << 31), "vkas_head_rows_fwd: too many workgroups");
   const long M = (long)B * 2 * h * W2;
   hipStream_t st = vkas_stream(stream);
 #define VKAS_HR(NHV)                                                                                                          \
-  head_rows_fwd_kernel<T, NHV><<<(unsigned)blocks, 256, 0, st>>>((const T*)Tt, bias, hd->params, (T*)z, hd->stats, hd->proj, a, h, \
-                                                                 W2, Nt, seg, nseg, M, ocm)
+  do {                                                                                                                        \
+    if (npm <= 192)                                                                                                           \
+      head_rows_fwd_kernel<T, NHV, 3><<<(unsigned)blocks, 256, 0, st>>>((const T*)Tt, bias, hd->params, (T*)z, hd->stats,     \
+                                                                        hd->proj, a, h, W2, Nt, seg, nseg, M);                \
+    else                                                                                                                      \
+      head_rows_fwd_kernel<T, NHV, 4><<<(unsigned)blocks, 256, 0, st>>>((const T*)Tt, bias, hd->params, (T*)z, hd->stats,     \
+                                                                        hd->proj, a, h, W2, Nt, seg, nseg, M);                \
+  } while (0)
   if (dtype == VKAS_BF16) {
     typedef bf16_t T;
     if (NH == 1) VKAS_HR(1); else if (NH == 2) VKAS_HR(2); else VKAS_HR(4);
