@@ -730,6 +730,26 @@ int vkas_warp_region_labels(const int* labels, int Hl, int Wl, int valid_h, int 
  * out is 16-byte aligned, plain stores otherwise. */
 int vkas_crop_warp_f32(const unsigned char* arena, long long arena_bytes, const long long* sources, int S,
                        const long long* rows, int B, float* out, int H, int W, void* stream);
+/* Text lines cut into upright strips of one height h (inferencing/strips.py holds the rule from a quadrilateral to a row and
+ * the host oracle quad_strips_host).  The images lie in one byte arena with the (S,4) int64 source table of
+ * vkas_resample_pack_u8_multi.  The table `rows` holds 13*n + 1 int64 words: n strip rows of 12 words (src, offset, slot_w,
+ * w, ay, ax, myy, myx, mxy, mxx, log2n, 0), then tile_start, n + 1 words: tile_start[0] = 0 and tile_start[r + 1] =
+ * tile_start[r] + ceil(h/16) * ceil(slot_w[r]/64), the tiles of 16 x 64 pixels that the kernel gives row r (a workgroup finds
+ * the row of its tile by binary search).  Strip row r owns the slot of h x slot_w x 3 bytes at out + offset: pixel (i, j)
+ * with j < w is the pixel of vkas_warp_pack_u8 for the warp (0, 0, h, w, ay, ax, myy, myx, mxy, mxx, log2n) of image src
+ * (N x N bilinear sub-samples, a tap outside the image reading 0, one rounding), the columns w..slot_w-1 are 0.  Every byte
+ * of every slot is written, no other byte of out is touched; slots are pairwise disjoint (the caller's check).  The kernel
+ * checks every row itself: a row whose slot is not defined inside out (slot_w outside 1..8192, offset < 0, offset +
+ * 3*h*slot_w > out_bytes) is skipped; a row with src outside 0..S-1, a source entry with a side outside 1..32768, offset < 0
+ * or offset + 3*Hs*Ws > arena_bytes, w outside 1..slot_w, |m| > 2^22, |a| >= 2^40 or log2n outside 0..3 gets a slot of zeros.
+ * tile_start is not trusted either: its total is clamped to n * ceil(h/16) * 128, and a tile outside its row's own count is
+ * dropped (a wrong tile_start leaves tiles unwritten, nothing else): no table content makes the kernel touch memory outside
+ * its buffers.  One launch (none for n = 0) of min(n * ceil(h/16) * 128, 2048) workgroups that stride over the tiles;
+ * capture-safe: no allocation, no synchronisation, no atomics; bit-identical from run to run.  h in 1..256, n >= 0,
+ * out_bytes < 2^40, tables 8-byte aligned; three aligned dword stores per 4 pixels where the address is 4-byte aligned
+ * (always when out, offset and slot_w are multiples of 4), byte stores otherwise. */
+int vkas_quad_strips_u8(const unsigned char* arena, long long arena_bytes, const long long* sources, int S,
+                        const long long* rows, int n, int h, unsigned char* out, long long out_bytes, void* stream);
 
 /* ---- optimizer on the flat parameter / gradient buffers: train.py:468-478 ------------------------------ */
 /* sumsq (1 double, zeroed by the call) = sum g^2 */

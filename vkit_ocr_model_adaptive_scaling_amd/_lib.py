@@ -213,6 +213,7 @@ _SIGS = {
     'vkas_warp_region_labels': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, c_int, _P, c_int, c_int,
                                         _P]),
     'vkas_crop_warp_f32': (c_int, [_P, c_longlong, _P, c_int, _P, c_int, _P, c_int, c_int, _P]),
+    'vkas_quad_strips_u8': (c_int, [_P, c_longlong, _P, c_int, _P, c_int, c_int, _P, c_longlong, _P]),
     'vkas_l2norm_sq': (c_int, [_P, c_long, _P, _P]),
     'vkas_adamw_step': (c_int, [_P, _P, _P, _P, c_long, _P, c_float, c_float, c_float, c_float, c_float, c_float,
                                 c_float, c_int, _P]),

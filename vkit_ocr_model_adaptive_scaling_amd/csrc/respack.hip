@@ -19,6 +19,7 @@
 // staged in LDS.  All arithmetic is integer: inner row sums in 32 bits, the outer sum in 64, one rounding division by the
 // product of the axis denominators.
 #include "vkas_common.h"
+#include "warp_pixel.h"  // WarpRow, warp_pixel, SIDE_MAX, DIM_MAX, side_ok
 
 namespace {
 
@@ -26,8 +27,6 @@ constexpr int TILE_H = 16, TILE_W = 64, QUAD = 4;           // cells per tile; c
 constexpr int THREADS = TILE_H * TILE_W / QUAD;             // 256
 constexpr int WAVES = THREADS / 64;
 constexpr int LIST_CAP = TILE_H * TILE_W;                   // disjoint placements: at most one per cell of the tile
-constexpr int SIDE_MAX = 8192;
-constexpr int DIM_MAX = 32768;                              // source / page sides: pixel counts stay below 2^30
 
 // ---- row types: load(table, i), the destination rectangle dy, dx, dh, dw in page pixels, and ok(what the check needs) -----
 // The kernels trust the host's disjointness check, but never a row's bounds: a row that fails ok() is treated as absent, so
@@ -58,28 +57,6 @@ struct MultiRow : Placement {
   }
 };
 
-// 12 int64 (dy, dx, dh, dw, ay, ax, myy, myx, mxy, mxx, log2n, 0), an affine warp (inferencing/orient.py builds the rows):
-// destination pixel (i, j) of the rectangle reads the source at Y = ay + i*myy + j*myx, X = ax + i*mxy + j*mxx in Q16, an
-// integer coordinate being a pixel centre.
-constexpr int WARP_WORDS = 12;
-constexpr long long WARP_M_MAX = 1LL << 22, WARP_A_MAX = 1LL << 40;
-
-struct WarpRow {
-  long long dy, dx, dh, dw, ay, ax, myy, myx, mxy, mxx, log2n;
-  static __device__ __forceinline__ WarpRow load(const long long* __restrict__ table, int i) {
-    const long long* t = table + (long)i * WARP_WORDS;
-    return WarpRow{t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7], t[8], t[9], t[10]};
-  }
-  // needs no source: within these bounds no intermediate leaves 64 bits (|Y| < 2^40 + 2^36) and a tap outside the source
-  // reads 0, so no table content makes a kernel read outside the source
-  __device__ __forceinline__ bool ok() const {
-    const auto m_ok = [](long long m) { return m >= -WARP_M_MAX && m <= WARP_M_MAX; };
-    return dh >= 1 && dw >= 1 && dh <= SIDE_MAX && dw <= SIDE_MAX && dy >= 0 && dx >= 0 && dy <= DIM_MAX && dx <= DIM_MAX &&
-           ay > -WARP_A_MAX && ay < WARP_A_MAX && ax > -WARP_A_MAX && ax < WARP_A_MAX && m_ok(myy) && m_ok(myx) &&
-           m_ok(mxy) && m_ok(mxx) && log2n >= 0 && log2n <= 3;
-  }
-};
-
 // ---- source policies: ok(row), and after select(row, its index) what that row reads from ----------------------------------
 
 // the one image of the kernel's arguments
@@ -102,8 +79,6 @@ struct OneLabelMap {
   template <class Row>
   __device__ __forceinline__ void select(const Row&, int i) { local_id = global_id = region_ids[i]; }
 };
-
-__device__ __forceinline__ bool side_ok(long long v) { return v >= 1 && v <= DIM_MAX; }
 
 // The sources of a multi pack lie in ONE arena: a table of int64 rows per source gives its offset and sides, and every
 // address is arena + offset.  select(row with src in [0, S)) says whether that entry lies inside the arena; a row is valid
@@ -437,48 +412,7 @@ __global__ __launch_bounds__(THREADS) void pack_labels_multi_kernel(const int* _
                         out + (long)q * Hq * Wq, Hq, Wq, vec_stores);
 }
 
-// ---- the warp kernels: the prologue and the one-source policies, their own cell rules ------------------------------------
-
-// two-tap bilinear in x on source row k (zero outside the source): sum over the taps of weight * pixel, below 2^24
-__device__ __forceinline__ void warp_row_taps(const unsigned char* __restrict__ src, int Hs, int Ws, long long k,
-                                              long long kx, unsigned fx, unsigned in[3]) {
-  in[0] = in[1] = in[2] = 0u;
-  if (k < 0 || k >= Hs) return;
-  const unsigned char* row = src + (long)k * Ws * 3;
-  if (kx >= 0 && kx < Ws) {
-    const unsigned char* px = row + kx * 3;
-    const unsigned w = 65536u - fx;
-    in[0] += w * px[0]; in[1] += w * px[1]; in[2] += w * px[2];
-  }
-  if (fx != 0u && kx + 1 >= 0 && kx + 1 < Ws) {
-    const unsigned char* px = row + (kx + 1) * 3;
-    in[0] += fx * px[0]; in[1] += fx * px[1]; in[2] += fx * px[2];
-  }
-}
-
-__device__ __forceinline__ void warp_pixel(const unsigned char* __restrict__ src, int Hs, int Ws, const WarpRow& p, int i,
-                                           int j, unsigned out[3]) {
-  const long long Y = p.ay + i * p.myy + j * p.myx, X = p.ax + i * p.mxy + j * p.mxx;
-  const int ln = (int)p.log2n, n = 1 << ln;
-  unsigned long long acc[3] = {0ull, 0ull, 0ull};
-  for (int a = 0; a < n; ++a) {
-    for (int b = 0; b < n; ++b) {
-      const long long ka = 2 * a + 1 - n, kb = 2 * b + 1 - n;
-      const long long Ys = Y + ((ka * p.myy + kb * p.myx) >> (1 + ln));  // arithmetic shifts: floors
-      const long long Xs = X + ((ka * p.mxy + kb * p.mxx) >> (1 + ln));
-      const long long ky = Ys >> 16, kx = Xs >> 16;
-      const unsigned fy = (unsigned)(Ys & 65535), fx = (unsigned)(Xs & 65535);
-      unsigned r0[3], r1[3] = {0u, 0u, 0u};
-      warp_row_taps(src, Hs, Ws, ky, kx, fx, r0);
-      if (fy != 0u) warp_row_taps(src, Hs, Ws, ky + 1, kx, fx, r1);
-#pragma unroll
-      for (int c = 0; c < 3; ++c) acc[c] += (unsigned long long)(65536u - fy) * r0[c] + (unsigned long long)fy * r1[c];
-    }
-  }
-  const int shift = 32 + 2 * ln;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) out[c] = (unsigned)((acc[c] + (1ull << (shift - 1))) >> shift);
-}
+// ---- the warp kernels: the prologue and the one-source policies, their own cell rules (the pixel: warp_pixel.h) -----------
 
 // writes ONLY the pixels inside the destinations: the page keeps every other byte (resample_pack_kernel ran before)
 __global__ __launch_bounds__(THREADS) void warp_pack_kernel(const unsigned char* __restrict__ src, int Hs, int Ws,

@@ -26,3 +26,6 @@ from .ranking import (OperatingPoint, PRCurve, RankedMatchResult, RankedPairs, R
                       match_quads_ranked_rounds_host, quad_inter2_host, ranked_matching, ranked_matching_rounds, ranked_pairs,
                       ranked_score)
 from .orient import (orient_regions, oriented_rects, region_directions, region_extents_host, region_moments_host, warp_row)
+from .strips import (QuadStrips, StripLayout, check_strip_rows, quad_strips_host, remap_strip_points, strip_params, strip_rows,
+                     strip_table, strip_warp)
+from .line_strips import quad_strips, strips_for_results

@@ -46,6 +46,8 @@ from .packing import (SIDE_MAX, check_multi_rows, check_warps, region_crops, rem
 from .orient import orient_regions, region_directions, warp_row
 from .nms import suppress_results
 from .lines import group_results
+from .line_strips import strips_for_results
+from .strips import QuadStrips
 from .. import ops
 from .._lib import lib, check
 from ..model import AdaptiveScaling, AdaptiveScalingConfig
@@ -118,6 +120,16 @@ class AdaptiveScalingInferencingConfig:
     precise_char_line_gap: float = 1.5
     precise_char_line_cross: float = 0.5
     precise_char_line_height_ratio: float = 2.0
+    # Line strips (inferencing/strips.py), read by infer and infer_batch; needs precise_char_lines: the oriented rectangle of
+    # every line is cut out of its image, turned upright and brought to ``height`` rows - the recogniser's input -, all
+    # lines of all images in one launch (csrc/strips.hip).  ``margin`` (around the rectangle) is in line heights; a strip is
+    # at most ``width_max`` columns (a longer line is squeezed) and lies in a slot whose width is a multiple of
+    # ``width_step``.  Off: every result is bit for bit what it is without the feature, with no extra launch or copy.
+    precise_line_strips: bool = False
+    precise_line_strip_height: int = 32
+    precise_line_strip_width_max: int = 2048
+    precise_line_strip_width_step: int = 64
+    precise_line_strip_margin: float = 0.125
 
 
 @attrs.define
@@ -203,6 +215,10 @@ class AdaptiveScalingInferencingResult:
     line_chars: list = attrs.field(factory=list)                                          # L int32 index arrays
     line_polygons: np.ndarray = attrs.field(factory=lambda: np.zeros((0, 4, 2), np.float64))  # (L, 4, 2) float64 (y, x)
     lines_status: int = 0
+    # config.precise_line_strips: for each line its index into the strips object (inferencing/strips.py::QuadStrips) - from
+    # infer ``line_strips``, from infer_batch the batch result's ``line_strips``, which all its images share
+    line_strip_ids: np.ndarray = attrs.field(factory=lambda: np.zeros((0,), np.int32))     # (L,) int32
+    line_strips: Optional[QuadStrips] = None
 
 
 @attrs.define
@@ -214,6 +230,7 @@ class AdaptiveScalingInferencingBatchResult:
     # only on request, per page (none when no region was packed): (Hp, Wp, 3) uint8; (Hp/FDF, Wp/FDF) int32 global region ids
     pages: Optional[Sequence[np.ndarray]] = None
     region_labels: Optional[Sequence[np.ndarray]] = None
+    line_strips: Optional[QuadStrips] = None  # config.precise_line_strips: the strips of the lines of all images
 
 
 def rough_resized_shape(height: int, width: int, short_side: int) -> Tuple[int, int]:
@@ -597,6 +614,13 @@ class AdaptiveScalingInferencing:
     def precise_infer_char_polygons(self, image) -> AdaptiveScalingInferencingPreciseCharPolygons:
         return self.precise_infer_char_polygons_batch([image])[0]
 
+    def _line_strips(self, results, images_or_arena):
+        """The line-strip step of ``infer`` / ``infer_batch`` (after ``group_results``): the results with ``line_strip_ids``
+        and the one ``QuadStrips`` of all their lines."""
+        c = self.config
+        return strips_for_results(results, images_or_arena, c.precise_line_strip_height, c.precise_line_strip_width_max,
+                                  c.precise_line_strip_width_step, c.precise_line_strip_margin, c.device)
+
     # ---- image in, characters out --------------------------------------------------------------------------------
     def infer(self, image, return_page: bool = False, return_labels: bool = False) -> AdaptiveScalingInferencingResult:
         """Both passes and the step between them (:92-525 on pixels): the uint8 image is uploaded once; the 720 rule's shrink
@@ -615,6 +639,8 @@ class AdaptiveScalingInferencing:
         ``ops.warp_pack_u8`` / ``ops.warp_region_labels`` write the oriented regions into the page and the label page after
         the axis-aligned ones; their characters go back through ``remap_polygons_affine``."""
         c = self.config
+        if c.precise_line_strips and not c.precise_char_lines:
+            raise ValueError('precise_line_strips cuts the text lines: set precise_char_lines too')
         mat = _as_mat(image)
         if mat.dtype != np.uint8:
             raise ValueError(f'infer takes a uint8 image, got {mat.dtype}')
@@ -690,6 +716,9 @@ class AdaptiveScalingInferencing:
         if c.precise_char_lines:
             result = group_results([result], c.precise_char_line_gap, c.precise_char_line_cross,
                                    c.precise_char_line_height_ratio, c.device)[0]
+        if c.precise_line_strips:  # the image is on the device already: a one-entry source table
+            (result,), strips = self._line_strips([result], (src.reshape(-1), np.array([[0, *image_shape, 0]], np.int64)))
+            result.line_strips = strips
         return result
 
     def infer_batch(self, images: Sequence, return_pages: bool = False,
@@ -716,6 +745,8 @@ class AdaptiveScalingInferencing:
         c = self.config
         if c.precise_text_region_orient:
             raise ValueError('infer_batch does not take oriented text regions yet: unset precise_text_region_orient or use infer')
+        if c.precise_line_strips and not c.precise_char_lines:
+            raise ValueError('precise_line_strips cuts the text lines: set precise_char_lines too')
         if not len(images):
             return AdaptiveScalingInferencingBatchResult(results=[], page_shapes=[], rows=np.zeros((0, 12), np.int32),
                                                          pages=[] if return_pages else None,
@@ -795,9 +826,12 @@ class AdaptiveScalingInferencing:
         if c.precise_char_lines:
             results = group_results(results, c.precise_char_line_gap, c.precise_char_line_cross,
                                     c.precise_char_line_height_ratio, c.device)  # one call for all images
+        strips = None
+        if c.precise_line_strips:  # one launch for the lines of all images, out of the arena
+            results, strips = self._line_strips(results, (arena, sources, d_sources))
         return AdaptiveScalingInferencingBatchResult(
             results=results, page_shapes=page_shapes, rows=rows, pages=pages if return_pages else None,
-            region_labels=region_labels if return_labels else None)
+            region_labels=region_labels if return_labels else None, line_strips=strips)
 
     @staticmethod
     def precise_group_char_polygons(result: AdaptiveScalingInferencingPreciseCharPolygons,

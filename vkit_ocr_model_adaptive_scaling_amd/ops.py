@@ -3022,6 +3022,61 @@ def image_arena(mats, device):
     return host.to(device, non_blocking=True), table, torch.from_numpy(table).to(device, non_blocking=True)
 
 
+def quad_strips_u8(arena: torch.Tensor, sources, rows, h: int, out_bytes: int, validate: bool = True) -> torch.Tensor:
+    """Cuts text lines out of the images of an arena into upright strips of height ``h``, all in one launch (csrc/strips.hip;
+    the rule, the row layout and the oracle: inferencing/strips.py).  ``arena``: a 1-D uint8 device tensor that holds the
+    images; ``sources`` (S,4) int64 rows (byte offset, Hs, Ws, 0) as ``image_arena`` builds them; ``rows``: the (n,12) int64
+    strip rows, host or device, or the 1-D int64 device table ``strips.strip_table`` lays out (the rows, then ``tile_start``)
+    - from (n,12) rows that table is built here, on the host for host rows, with a few small device operations for device
+    rows.  Host tables are always checked (``check_strip_rows``), device tables when ``validate`` - a synchronisation.
+    Returns the 1-D uint8 output of ``out_bytes`` bytes: every byte of every slot is written - the slots of ``strip_rows``
+    cover the output -, a byte outside the slots keeps what the allocation held.  Allocates only its output (and the small
+    table); with device tables and ``validate=False`` it never synchronises, so it can be captured into a HIP graph."""
+    import numpy as np
+    from .inferencing.strips import ROW_WORDS, TILE_H, TILE_W, HEIGHT_MAX, check_strip_rows, strip_table
+    if arena.dim() != 1 or arena.dtype != torch.uint8:
+        raise ValueError(f'quad_strips_u8: arena must be a 1-D uint8 tensor, got {arena.dtype} {tuple(arena.shape)}')
+    if arena.numel() < 1 or not arena.is_contiguous():
+        raise ValueError('quad_strips_u8: arena must be contiguous and not empty')
+    if h != int(h) or not 1 <= int(h) <= HEIGHT_MAX:
+        raise ValueError(f'quad_strips_u8: h must be an integer in [1, {HEIGHT_MAX}], got {h}')
+    h, out_bytes = int(h), int(out_bytes)
+    if not 0 <= out_bytes < 1 << 40:
+        raise ValueError(f'quad_strips_u8: out_bytes must be in [0, 2^40), got {out_bytes}')
+    d_sources, h_sources = _pack_table('quad_strips_u8', 'sources', sources, (None, 4), 'int64', arena.device, validate)
+    if int(d_sources.shape[0]) < 1:
+        raise ValueError('quad_strips_u8: no sources')
+    flat = isinstance(rows, torch.Tensor) and rows.is_cuda and rows.dim() == 1
+    if flat:
+        if (int(rows.numel()) - 1) % (ROW_WORDS + 1):
+            raise ValueError(f'quad_strips_u8: a 1-D row table holds 13*n + 1 words, got {int(rows.numel())}')
+        d_table, h_table = _pack_table('quad_strips_u8', 'rows', rows, (None,), 'int64', arena.device, validate)
+        n = (int(d_table.numel()) - 1) // (ROW_WORDS + 1)
+        h_rows = None if h_table is None else h_table[:n * ROW_WORDS].reshape(n, ROW_WORDS)
+        if h_table is not None and not np.array_equal(h_table, strip_table(h_rows, h)):
+            raise ValueError('quad_strips_u8: tile_start does not give each row its tiles')
+    else:
+        d_rows, h_rows = _pack_table('quad_strips_u8', 'rows', rows, (None, ROW_WORDS), 'int64', arena.device, validate)
+        n = int(d_rows.shape[0])
+        if isinstance(rows, torch.Tensor) and rows.is_cuda:
+            tiles = -(-h // TILE_H) * ((d_rows[:, 2].clamp(0, 8192) + (TILE_W - 1)) // TILE_W)
+            d_table = torch.cat([d_rows.reshape(-1), tiles.new_zeros(1), tiles.cumsum(0)])
+        else:
+            d_table = torch.from_numpy(strip_table(h_rows, h)).to(arena.device, non_blocking=True)
+    if h_rows is not None:
+        if h_sources is None:
+            raise ValueError('quad_strips_u8: host rows need a host source table (or validate=True) to be checked against')
+        if ((h_sources[:, 0] < 0) | (h_sources[:, 0] + 3 * h_sources[:, 1] * h_sources[:, 2] > int(arena.numel()))).any():
+            raise ValueError(f'quad_strips_u8: a source leaves the arena of {int(arena.numel())} bytes')
+        check_strip_rows(h_rows, h_sources, h, out_bytes)
+    _require_cuda(arena)
+    out = torch.empty((out_bytes,), dtype=torch.uint8, device=arena.device)
+    if n:
+        check(lib.vkas_quad_strips_u8(_p(arena), int(arena.numel()), _p(d_sources), int(d_sources.shape[0]), _p(d_table), n, h,
+                                      _p(out), out_bytes, _stream()), 'quad_strips_u8')
+    return out
+
+
 def crop_warp(arena: torch.Tensor, sources, rows, size: Tuple[int, int], validate: bool = True,
               out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Training crops of annotated pages: one affine map and one photometric jitter per output image, in one launch
