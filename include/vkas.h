@@ -609,6 +609,37 @@ long long vkas_quad_nms_workspace_bytes(int B, int K, int max_pairs);
 int vkas_quad_nms(const int* rows, const int* count, const float* probs, int B, int K, double iou_thr, int max_pairs,
                   void* workspace, size_t workspace_bytes, unsigned char* keep, int* suppressor, long long* stats, int* rounds,
                   void* stream);
+/* Scoring detected text lines against annotated ones with one-to-one matches, splits and merges (inferencing/
+ * line_evaluation.py holds the rule - this project's own - and the host oracles match_lines_host, the sequential form, and
+ * match_lines_rounds_host).  Tables as for vkas_quad_match_ranked (no probs); tr_q8 and tp_q8 in 1..256 are the recall and
+ * precision thresholds as rint(x * 256); cover_thr in (0, 1].  A row takes part iff it lies within the (clamped) count and
+ * its valid word is set.  For a box-overlapping pair one clip of p against g (that of vkas_quad_match) gives inter2.  With a
+ * don't-care g: p is IGNORED iff inter2 >= cover_thr * area2_p (one rounding, inclusive); don't-care gts and ignored preds
+ * take no further part.  With a care g: I = int64(floor(min(inter2, 2^41))), A = min(max(area2, 0), 2^41) of either row;
+ * rec_ok <=> 256 I >= tr_q8 A_g, prec_ok <=> 256 I >= tp_q8 A_p, all int64; the pair is a candidate iff I > 0 and one of the
+ * two holds.  Phase A: (g, p) match one to one iff both tests hold and no other pair of g's row or p's column passes both.
+ * Phase B, free care gts ascending: S_g = the free preds with prec_ok; g is SPLIT into them iff |S_g| >= 2 and
+ * 256 sum I >= tr_q8 A_g.  Phase C, free preds ascending: M_p = the free care gts with rec_ok; they are MERGED into p iff
+ * |M_p| >= 2 and 256 sum I >= tp_q8 A_p.  B and C are computed as rounds: every ready gt (pred) offers itself to its set, a
+ * pred (gt) keeps the lowest offer, a ready gt (pred) takes its set iff it holds all of it; a round reads what the previous
+ * one left.  Outputs: gt_kind (B,M) uint8 = 0 absent, 1 unmatched, 2 one-to-one, 3 split, 4 merged, 5 don't care; gt_group
+ * (B,M) int32 = the pred for 2 and 4, g for 3, else -1; pred_kind (B,N) uint8 = 0 absent, 1 unmatched, 2 one-to-one, 3 split
+ * part, 4 merge, 5 ignored; pred_group (B,N) int32 = the gt for 2 and 3, p for 4, else -1; stats (B,16) int64 = n_gt (care),
+ * n_pred (taking part, not ignored), one_to_one, split_gt, split_pred, merged_gt, merge_pred, n_dc, n_ignored, pairs (box
+ * pairs of rows taking part), candidates (among care gts and preds not ignored), status, rounds_split, rounds_merge, 0, 0;
+ * rounds (B,2) int32, may be NULL = the two round counts again.  An image with more than max_pairs candidates keeps its
+ * true counts and gets status = 1, no match of any kind and both round counts 0: never a partial result.  Four launches on
+ * one stream (counting pass over 64 x 64 tiles, scan, filling pass, one workgroup per image for the phases); integer
+ * atomics in LDS only, no allocation, no synchronisation, every output element and every workspace word that is read is
+ * written by the call's own kernels: capture-safe and bit-identical from run to run; reads are bounded by the tables and
+ * stores by the buffers whatever the tables hold.  B in 0..65535, M and N in 1..8192 (beyond: an error, not a clamp),
+ * max_pairs >= 0, B*max_pairs < 2^31; tables and workspace 16-byte aligned, stats 8-byte aligned, workspace at least
+ * vkas_line_match_workspace_bytes (-1 on bad arguments).  Argument errors return before any launch. */
+long long vkas_line_match_workspace_bytes(int B, int M, int N, int max_pairs);
+int vkas_line_match(const int* gt_rows, const int* gt_count, const unsigned char* gt_care, const int* pred_rows,
+                    const int* pred_count, int B, int M, int N, int tr_q8, int tp_q8, double cover_thr, int max_pairs,
+                    void* workspace, size_t workspace_bytes, unsigned char* gt_kind, int* gt_group, unsigned char* pred_kind,
+                    int* pred_group, long long* stats, int* rounds, void* stream);
 /* Grouping character quadrilaterals into text lines (inferencing/lines.py holds the rule - this project's own, all integer -
  * and the host oracle quad_lines_host).  rows (B,K,16) int32 match rows, count (B) clamped to [0, K] on the device; gap_q4
  * and cross_q4 in 1..4096, ratio_q4 in 16..256 (Q4).  A row takes part iff it lies within the count and its valid word is

@@ -198,6 +198,9 @@ _SIGS = {
     'vkas_quad_rows': (c_int, [_P, _P, c_int, c_int, _P, _P]),
     'vkas_quad_nms_workspace_bytes': (c_longlong, [c_int, c_int, c_int]),
     'vkas_quad_nms': (c_int, [_P, _P, _P, c_int, c_int, c_double, c_int, _P, c_size_t, _P, _P, _P, _P, _P]),
+    'vkas_line_match_workspace_bytes': (c_longlong, [c_int, c_int, c_int, c_int]),
+    'vkas_line_match': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_double, c_int, _P, c_size_t, _P, _P, _P,
+                                _P, _P, _P, _P]),
     'vkas_quad_lines_workspace_bytes': (c_longlong, [c_int, c_int]),
     'vkas_quad_lines': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_size_t, _P, _P, _P, _P, _P]),
     'vkas_text_regions_workspace_bytes': (c_longlong, [c_int, c_int, c_int, c_int]),

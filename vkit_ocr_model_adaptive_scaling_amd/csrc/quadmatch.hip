@@ -35,114 +35,16 @@
 // No float atomics, no allocation, no synchronisation: capture-safe and bit-identical from run to run.  Table reads are
 // bounded by the tables' K rows (a row beyond the clamped count is dropped after its load), ring stores by RING_MAX, candidate stores by max_pairs, tile stores by the padded tile grid
 // the workspace is sized for: no table content makes a kernel touch memory outside its buffers.
-#include "vkas_common.h"
-
-#include <limits.h>
+// The tile constants, the row staging and the clip live in quad_clip.h, which linematch.hip shares.
+#include "quad_clip.h"
 
 namespace {
 
-constexpr int QM_TILE = 64;                // gts and preds per tile
-constexpr int QM_THREADS = 128;            // pair pass
-constexpr int QM_WAVES = QM_THREADS / 64;
-constexpr int QM_LIST = QM_TILE * QM_TILE / QM_WAVES;  // list slots per wave
-constexpr int QM_RING = 8;                 // vertices per ring
-constexpr int QM_MAX = 8192;               // quads per image and side (the LDS state of the scan and matching passes)
-constexpr int QM_BLOCK = 1024;             // scan and matching passes
 constexpr int QM_STATS = 6;                // tp, n_gt, n_pred, pairs, candidates, status
 constexpr int QR_STATS = 8;                // ranked: tp, fp, ignored, n_gt, n_pred, pairs, candidates, status
 constexpr int QR_TMAX = 16;                // ranked: IoU thresholds per call
 constexpr int QM_MATCH = 0, QM_SELF = 1, QM_RANKED = 2;  // what the three shared passes serve
 constexpr unsigned long long QM_TAKEN = ~0ull;
-
-#pragma clang fp contract(off)
-__device__ __forceinline__ double qm_mul(double a, double b) { return a * b; }
-__device__ __forceinline__ double qm_add(double a, double b) { return a + b; }
-__device__ __forceinline__ double qm_sub(double a, double b) { return a - b; }
-__device__ __forceinline__ double qm_div(double a, double b) { return a / b; }
-#pragma clang fp contract(fast)
-
-__device__ __forceinline__ int qm_clamp(int v, int hi) { return min(max(v, 0), hi); }
-__device__ __forceinline__ bool qm_finite_bits(unsigned b) { return (b & 0x7f800000u) != 0x7f800000u; }
-
-// The rule's IoU of the LDS rows g and p (four int4 each), and through inter2_out the clamped twice-intersection it is made
-// of (quad_inter2_host).  ring: this thread's slots, element (r, k, c) at ring[((r * QM_RING + k) * 2 + c) * QM_THREADS].
-__device__ __forceinline__ double qm_inter2_iou(const int4* g, const int4* p, double* ring, double* inter2_out) {
-#define QM_AT(r, k, c) ring[(((r) * QM_RING + (k)) * 2 + (c)) * QM_THREADS]
-  const int4 g01 = g[0], g23 = g[1], gb = g[2], ga = g[3];
-  const int4 p01 = p[0], p23 = p[1], pb = p[2], pa = p[3];
-  const long oy = min(gb.x, pb.x), ox = min(gb.y, pb.y);
-  const double gy[4] = {(double)(g01.x - oy), (double)(g01.z - oy), (double)(g23.x - oy), (double)(g23.z - oy)};
-  const double gx[4] = {(double)(g01.y - ox), (double)(g01.w - ox), (double)(g23.y - ox), (double)(g23.w - ox)};
-  QM_AT(0, 0, 0) = (double)(p01.x - oy);
-  QM_AT(0, 0, 1) = (double)(p01.y - ox);
-  QM_AT(0, 1, 0) = (double)(p01.z - oy);
-  QM_AT(0, 1, 1) = (double)(p01.w - ox);
-  QM_AT(0, 2, 0) = (double)(p23.x - oy);
-  QM_AT(0, 2, 1) = (double)(p23.y - ox);
-  QM_AT(0, 3, 0) = (double)(p23.z - oy);
-  QM_AT(0, 3, 1) = (double)(p23.w - ox);
-  int n = 4;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int src = e & 1, dst = src ^ 1;
-    const double ay = gy[e], ax = gx[e];
-    const double ey = qm_sub(gy[(e + 1) & 3], ay), ex = qm_sub(gx[(e + 1) & 3], ax);
-    int m = 0;
-    if (n > 0) {
-      const double fy = QM_AT(src, 0, 0), fx = QM_AT(src, 0, 1);
-      const double fd = qm_sub(qm_mul(ex, qm_sub(fy, ay)), qm_mul(ey, qm_sub(fx, ax)));
-      double vy = fy, vx = fx, dv = fd;
-      for (int k = 0; k < n; ++k) {
-        double wy = fy, wx = fx, dw = fd;
-        if (k + 1 < n) {
-          wy = QM_AT(src, k + 1, 0);
-          wx = QM_AT(src, k + 1, 1);
-          dw = qm_sub(qm_mul(ex, qm_sub(wy, ay)), qm_mul(ey, qm_sub(wx, ax)));
-        }
-        if (dv >= 0.0 && m < QM_RING) {
-          QM_AT(dst, m, 0) = vy;
-          QM_AT(dst, m, 1) = vx;
-          ++m;
-        }
-        if ((dv >= 0.0) != (dw >= 0.0) && m < QM_RING) {
-          const double t = qm_div(dv, qm_sub(dv, dw));
-          QM_AT(dst, m, 0) = qm_add(vy, qm_mul(t, qm_sub(wy, vy)));
-          QM_AT(dst, m, 1) = qm_add(vx, qm_mul(t, qm_sub(wx, vx)));
-          ++m;
-        }
-        vy = wy;
-        vx = wx;
-        dv = dw;
-      }
-    }
-    n = m;
-  }
-  double acc = 0.0;  // four clips: the result is in ring 0
-  if (n > 0) {
-    const double fy = QM_AT(0, 0, 0), fx = QM_AT(0, 0, 1);
-    double y0 = fy, x0 = fx;
-    for (int k = 0; k < n; ++k) {
-      double y1 = fy, x1 = fx;
-      if (k + 1 < n) {
-        y1 = QM_AT(0, k + 1, 0);
-        x1 = QM_AT(0, k + 1, 1);
-      }
-      acc = qm_add(acc, qm_sub(qm_mul(x0, y1), qm_mul(x1, y0)));
-      y0 = y1;
-      x0 = x1;
-    }
-  }
-#undef QM_AT
-  const double ag = (double)(long)(((unsigned long long)(unsigned)ga.y << 32) | (unsigned)ga.x);
-  const double ap = (double)(long)(((unsigned long long)(unsigned)pa.y << 32) | (unsigned)pa.x);
-  const double hi = ap < ag ? ap : ag;
-  double inter2 = acc;
-  if (inter2 > hi) inter2 = hi;
-  if (inter2 < 0.0) inter2 = 0.0;
-  *inter2_out = inter2;
-  const double den = qm_sub(qm_add(ag, ap), inter2);
-  return den > 0.0 ? qm_div(inter2, den) : 0.0;
-}
 
 __device__ __forceinline__ double qm_iou(const int4* g, const int4* p, double* ring) {
   double inter2;
@@ -204,41 +106,25 @@ __global__ __launch_bounds__(QM_THREADS) void qm_pair_kernel(const int* __restri
   if (FILL && status != 0) return;  // nothing of this image is stored
   unsigned long long word = 0ull;
   if (FILL && tid < QM_TILE) word = words[word_at + tid];
-  // a part of the 128 rows of the tile: 0, 1 = the corners, 2 = the box, 3 = area and valid; two loads per thread and half.
-  // The row index is clamped to the table; a row beyond the count becomes a zero row (valid = 0) after the load.
-  const auto stage = [&](int half) {
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int i = tid + k * QM_THREADS, row = i >> 1, part = 2 * half + (i & 1);
-      int4 v;
-      bool keep;
-      int at;
-      if (row < QM_TILE) {
-        at = min(g0 + row, M - 1);
-        v = reinterpret_cast<const int4*>(gt_rows)[((long)b * M + at) * 4 + part];
-        keep = g0 + row < ng;
+  // a part of the 128 rows of the tile: 0, 1 = the corners, 2 = the box, 3 = area and valid (qm_stage_half); what rides in
+  // the zero word of part 3 is put there as the row is staged
+  const auto fix = [&](int4& v, bool is_gt, int at, int part) {
+    if (SELF && part == 3) {  // M == N: one table
+      const unsigned pb = __float_as_uint(probs[(long)b * M + at]);
+      v.z = (v.z != 0 && qm_finite_bits(pb)) ? 1 : 0;
+      v.w = (int)pb;
+    }
+    if (RANKED && part == 3) {
+      if (is_gt) {
+        v.w = x.gt_care ? (x.gt_care[(long)b * M + at] != 0 ? 1 : 0) : 1;
       } else {
-        at = min(p0 + row - QM_TILE, N - 1);
-        v = reinterpret_cast<const int4*>(pred_rows)[((long)b * N + at) * 4 + part];
-        keep = p0 + row - QM_TILE < np;
-      }
-      if (SELF && part == 3) {  // M == N: one table
-        const unsigned pb = __float_as_uint(probs[(long)b * M + at]);
+        const unsigned pb = __float_as_uint(probs[(long)b * N + at]);
         v.z = (v.z != 0 && qm_finite_bits(pb)) ? 1 : 0;
         v.w = (int)pb;
       }
-      if (RANKED && part == 3) {
-        if (row < QM_TILE) {
-          v.w = x.gt_care ? (x.gt_care[(long)b * M + at] != 0 ? 1 : 0) : 1;
-        } else {
-          const unsigned pb = __float_as_uint(probs[(long)b * N + at]);
-          v.z = (v.z != 0 && qm_finite_bits(pb)) ? 1 : 0;
-          v.w = (int)pb;
-        }
-      }
-      s_rows[row * 4 + part] = keep ? v : make_int4(0, 0, 0, 0);
     }
   };
+  const auto stage = [&](int half) { qm_stage_half(s_rows, gt_rows, pred_rows, b, M, N, g0, p0, ng, np, half, tid, fix); };
   if (tid < QM_TILE) s_word[tid] = word;
   if (RANKED && !FILL) {
     if (tid == 0) s_cover = 0ull;
@@ -337,12 +223,6 @@ __global__ __launch_bounds__(QM_THREADS) void qm_pair_kernel(const int* __restri
       tile_pairs[((long)b * gridDim.y + tm) * NT + tn] = total;
     }
   }
-}
-
-__device__ __forceinline__ int qm_wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // SELF (the suppression): stats = kept (written by the rounds), n = the clamped count, n_valid = the rows that take part.
@@ -881,7 +761,6 @@ __global__ __launch_bounds__(256) void qm_rows_kernel(const double* __restrict__
   out[3] = r3;
 }
 
-size_t qm_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
 QmLayout qm_layout(int B, int M, int N, int max_pairs, bool with_iou = true) {
   QmLayout l;

@@ -29,3 +29,5 @@ from .orient import (orient_regions, oriented_rects, region_directions, region_e
 from .strips import (QuadStrips, StripLayout, check_strip_rows, quad_strips_host, remap_strip_points, strip_params, strip_rows,
                      strip_table, strip_warp)
 from .line_strips import quad_strips, strips_for_results
+from .line_evaluation import (LineMatchResult, LineScore, check_line_thresholds, evaluate_lines, evaluate_lines_host,
+                              line_pairs, match_lines_host, match_lines_rounds_host)

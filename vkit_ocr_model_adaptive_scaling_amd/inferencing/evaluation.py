@@ -51,7 +51,7 @@ unmatched), ``tp``, ``n_gt`` / ``n_pred`` (the valid rows within the count), ``p
 
 Average precision over the scores, several IoU thresholds at once and don't-care annotations: inferencing/ranking.py.
 
-Out of scope: many-to-one matching, text-line or word level scoring."""
+Text lines and words, scored with one-to-many splits and many-to-one merges: inferencing/line_evaluation.py."""
 from typing import List, Optional, Sequence, Tuple
 
 import attrs

@@ -62,7 +62,7 @@ the same, ICDAR matches once); a don't-care annotation is never matched, so a pr
 then ignored; everything is measured on the Q4 grid of the match rows; precision is interpolated at all points, not at 101
 recall levels.
 
-Out of scope: many-to-one matching, text-line or word level scoring."""
+Text lines and words, scored with one-to-many splits and many-to-one merges: inferencing/line_evaluation.py."""
 import math
 from typing import List, Optional, Sequence, Tuple
 

@@ -2487,6 +2487,66 @@ def match_quads_ranked(gt_rows: torch.Tensor, gt_count: torch.Tensor, gt_care: O
     return pred_match, pred_state, gt_match, pred_iou, covered, stats, dc_stats
 
 
+def match_lines(gt_rows: torch.Tensor, gt_count: torch.Tensor, gt_care: Optional[torch.Tensor], pred_rows: torch.Tensor,
+                pred_count: torch.Tensor, recall_thr: float = 0.8, precision_thr: float = 0.4, cover_thr: float = 0.5,
+                max_pairs: Optional[int] = None, rounds: Optional[torch.Tensor] = None):
+    """Detected text lines scored against annotated ones with one-to-one matches, splits and merges on the device
+    (csrc/linematch.hip; the rule and the host oracles: inferencing/line_evaluation.py).  ``gt_rows`` (B, M, 16) / ``gt_count``
+    (B,) and ``pred_rows`` (B, N, 16) / ``pred_count`` (B,): int32 match rows and counts; ``gt_care`` (B, M) uint8 with 0 =
+    don't care, or None = every annotation counts; all on the device, M and N at most 8192.  ``recall_thr`` and
+    ``precision_thr`` in (0, 1] become Q8 integers by ``rint(x * 256)``; ``cover_thr`` in (0, 1].  ``max_pairs`` is the capacity
+    for stored candidates per image, 4 * max(M, N) by default.  Returns ``(gt_kind (B, M) uint8, gt_group (B, M) int32,
+    pred_kind (B, N) uint8, pred_group (B, N) int32, stats (B, 16) int64)`` as the rule lays them out.  An image over the
+    capacity keeps its true counts and gets ``status = 1`` and no match.  ``rounds``, if given, is a (B, 2) int32 device tensor
+    that receives the split and merge rounds.  Four launches; allocates only its outputs and workspace and never
+    synchronises, so it can be captured into a HIP graph."""
+    what = 'match_lines'
+    for name, t, other in (('gt', gt_rows, gt_count), ('pred', pred_rows, pred_count)):
+        if t.dim() != 3 or t.shape[2] != 16:
+            raise ValueError(f'{what}: {name}_rows must be (B, K, 16), got {tuple(t.shape)}')
+        if tuple(other.shape) != (t.shape[0],):
+            raise ValueError(f'{what}: {name}_count must be {(t.shape[0],)}, got {tuple(other.shape)}')
+        if t.dtype != torch.int32 or other.dtype != torch.int32:
+            raise ValueError(f'{what}: {name}_rows and {name}_count must be int32, got {t.dtype} and {other.dtype}')
+    B, M, _ = (int(v) for v in gt_rows.shape)
+    N = int(pred_rows.shape[1])
+    if pred_rows.shape[0] != B:
+        raise ValueError(f'{what}: {B} images of annotations against {pred_rows.shape[0]} of predictions')
+    if gt_care is not None and (tuple(gt_care.shape) != (B, M) or gt_care.dtype != torch.uint8):
+        raise ValueError(f'{what}: gt_care must be a {(B, M)} uint8 tensor, got {tuple(gt_care.shape)} {gt_care.dtype}')
+    if not (1 <= M <= 8192 and 1 <= N <= 8192):
+        raise ValueError(f'{what}: M = {M} and N = {N} must lie in 1..8192')
+    if B > 65535:
+        raise ValueError(f'{what}: B = {B} above 65535')
+    from .inferencing.line_evaluation import check_line_thresholds  # the rule's own check, stated once
+    tr_q8, tp_q8, cover_thr = check_line_thresholds(recall_thr, precision_thr, cover_thr)
+    max_pairs = 4 * max(M, N) if max_pairs is None else int(max_pairs)
+    if max_pairs < 0 or B * max_pairs >= 1 << 31:
+        raise ValueError(f'{what}: max_pairs = {max_pairs} must be >= 0 and B*max_pairs below 2^31')
+    if rounds is not None and (tuple(rounds.shape) != (B, 2) or rounds.dtype != torch.int32 or not rounds.is_contiguous()):
+        raise ValueError(f'{what}: rounds must be a contiguous ({B}, 2) int32 tensor')
+    tensors = (gt_rows, gt_count, pred_rows, pred_count) + tuple(t for t in (gt_care, rounds) if t is not None)
+    _require_cuda(*tensors)
+    if any(t.device != gt_rows.device for t in tensors):
+        raise ValueError(f'{what}: all tensors must be on one device')
+    gt_rows, gt_count, pred_rows, pred_count = (t.contiguous() for t in (gt_rows, gt_count, pred_rows, pred_count))
+    gt_care = None if gt_care is None else gt_care.contiguous()
+    dev = gt_rows.device
+    new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+    gt_kind, gt_group = new((B, M), torch.uint8), new((B, M), torch.int32)
+    pred_kind, pred_group = new((B, N), torch.uint8), new((B, N), torch.int32)
+    stats = new((B, 16), torch.int64)
+    if B:
+        nbytes = lib.vkas_line_match_workspace_bytes(B, M, N, max_pairs)
+        if nbytes < 0:
+            check(-1, what)
+        ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+        check(lib.vkas_line_match(_p(gt_rows), _p(gt_count), _p(gt_care), _p(pred_rows), _p(pred_count), B, M, N, tr_q8, tp_q8,
+                                  cover_thr, max_pairs, _p(ws), ws.numel(), _p(gt_kind), _p(gt_group), _p(pred_kind),
+                                  _p(pred_group), _p(stats), _p(rounds), _stream()), what)
+    return gt_kind, gt_group, pred_kind, pred_group, stats
+
+
 def quad_rows(quads: torch.Tensor, valid: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``inferencing.match_rows`` on the device (csrc/quadmatch.hip): ``quads`` (B, K, 4, 2) float64 ``(y, x)`` corners and an
     optional ``valid`` (B, K) uint8 on the device -> (B, K, 16) int32 match rows, equal to the host's on every input (an
