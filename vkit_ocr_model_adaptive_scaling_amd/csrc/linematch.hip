@@ -1,30 +1,21 @@
 // Scoring detected text lines against annotated ones with one-to-one matches, splits and merges (inferencing/
 // line_evaluation.py holds the rule and the host oracles match_lines_host / match_lines_rounds_host; the rule is this
-// project's own).  rows (B, K, 16) int32 are the match rows of quadmatch.hip.  Four launches on one stream:
+// project's own).  rows (B, K, 16) int32 are the match rows of quadmatch.hip.  Four launches on one stream: the three pair
+// passes of quad_pairs.h under LmRule - lm_pair_kernel<false>, lm_scan_kernel, lm_pair_kernel<true> - then the phases:
 //
-//   lm_pair_kernel<false>  the counting pass: a 128-thread workgroup owns a 64 gt x 64 pred tile of one image, box-tests it
-//                          and clips the overlapping pairs exactly as qm_pair_kernel does (quad_clip.h: the same staging,
-//                          the same clip).  A pair with a don't-care gt takes the coverage test of the ranked matching and
-//                          sets the pred's bit of the tile's cover word; a care pair takes I = floor(min(inter2, 2^41)),
-//                          the two integer tests rec_ok / prec_ok on the clamped areas, and sets bit pj of the gt's word
-//                          when it is a candidate (LDS atomic OR: integer, order-free).
-//   lm_scan_kernel         one workgroup per image: the cover words OR-ed down the gt tiles = the ignored preds (kept as
-//                          B x NT words); every candidate word loses the ignored preds' bits and is written back; per gt the
-//                          prefix of the popcounts over the pred tiles, then the exclusive scan over the gts = the CSR row
-//                          offsets; n_gt, n_pred, n_dc, n_ignored, pairs, candidates, status.
-//   lm_pair_kernel<true>   the filling pass: the same tile body with the stored words in place of the box test; a candidate
-//                          is clipped again (same code, same bits) and stored as one 64-bit word  I << 15 | prec_ok << 14 |
-//                          rec_ok << 13 | pred  at  row offset + tile prefix + popcount of the lower bits: no slot
-//                          atomics, preds ascending within a gt.
-//   lm_phase_kernel        one workgroup per image: phase A (row and column counts of Q, integer LDS atomics), the split
-//                          rounds, the merge rounds, then one sweep that writes every output.
+//   LmRule           a pair with a don't-care gt takes the coverage test of the ranked matching and sets the pred's bit of the
+//                    tile's cover word; a care pair takes I = floor(min(inter2, 2^41)) and the two integer tests rec_ok /
+//                    prec_ok on the clamped areas, and is a candidate when I > 0 and one of them holds.  Its slot holds one
+//                    64-bit word  I << 15 | prec_ok << 14 | rec_ok << 13 | pred.
+//   lm_scan_kernel   the cover words OR-ed down the gt tiles = the ignored preds (kept as B x NT words), which are the scan's
+//                    mask: every candidate word loses their bits; n_gt, n_pred, n_dc, n_ignored, pairs, candidates, status.
+//   lm_phase_kernel  one workgroup per image: phase A (row and column counts of Q, integer LDS atomics), the split rounds,
+//                    the merge rounds, then one sweep that writes every output.
 //
-// Integer atomics only (add, min on 32 and 64-bit words in LDS): nothing depends on arrival order.  No allocation, no
-// synchronisation: capture-safe and bit-identical from run to run.  Table reads are bounded by the tables' K rows, ring
-// stores by the ring's 8 slots, candidate stores by max_pairs, tile stores by the padded tile grid the workspace is sized
-// for, and a pred index read back from a candidate word is checked against N: no table content makes a kernel touch memory
-// outside its buffers.  Every output word and every workspace word that is read is written earlier in the same call.
-#include "quad_clip.h"
+// Integer atomics only (add, min on 32 and 64-bit words in LDS): nothing depends on arrival order.  A pred index read back
+// from a candidate word is checked against N.  Every output word and every workspace word that is read is written earlier
+// in the same call.
+#include "quad_pairs.h"
 
 namespace {
 
@@ -41,214 +32,82 @@ __host__ __device__ constexpr size_t lm_lds_bytes(int M, int N) {
 
 __device__ __forceinline__ long lm_area(long a) { return min(max(a, 0L), LM_AREA_MAX); }
 
-// workspace: words (B, NT, Mp) u64, cand (B, max_pairs) u64, cover (B, MT * NT) u64, ignored (B, NT) u64,
-// tpre (B, NT, Mp) int, rowoff (B, Mp + 1) int, tile_pairs (B, MT * NT) int
-struct LmLayout {
-  size_t words, cand, cover, ignored, tpre, rowoff, tile_pairs, bytes;
-  int MT, NT, Mp;
+struct LmRule : QpRule {
+  const unsigned char* gt_care;  // (B, M), 0 = don't care; null = every gt is a care gt
+  int tr_q8, tp_q8;
+  double cover_thr;
+  unsigned long long* cover;     // (B, MT * NT): per tile, bit j = pred j of the tile is covered by a don't-care gt of the tile
+  long long* stats;              // (B, 16)
+  unsigned long long* cand;      // (B, max_pairs)
+  struct Tile {
+    unsigned long long cover;
+  };
+  __device__ __forceinline__ void begin(Tile& s, int tid) const {
+    if (tid == 0) s.cover = 0ull;
+  }
+  __device__ __forceinline__ void fix(int4& v, bool is_gt, int b, int M, int, int at, int part) const {
+    if (part == 3 && is_gt) qp_fix_care(v, gt_care, (long)b * M + at);  // the care flag rides in the gt row's zero word
+  }
+  __device__ __forceinline__ long long status(int b) const { return stats[(long)b * LM_STATS + 11]; }
+  template <bool FILL>
+  __device__ __forceinline__ bool pair(Tile& s, const int4& g3, const int4& p3, int pj, double, double inter2,
+                                       unsigned long long& val) const {
+    if (g3.w == 0) {  // a don't-care gt: the coverage test, never a candidate (the fill never meets one: its words are zero)
+      if (!FILL && qp_covers(cover_thr, inter2, p3)) atomicOr(&s.cover, 1ull << pj);
+      return false;
+    }
+    const long I = (long)__builtin_floor(inter2 < (double)LM_AREA_MAX ? inter2 : (double)LM_AREA_MAX);  // inter2 >= 0, never NaN
+    const bool rec = 256L * I >= (long)tr_q8 * lm_area(qm_area2(g3));
+    const bool prec = 256L * I >= (long)tp_q8 * lm_area(qm_area2(p3));
+    val = ((unsigned long long)I << (LM_PRED_BITS + 2)) | ((unsigned long long)prec << (LM_PRED_BITS + 1)) |
+          ((unsigned long long)rec << LM_PRED_BITS);
+    return I > 0 && (rec || prec);
+  }
+  __device__ __forceinline__ void store(long at, int pred, unsigned long long val) const { cand[at] = val | (unsigned)pred; }
+  __device__ __forceinline__ void tile_out(const Tile& s, long tile, int tid) const {
+    if (tid == 0) cover[tile] = s.cover;
+  }
 };
 
 template <bool FILL>
-__global__ __launch_bounds__(QM_THREADS) void lm_pair_kernel(const int* __restrict__ gt_rows, const int* __restrict__ gt_count,
-                                                              const unsigned char* __restrict__ gt_care,
-                                                              const int* __restrict__ pred_rows,
-                                                              const int* __restrict__ pred_count, int M, int N, int Mp,
-                                                              int NT, int tr_q8, int tp_q8, double cover_thr,
-                                                              unsigned long long* __restrict__ words,
-                                                              unsigned long long* __restrict__ cover,
-                                                              const int* __restrict__ tpre, int* __restrict__ tile_pairs,
-                                                              const int* __restrict__ rowoff,
-                                                              const long long* __restrict__ stats,
-                                                              unsigned long long* __restrict__ cand, int max_pairs) {
-  __shared__ int4 s_rows[2 * QM_TILE * 4];
-  __shared__ unsigned long long s_word[QM_TILE];
-  __shared__ unsigned short s_list[QM_WAVES * QM_LIST];
-  __shared__ int s_cnt[QM_WAVES];
-  __shared__ double s_ring[2 * QM_RING * 2 * QM_THREADS];
-  __shared__ unsigned long long s_cover;  // the counting pass only
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tn = blockIdx.x, tm = blockIdx.y, b = blockIdx.z;
-  const int g0 = tm * QM_TILE, p0 = tn * QM_TILE;
-  const long word_at = ((long)b * NT + tn) * Mp + g0;
-  const long tile = ((long)b * gridDim.y + tm) * NT + tn;
-  // every early return is taken by the whole workgroup
-  const long long status = FILL ? stats[(long)b * LM_STATS + 11] : 0;
-  const int ng = qm_clamp(gt_count[b], M), np = qm_clamp(pred_count[b], N);
-  if (FILL && status != 0) return;  // nothing of this image is stored
-  unsigned long long word = 0ull;
-  if (FILL && tid < QM_TILE) word = words[word_at + tid];
-  const auto fix = [&](int4& v, bool is_gt, int at, int part) {  // the care flag rides in the gt row's zero word
-    if (part == 3 && is_gt) v.w = gt_care ? (gt_care[(long)b * M + at] != 0 ? 1 : 0) : 1;
-  };
-  const auto stage = [&](int half) { qm_stage_half(s_rows, gt_rows, pred_rows, b, M, N, g0, p0, ng, np, half, tid, fix); };
-  if (tid < QM_TILE) s_word[tid] = word;
-  if (!FILL && tid == 0) s_cover = 0ull;
-  if (FILL) {  // most tiles of a page hold no candidate: they end here, on 512 bytes
-    __syncthreads();
-    if (__ballot(s_word[lane] != 0ull) == 0ull) return;
-  }
-  stage(1);  // the box test needs boxes and valid only; a tile without a pair ends on them
-  __syncthreads();
-
-  const int4 pbox = s_rows[(QM_TILE + lane) * 4 + 2];
-  const bool pvalid = s_rows[(QM_TILE + lane) * 4 + 3].z != 0;
-  int cnt = 0;
-  for (int s = 0; s < QM_TILE / QM_WAVES; ++s) {
-    const int gi = wave * (QM_TILE / QM_WAVES) + s;
-    bool hit;
-    if (FILL) {
-      hit = (s_word[gi] >> lane) & 1ull;
-    } else {
-      const int4 gbox = s_rows[gi * 4 + 2];
-      hit = pvalid && s_rows[gi * 4 + 3].z != 0 && gbox.x <= pbox.z && pbox.x <= gbox.z && gbox.y <= pbox.w &&
-            pbox.y <= gbox.w;
-    }
-    const unsigned long long bits = __ballot(hit);
-    if (hit) s_list[wave * QM_LIST + cnt + __popcll(bits & ((1ull << lane) - 1ull))] = (unsigned short)(gi * QM_TILE + lane);
-    cnt += __popcll(bits);  // <= 32 * 64 = QM_LIST
-  }
-  if (lane == 0) s_cnt[wave] = cnt;
-  __syncthreads();
-  const int c0 = s_cnt[0], total = c0 + s_cnt[1];
-  static_assert(QM_WAVES == 2, "the two lists are read as one");
-  if (total == 0) {  // the whole workgroup
-    if (!FILL) {
-      if (tid < QM_TILE) words[word_at + tid] = 0ull;
-      if (tid == 0) {
-        tile_pairs[tile] = 0;
-        cover[tile] = 0ull;
-      }
-    }
-    return;
-  }
-  stage(0);
-  __syncthreads();
-  for (int e = tid; e < total; e += QM_THREADS) {
-    const int q = e < c0 ? s_list[e] : s_list[QM_LIST + e - c0];
-    const int gi = q >> 6, pj = q & 63;
-    double inter2;
-    qm_inter2_iou(s_rows + gi * 4, s_rows + (QM_TILE + pj) * 4, s_ring + tid, &inter2);
-    const int4 ga = s_rows[gi * 4 + 3], pa = s_rows[(QM_TILE + pj) * 4 + 3];
-    if (ga.w == 0) {  // a don't-care gt: the coverage test, never a candidate (the fill never meets one: its words are zero)
-      if (!FILL && inter2 >= qm_mul(cover_thr, (double)qm_area2(pa))) atomicOr(&s_cover, 1ull << pj);
-      continue;
-    }
-    const long I = (long)__builtin_floor(inter2 < (double)LM_AREA_MAX ? inter2 : (double)LM_AREA_MAX);  // inter2 >= 0, never NaN
-    const bool rec = 256L * I >= (long)tr_q8 * lm_area(qm_area2(ga));
-    const bool prec = 256L * I >= (long)tp_q8 * lm_area(qm_area2(pa));
-    if (!(I > 0 && (rec || prec))) continue;
-    if (FILL) {
-      const long slot = (long)rowoff[(long)b * (Mp + 1) + g0 + gi] + tpre[word_at + gi] +
-                        __popcll(s_word[gi] & ((1ull << pj) - 1ull));
-      if (slot >= 0 && slot < max_pairs)
-        cand[(long)b * max_pairs + slot] = ((unsigned long long)I << (LM_PRED_BITS + 2)) |
-                                           ((unsigned long long)prec << (LM_PRED_BITS + 1)) |
-                                           ((unsigned long long)rec << LM_PRED_BITS) | (unsigned)(p0 + pj);
-    } else {
-      atomicOr(&s_word[gi], 1ull << pj);
-    }
-  }
-  if (!FILL) {
-    __syncthreads();
-    if (tid < QM_TILE) words[word_at + tid] = s_word[tid];
-    if (tid == 0) {
-      tile_pairs[tile] = total;
-      cover[tile] = s_cover;
-    }
-  }
+__global__ __launch_bounds__(QM_THREADS) void lm_pair_kernel(const QpTables t, const LmRule r) {
+  qp_tile<FILL>(t, r);
 }
 
 // stats words 0, 1 and 7..11: n_gt (care gts), n_pred (preds taking part that are not ignored), n_dc, n_ignored, pairs,
 // candidates, status.  The others are the phase kernel's.
-__global__ __launch_bounds__(QM_BLOCK) void lm_scan_kernel(const int* __restrict__ gt_rows, const int* __restrict__ gt_count,
-                                                            const unsigned char* __restrict__ gt_care,
-                                                            const int* __restrict__ pred_rows,
-                                                            const int* __restrict__ pred_count, int M, int N, int Mp, int NT,
-                                                            int MT, unsigned long long* __restrict__ words,
-                                                            const unsigned long long* __restrict__ cover,
-                                                            unsigned long long* __restrict__ ignored, int* __restrict__ tpre,
-                                                            const int* __restrict__ tile_pairs, int* __restrict__ rowoff,
-                                                            long long* __restrict__ stats, int max_pairs) {
-  __shared__ int s_cnt[QM_MAX];
-  __shared__ int s_wave[QM_BLOCK / 64];
+__global__ __launch_bounds__(QM_BLOCK) void lm_scan_kernel(const QpTables t, const LmRule r,
+                                                            unsigned long long* __restrict__ ignored) {
   __shared__ int s_sum[5];  // n_gt, n_dc, preds taking part, n_ignored, pairs
   __shared__ unsigned long long s_cov[QM_MAX / QM_TILE];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, b = blockIdx.x;
-  const int ng = qm_clamp(gt_count[b], M), np = qm_clamp(pred_count[b], N);
-  if (t < 5) s_sum[t] = 0;
-  int n_ign = 0;
-  if (t < NT) {  // NT <= QM_MAX / QM_TILE <= QM_BLOCK
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const int ng = qm_clamp(t.gt_count[b], t.M), np = qm_clamp(t.pred_count[b], t.N);
+  if (tid < 5) s_sum[tid] = 0;
+  int sums[4] = {0, 0, 0, 0};
+  if (tid < t.NT) {  // NT <= QM_MAX / QM_TILE <= QM_BLOCK
     unsigned long long w = 0ull;
-    for (int tm = 0; tm < MT; ++tm) w |= cover[((long)b * MT + tm) * NT + t];
-    s_cov[t] = w;
-    ignored[(long)b * NT + t] = w;
-    n_ign = __popcll(w);
+    for (int tm = 0; tm < t.MT; ++tm) w |= r.cover[((long)b * t.MT + tm) * t.NT + tid];
+    s_cov[tid] = w;
+    ignored[(long)b * t.NT + tid] = w;
+    sums[3] = __popcll(w);
   }
   __syncthreads();
-  for (int g = t; g < Mp; g += QM_BLOCK) {  // Mp <= QM_MAX
-    int run = 0;
-#pragma unroll 8
-    for (int tn = 0; tn < NT; ++tn) {
-      const long at = ((long)b * NT + tn) * Mp + g;
-      const unsigned long long w = words[at] & ~s_cov[tn];  // an ignored pred takes no further part
-      words[at] = w;
-      tpre[at] = run;
-      run += __popcll(w);
-    }
-    s_cnt[g] = run;
+  for (int g = tid; g < ng; g += QM_BLOCK) {
+    const bool part = qp_valid(t.gt_rows, t.M, b, g), care = !r.gt_care || r.gt_care[(long)b * t.M + g] != 0;
+    sums[0] += part && care;
+    sums[1] += part && !care;
   }
-  int n_gt = 0, n_dc = 0, n_part = 0, pairs = 0;
-  for (int g = t; g < ng; g += QM_BLOCK) {
-    const bool part = gt_rows[((long)b * M + g) * 16 + 14] != 0, care = !gt_care || gt_care[(long)b * M + g] != 0;
-    n_gt += part && care;
-    n_dc += part && !care;
-  }
-  for (int p = t; p < np; p += QM_BLOCK) n_part += pred_rows[((long)b * N + p) * 16 + 14] != 0;
-  for (int i = t; i < MT * NT; i += QM_BLOCK) pairs += tile_pairs[(long)b * MT * NT + i];  // <= M * N <= 2^26
-  __syncthreads();
-  n_gt = qm_wave_sum_i(n_gt);
-  n_dc = qm_wave_sum_i(n_dc);
-  n_part = qm_wave_sum_i(n_part);
-  n_ign = qm_wave_sum_i(n_ign);
-  pairs = qm_wave_sum_i(pairs);
-  if (lane == 0) {
-    atomicAdd(&s_sum[0], n_gt);
-    atomicAdd(&s_sum[1], n_dc);
-    atomicAdd(&s_sum[2], n_part);
-    atomicAdd(&s_sum[3], n_ign);
-    atomicAdd(&s_sum[4], pairs);
-  }
-  // exclusive scan of s_cnt: each thread owns a contiguous run of gts
-  const int seg = (Mp + QM_BLOCK - 1) / QM_BLOCK;
-  const int lo = min(Mp, t * seg), hi = min(Mp, lo + seg);
-  int own = 0;
-  for (int g = lo; g < hi; ++g) own += s_cnt[g];
-  int v = own;
-  for (int d = 1; d < 64; d <<= 1) {
-    const int u = __shfl_up(v, d);
-    if (lane >= d) v += u;
-  }
-  if (lane == 63) s_wave[wave] = v;
-  __syncthreads();
-  int run = v - own, all = 0;
-  for (int w = 0; w < QM_BLOCK / 64; ++w) {
-    if (w < wave) run += s_wave[w];
-    all += s_wave[w];
-  }
-  for (int g = lo; g < hi; ++g) {
-    rowoff[(long)b * (Mp + 1) + g] = run;
-    run += s_cnt[g];
-  }
-  if (t == 0) {
-    rowoff[(long)b * (Mp + 1) + Mp] = all;
-    long long* st = stats + (long)b * LM_STATS;
+  for (int p = tid; p < np; p += QM_BLOCK) sums[2] += qp_valid(t.pred_rows, t.N, b, p);
+  const int all = qp_scan(t, b, s_cov, sums, s_sum);  // an ignored pred takes no further part
+  if (tid == 0) {
+    long long* st = r.stats + (long)b * LM_STATS;
     st[0] = s_sum[0];
     st[1] = s_sum[2] - s_sum[3];
     st[7] = s_sum[1];
     st[8] = s_sum[3];
     st[9] = s_sum[4];
     st[10] = all;
-    st[11] = all > max_pairs ? 1 : 0;
+    st[11] = all > t.max_pairs ? 1 : 0;
   }
 }
 
@@ -486,35 +345,24 @@ __global__ __launch_bounds__(QM_BLOCK) void lm_phase_kernel(const int* __restric
   }
 }
 
-LmLayout lm_layout(int B, int M, int N, int max_pairs) {
-  LmLayout l;
-  l.MT = (int)vkas_cdiv(M, QM_TILE);
-  l.NT = (int)vkas_cdiv(N, QM_TILE);
-  l.Mp = l.MT * QM_TILE;
-  const size_t tiles = (size_t)B * l.NT * l.Mp;
-  l.words = 0;
-  l.cand = qm_align(l.words + tiles * sizeof(unsigned long long));
-  l.cover = qm_align(l.cand + (size_t)B * max_pairs * sizeof(unsigned long long));
-  l.ignored = qm_align(l.cover + (size_t)B * l.MT * l.NT * sizeof(unsigned long long));
-  l.tpre = qm_align(l.ignored + (size_t)B * l.NT * sizeof(unsigned long long));
-  l.rowoff = qm_align(l.tpre + tiles * sizeof(int));
-  l.tile_pairs = qm_align(l.rowoff + (size_t)B * (l.Mp + 1) * sizeof(int));
-  l.bytes = qm_align(l.tile_pairs + (size_t)B * l.MT * l.NT * sizeof(int));
-  return l;
-}
+// workspace: QpLayout's, then cand (B, max_pairs) u64, cover (B, MT * NT) u64, ignored (B, NT) u64
+struct LmLayout : QpLayout {
+  size_t cand, cover, ignored;
+};
 
-int lm_check_dims(const char* what, int B, int M, int N, int max_pairs) {
-  VKAS_CHECK(B >= 0 && B <= 65535, "%s: bad B=%d (0..65535)", what, B);
-  VKAS_CHECK(M >= 1 && M <= QM_MAX && N >= 1 && N <= QM_MAX, "%s: M=%d and N=%d must lie in 1..%d", what, M, N, QM_MAX);
-  VKAS_CHECK(max_pairs >= 0, "%s: max_pairs=%d must be >= 0", what, max_pairs);
-  VKAS_CHECK((long)B * max_pairs < (1L << 31), "%s: B*max_pairs = %ld must stay below 2^31", what, (long)B * max_pairs);
-  return VKAS_OK;
+LmLayout lm_layout(int B, int M, int N, int max_pairs) {
+  LmLayout l{qp_layout(B, M, N)};
+  l.cand = l.bytes;
+  l.cover = qm_align(l.cand + (size_t)B * max_pairs * sizeof(unsigned long long));
+  l.ignored = qm_align(l.cover + l.tiles * sizeof(unsigned long long));
+  l.bytes = qm_align(l.ignored + (size_t)B * l.NT * sizeof(unsigned long long));
+  return l;
 }
 
 }  // namespace
 
 extern "C" long long vkas_line_match_workspace_bytes(int B, int M, int N, int max_pairs) {
-  if (lm_check_dims("vkas_line_match_workspace_bytes", B, M, N, max_pairs) != VKAS_OK) return -1;
+  if (qp_check_dims("vkas_line_match_workspace_bytes", B, M, N, max_pairs) != VKAS_OK) return -1;
   return (long long)lm_layout(B, M, N, max_pairs).bytes;
 }
 
@@ -522,7 +370,7 @@ extern "C" int vkas_line_match(const int* gt_rows, const int* gt_count, const un
                                const int* pred_count, int B, int M, int N, int tr_q8, int tp_q8, double cover_thr,
                                int max_pairs, void* workspace, size_t workspace_bytes, unsigned char* gt_kind, int* gt_group,
                                unsigned char* pred_kind, int* pred_group, long long* stats, int* rounds, void* stream) {
-  const int rc = lm_check_dims("vkas_line_match", B, M, N, max_pairs);
+  const int rc = qp_check_dims("vkas_line_match", B, M, N, max_pairs);
   if (rc != VKAS_OK) return rc;
   VKAS_CHECK(tr_q8 >= 1 && tr_q8 <= 256, "vkas_line_match: recall threshold tr_q8 = %d must lie in 1..256", tr_q8);
   VKAS_CHECK(tp_q8 >= 1 && tp_q8 <= 256, "vkas_line_match: precision threshold tp_q8 = %d must lie in 1..256", tp_q8);
@@ -537,42 +385,24 @@ extern "C" int vkas_line_match(const int* gt_rows, const int* gt_count, const un
              "vkas_line_match: stats must be 8-byte aligned, gt_group and pred_group 4-byte aligned");
   const LmLayout l = lm_layout(B, M, N, max_pairs);
   VKAS_CHECK(workspace_bytes >= l.bytes, "vkas_line_match: workspace of %zu bytes, %zu needed", workspace_bytes, l.bytes);
-  // the phases keep 14 bytes per pred and 3 per gt in LDS: above the default 64 KB the kernel is opted in, once
+  // the phases keep 14 bytes per pred and 3 per gt in LDS
   const size_t lds = lm_lds_bytes(M, N);
-  static size_t lds_allowed = 48 * 1024;
-  if (lds > lds_allowed) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(lm_phase_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm_lds_bytes(QM_MAX, QM_MAX));
-    if (e != hipSuccess) {
-      vkas_set_error("vkas_line_match: %zu bytes of LDS for M = %d, N = %d refused: %s", lds, M, N, hipGetErrorString(e));
-      return VKAS_E_LAUNCH;
-    }
-    lds_allowed = lm_lds_bytes(QM_MAX, QM_MAX);
-  }
-  char* ws = static_cast<char*>(workspace);
-  unsigned long long* words = reinterpret_cast<unsigned long long*>(ws + l.words);
-  unsigned long long* cand = reinterpret_cast<unsigned long long*>(ws + l.cand);
-  unsigned long long* cover = reinterpret_cast<unsigned long long*>(ws + l.cover);
-  unsigned long long* ignored = reinterpret_cast<unsigned long long*>(ws + l.ignored);
-  int* tpre = reinterpret_cast<int*>(ws + l.tpre);
-  int* rowoff = reinterpret_cast<int*>(ws + l.rowoff);
-  int* tile_pairs = reinterpret_cast<int*>(ws + l.tile_pairs);
+  if (const int e = qp_allow_lds<lm_phase_kernel>("vkas_line_match", lds, lm_lds_bytes(QM_MAX, QM_MAX))) return e;
+  const QpTables t = qp_tables(gt_rows, gt_count, pred_rows, pred_count, M, N, max_pairs, workspace, l);
+  const LmRule r{{}, gt_care, tr_q8, tp_q8, cover_thr, qp_at<unsigned long long>(workspace, l.cover), stats,
+                 qp_at<unsigned long long>(workspace, l.cand)};
+  unsigned long long* ignored = qp_at<unsigned long long>(workspace, l.ignored);
   hipStream_t s = vkas_stream(stream);
   const dim3 grid((unsigned)l.NT, (unsigned)l.MT, (unsigned)B);
-  lm_pair_kernel<false><<<grid, QM_THREADS, 0, s>>>(gt_rows, gt_count, gt_care, pred_rows, pred_count, M, N, l.Mp, l.NT, tr_q8,
-                                                    tp_q8, cover_thr, words, cover, tpre, tile_pairs, rowoff, stats, cand,
-                                                    max_pairs);
+  lm_pair_kernel<false><<<grid, QM_THREADS, 0, s>>>(t, r);
   VKAS_LAUNCH_CHECK("line_match pairs");
-  lm_scan_kernel<<<B, QM_BLOCK, 0, s>>>(gt_rows, gt_count, gt_care, pred_rows, pred_count, M, N, l.Mp, l.NT, l.MT, words, cover,
-                                        ignored, tpre, tile_pairs, rowoff, stats, max_pairs);
+  lm_scan_kernel<<<B, QM_BLOCK, 0, s>>>(t, r, ignored);
   VKAS_LAUNCH_CHECK("line_match scan");
-  lm_pair_kernel<true><<<grid, QM_THREADS, 0, s>>>(gt_rows, gt_count, gt_care, pred_rows, pred_count, M, N, l.Mp, l.NT, tr_q8,
-                                                   tp_q8, cover_thr, words, cover, tpre, tile_pairs, rowoff, stats, cand,
-                                                   max_pairs);
+  lm_pair_kernel<true><<<grid, QM_THREADS, 0, s>>>(t, r);
   VKAS_LAUNCH_CHECK("line_match fill");
   lm_phase_kernel<<<B, QM_BLOCK, lds, s>>>(gt_rows, gt_count, gt_care, pred_rows, pred_count, M, N, l.Mp, l.NT, tr_q8, tp_q8,
-                                           ignored, rowoff, cand, max_pairs, gt_kind, gt_group, pred_kind, pred_group, stats,
-                                           rounds);
+                                           ignored, t.rowoff, r.cand, max_pairs, gt_kind, gt_group, pred_kind, pred_group,
+                                           stats, rounds);
   VKAS_LAUNCH_CHECK("line_match rounds");
   return VKAS_OK;
 }

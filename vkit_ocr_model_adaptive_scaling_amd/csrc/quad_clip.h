@@ -1,5 +1,5 @@
-// What the pair passes over match rows share (quadmatch.hip: the one-to-one, ranked and self matching of character quads;
-// linematch.hip: the text-line score): the tile constants, the staging of a tile's 128 rows into LDS and the convex clip.
+// What the pair passes over match rows (quad_pairs.h) are made of: the tile constants, the staging of a tile's 128 rows into
+// LDS and the convex clip.
 //
 // The clip is Sutherland-Hodgman in binary64, every operation rounded once (qm_* helpers under contract(off): see labels.hip
 // for why __dmul_rn alone is not enough).  The two 8-vertex rings are indexed dynamically, so they live in per-thread LDS

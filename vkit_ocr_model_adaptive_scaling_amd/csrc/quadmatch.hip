@@ -1,55 +1,33 @@
 // Matching predicted character quadrilaterals to annotated ones by IoU (inferencing/evaluation.py holds the rule and the host
 // oracles quad_iou_host / match_quads_host; the rule is this project's own).  rows (B, K, 16) int32: Q4 corners (8), the
-// inclusive Q4 box (4), twice the area as int64 (2), valid, zero.  Four launches on one stream:
+// inclusive Q4 box (4), twice the area as int64 (2), valid, zero.  Four launches on one stream: the three pair passes of
+// quad_pairs.h - qm_pair_kernel<false>, qm_scan_kernel, qm_pair_kernel<true> - under the rule of the op, then its rounds:
 //
-//   qm_pair_kernel<false>  a 128-thread workgroup owns a 64 gt x 64 pred tile of one image.  The boxes and valid words of its
-//                          128 rows go to LDS; wave w box-tests gts [32w, 32w + 32) against pred = lane and appends the
-//                          overlapping valid pairs to its LDS list at the ballot's prefix count (a list is bounded by the
-//                          tile: no overflow path).  A tile without a pair - most tiles of a page - ends there.  Otherwise
-//                          the corners follow and all threads take pairs from the two lists, so the clip is balanced
-//                          whatever the tile holds.  A pair at or above iou_thr sets bit pj of the tile's 64-bit word of its
-//                          gt (LDS atomic OR: integer, order-free).  Out: the tile's words and its pair count.
-//   qm_scan_kernel         one workgroup per image: per gt the prefix of the words' popcounts over the pred tiles, then the
-//                          exclusive scan over the gts = the CSR row offsets; n_gt, n_pred, pairs, candidates, status.
-//   qm_pair_kernel<true>   the same tile body with the stored words in place of the box test: only candidates are clipped
-//                          again (same code, same bits), each stored at  row offset + tile prefix + popcount of the lower
-//                          bits: no slot atomics, pred ascending within a gt.  A tile whose words are all zero ends on
-//                          them, and an image with status set is skipped.
-//   qm_match_kernel        one workgroup per image, mutual-best rounds on integer atomicMax / atomicMin in LDS.
+//   QmMatchRule  (vkas_quad_match)  a pair at or above iou_thr is a candidate; its slot holds the pred and the iou bits.
+//                qm_match_kernel: one workgroup per image, mutual-best rounds on integer atomicMax / atomicMin in LDS.
+//   QmSelfRule   (vkas_quad_nms; inferencing/nms.py holds the rule and the oracle nms_quads_host)  one table against itself:
+//                the row that is judged in the gt's place, the row that may suppress it in the pred's.  A row takes part iff
+//                it is valid and its prob is finite, and a pair only where the pred outranks the gt (the higher float32
+//                prob, then the lower index): the diagonal and one of (i, j), (j, i) drop out before the clip.  The prob
+//                bits travel in the row's zero word in LDS; a slot holds the pred alone.  qn_rounds_kernel: one workgroup
+//                per image.
+//   QrRule       (vkas_quad_match_ranked; inferencing/ranking.py holds the rule and the oracles)  T IoU thresholds with
+//                don't-care annotations; the passes run at iou_thrs[0].  A pred takes part iff it is valid and its prob is
+//                finite; the care flag rides in the gt row's zero word.  In the counting pass a pair with a don't-care gt is
+//                clipped for the coverage test alone and sets the pred's bit of the tile's cover word instead of a candidate
+//                bit, and a care pair is counted at every threshold it reaches; the fill never meets a don't-care gt, whose
+//                words are zero.  qr_rounds_kernel: one workgroup per (image, threshold), all of them walking the one
+//                candidate list.
 //
-// The suppression of duplicate quads (vkas_quad_nms; inferencing/nms.py holds the rule and the oracle nms_quads_host) runs
-// the same three passes on one table against itself - qm_pair_kernel<.., QM_SELF> and qm_scan_kernel<QM_SELF>: the row that is
-// judged in the gt's place, the row that may suppress it in the pred's, pairs only where the pred outranks the gt - and
-// then qn_rounds_kernel, one workgroup per image.  qm_rows_kernel (vkas_quad_rows) is inferencing.match_rows on the device.
-//
-// The ranked matching at T IoU thresholds with don't-care annotations (vkas_quad_match_ranked; inferencing/ranking.py holds
-// the rule and the oracles) runs the three passes once more - qm_pair_kernel<.., QM_RANKED> and qm_scan_kernel<QM_RANKED>
-// with thr = iou_thrs[0]: a pred without a finite prob loses its valid word as it is staged, the care flag rides in the
-// gt row's zero word, a pair with a don't-care gt is clipped in the counting pass only and sets the pred's bit of the
-// tile's cover word instead of a candidate bit, and the tile counts its candidates at every threshold - and then
-// qr_rounds_kernel, one workgroup per (image, threshold), all of them walking the one candidate list.
-//
-// The clip is Sutherland-Hodgman in binary64, every operation rounded once (qm_* helpers under contract(off): see labels.hip
-// for why __dmul_rn alone is not enough).  The two 8-vertex rings are indexed dynamically, so they live in per-thread LDS
-// slots, [ring][vertex][coordinate][thread]: consecutive lanes hit consecutive 8-byte banks, and nothing goes to scratch.
-// No float atomics, no allocation, no synchronisation: capture-safe and bit-identical from run to run.  Table reads are
-// bounded by the tables' K rows (a row beyond the clamped count is dropped after its load), ring stores by RING_MAX, candidate stores by max_pairs, tile stores by the padded tile grid
-// the workspace is sized for: no table content makes a kernel touch memory outside its buffers.
-// The tile constants, the row staging and the clip live in quad_clip.h, which linematch.hip shares.
-#include "quad_clip.h"
+// qm_rows_kernel (vkas_quad_rows) is inferencing.match_rows on the device.
+#include "quad_pairs.h"
 
 namespace {
 
 constexpr int QM_STATS = 6;                // tp, n_gt, n_pred, pairs, candidates, status
 constexpr int QR_STATS = 8;                // ranked: tp, fp, ignored, n_gt, n_pred, pairs, candidates, status
 constexpr int QR_TMAX = 16;                // ranked: IoU thresholds per call
-constexpr int QM_MATCH = 0, QM_SELF = 1, QM_RANKED = 2;  // what the three shared passes serve
 constexpr unsigned long long QM_TAKEN = ~0ull;
-
-__device__ __forceinline__ double qm_iou(const int4* g, const int4* p, double* ring) {
-  double inter2;
-  return qm_inter2_iou(g, p, ring, &inter2);
-}
 
 // What only the ranked matching passes to the shared passes and to its rounds.
 struct QrArgs {
@@ -61,301 +39,193 @@ struct QrArgs {
   double thr[QR_TMAX];           // ascending; thr[0] is the threshold of the three passes
 };
 
-// workspace: words (B, NT, Mp) u64, cand_iou (B, max_pairs) u64, tpre (B, NT, Mp) int, rowoff (B, Mp + 1) int,
-// tile_pairs (B, MT * NT) int, cand_pred (B, max_pairs) int
-struct QmLayout {
-  size_t words, cand_iou, tpre, rowoff, tile_pairs, cand_pred, bytes;
-  int MT, NT, Mp;
-};
+// ---- the rules (quad_pairs.h says what each member is for) ---------------------------------------------------------------
 
-// SELF: one table against itself for the suppression (gt = the row that is judged, pred = the row that may suppress it).  A
-// row takes part iff it is valid and its prob is finite, and a pair only where the pred outranks the gt (the higher float32
-// prob, then the lower index): the diagonal and one of (i, j), (j, i) drop out before the clip.  The prob bits travel in the
-// row's zero word in LDS.
-// RANKED: a pred takes part iff it is valid and its prob is finite; the zero word of a gt row carries its care flag.  In the
-// counting pass a pair with a don't-care gt is clipped for the coverage test alone (inter2 >= cover_thr * area2_p, the
-// product rounded once) and a care pair is counted at every threshold it reaches; the fill never meets a don't-care gt,
-// whose words are zero.
-template <bool FILL, int KIND>
-__global__ __launch_bounds__(QM_THREADS) void qm_pair_kernel(const int* __restrict__ gt_rows, const int* __restrict__ gt_count,
-                                                              const int* __restrict__ pred_rows,
-                                                              const int* __restrict__ pred_count, int M, int N, int Mp,
-                                                              int NT, double thr, unsigned long long* __restrict__ words,
-                                                              int* __restrict__ tpre, int* __restrict__ tile_pairs,
-                                                              const int* __restrict__ rowoff,
-                                                              const long long* __restrict__ stats, int* __restrict__ cand_pred,
-                                                              unsigned long long* __restrict__ cand_iou, int max_pairs,
-                                                              const float* __restrict__ probs, const QrArgs x) {
-  constexpr bool SELF = KIND == QM_SELF, RANKED = KIND == QM_RANKED;
-  __shared__ int4 s_rows[2 * QM_TILE * 4];
-  __shared__ unsigned long long s_word[QM_TILE];
-  __shared__ unsigned short s_list[QM_WAVES * QM_LIST];
-  __shared__ int s_cnt[QM_WAVES];
-  __shared__ double s_ring[2 * QM_RING * 2 * QM_THREADS];
-  __shared__ unsigned long long s_cover;  // RANKED counting pass only, as the next two
-  __shared__ int s_dc[QM_WAVES];
-  __shared__ int s_ct[QR_TMAX];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tn = blockIdx.x, tm = blockIdx.y, b = blockIdx.z;
-  const int g0 = tm * QM_TILE, p0 = tn * QM_TILE;
-  const long word_at = ((long)b * NT + tn) * Mp + g0;
-  // Most tiles of a page end early: the status, the counts, the words and (below) the rows are read at addresses that depend
-  // on no other load, so such a workgroup lives one load's latency.  Every early return is taken by the whole workgroup.
-  const long long status = FILL ? stats[RANKED ? (long)b * x.T * QR_STATS + 7 : (long)b * QM_STATS + 5] : 0;
-  const int ng = qm_clamp(gt_count[b], M), np = qm_clamp(pred_count[b], N);
-  if (FILL && status != 0) return;  // nothing of this image is stored
-  unsigned long long word = 0ull;
-  if (FILL && tid < QM_TILE) word = words[word_at + tid];
-  // a part of the 128 rows of the tile: 0, 1 = the corners, 2 = the box, 3 = area and valid (qm_stage_half); what rides in
-  // the zero word of part 3 is put there as the row is staged
-  const auto fix = [&](int4& v, bool is_gt, int at, int part) {
-    if (SELF && part == 3) {  // M == N: one table
-      const unsigned pb = __float_as_uint(probs[(long)b * M + at]);
-      v.z = (v.z != 0 && qm_finite_bits(pb)) ? 1 : 0;
-      v.w = (int)pb;
-    }
-    if (RANKED && part == 3) {
-      if (is_gt) {
-        v.w = x.gt_care ? (x.gt_care[(long)b * M + at] != 0 ? 1 : 0) : 1;
-      } else {
-        const unsigned pb = __float_as_uint(probs[(long)b * N + at]);
-        v.z = (v.z != 0 && qm_finite_bits(pb)) ? 1 : 0;
-        v.w = (int)pb;
-      }
-    }
-  };
-  const auto stage = [&](int half) { qm_stage_half(s_rows, gt_rows, pred_rows, b, M, N, g0, p0, ng, np, half, tid, fix); };
-  if (tid < QM_TILE) s_word[tid] = word;
-  if (RANKED && !FILL) {
-    if (tid == 0) s_cover = 0ull;
-    if (tid < QR_TMAX) s_ct[tid] = 0;
-  }
-  if (FILL) {  // most tiles of a page hold no candidate: they end here, on 512 bytes
-    __syncthreads();
-    if (__ballot(s_word[lane] != 0ull) == 0ull) return;
-  }
-  stage(1);  // the box test needs boxes and valid only; a tile without a pair ends on them
-  __syncthreads();
-
-  const int4 pbox = s_rows[(QM_TILE + lane) * 4 + 2];
-  const bool pvalid = s_rows[(QM_TILE + lane) * 4 + 3].z != 0;
-  const float pprob = __int_as_float(s_rows[(QM_TILE + lane) * 4 + 3].w);  // SELF only
-  int cnt = 0, dcnt = 0;
-  for (int s = 0; s < QM_TILE / QM_WAVES; ++s) {
-    const int gi = wave * (QM_TILE / QM_WAVES) + s;
-    bool hit;
-    if (FILL) {
-      hit = (s_word[gi] >> lane) & 1ull;
-    } else {
-      const int4 gbox = s_rows[gi * 4 + 2];
-      hit = pvalid && s_rows[gi * 4 + 3].z != 0 && gbox.x <= pbox.z && pbox.x <= gbox.z && gbox.y <= pbox.w &&
-            pbox.y <= gbox.w;
-      if (SELF) {
-        const float gprob = __int_as_float(s_rows[gi * 4 + 3].w);
-        hit = hit && (pprob > gprob || (pprob == gprob && p0 + lane < g0 + gi));
-      }
-    }
-    const unsigned long long bits = __ballot(hit);
-    if (hit) s_list[wave * QM_LIST + cnt + __popcll(bits & ((1ull << lane) - 1ull))] = (unsigned short)(gi * QM_TILE + lane);
-    cnt += __popcll(bits);  // <= 32 * 64 = QM_LIST
-    if (RANKED && !FILL && s_rows[gi * 4 + 3].w == 0) dcnt += __popcll(bits);  // gi is the wave's: uniform
-  }
-  if (lane == 0) s_cnt[wave] = cnt;
-  if (RANKED && !FILL && lane == 0) s_dc[wave] = dcnt;
-  __syncthreads();
-  const int c0 = s_cnt[0], total = c0 + s_cnt[1];
-  static_assert(QM_WAVES == 2, "the two lists are read as one");
-  if (total == 0) {  // the whole workgroup
-    if (!FILL) {
-      if (tid < QM_TILE) words[word_at + tid] = 0ull;
-      if (tid == 0) tile_pairs[((long)b * gridDim.y + tm) * NT + tn] = 0;
-      if (RANKED) {
-        const long tile = ((long)b * gridDim.y + tm) * NT + tn;
-        if (tid == 0) x.cover[tile] = 0ull;
-        if (tid < 1 + x.T) x.tile_info[tile * (1 + x.T) + tid] = 0;
-      }
-    }
-    return;
-  }
-  stage(0);
-  __syncthreads();
-  for (int e = tid; e < total; e += QM_THREADS) {
-    const int q = e < c0 ? s_list[e] : s_list[QM_LIST + e - c0];
-    const int gi = q >> 6, pj = q & 63;
-    double inter2;
-    const double iou = qm_inter2_iou(s_rows + gi * 4, s_rows + (QM_TILE + pj) * 4, s_ring + tid, &inter2);
-    if (RANKED && !FILL) {
-      if (s_rows[gi * 4 + 3].w == 0) {  // a don't-care gt: the coverage test, never a candidate
-        const int4 pa = s_rows[(QM_TILE + pj) * 4 + 3];
-        const double ap = (double)(long)(((unsigned long long)(unsigned)pa.y << 32) | (unsigned)pa.x);
-        if (inter2 >= qm_mul(x.cover_thr, ap)) atomicOr(&s_cover, 1ull << pj);
-        continue;
-      }
-      for (int t = 0; t < x.T; ++t)
-        if (iou >= x.thr[t]) atomicAdd(&s_ct[t], 1);
-    }
-    if (!(iou >= thr)) continue;
-    if (FILL) {
-      const int g = g0 + gi;
-      const long slot = (long)rowoff[(long)b * (Mp + 1) + g] + tpre[word_at + gi] +
-                        __popcll(s_word[gi] & ((1ull << pj) - 1ull));
-      if (slot >= 0 && slot < max_pairs) {
-        cand_pred[(long)b * max_pairs + slot] = p0 + pj;
-        if (!SELF) cand_iou[(long)b * max_pairs + slot] = (unsigned long long)__double_as_longlong(iou);
-      }
-    } else {
-      atomicOr(&s_word[gi], 1ull << pj);
-    }
-  }
-  if (!FILL) {
-    __syncthreads();
-    if (tid < QM_TILE) words[word_at + tid] = s_word[tid];
-    if (RANKED) {  // pairs counts the care pairs alone
-      const long tile = ((long)b * gridDim.y + tm) * NT + tn;
-      const int dc = s_dc[0] + s_dc[1];
-      if (tid == 0) {
-        tile_pairs[tile] = total - dc;
-        x.cover[tile] = s_cover;
-        x.tile_info[tile * (1 + x.T)] = dc;
-      }
-      if (tid < x.T) x.tile_info[tile * (1 + x.T) + 1 + tid] = s_ct[tid];
-    } else if (tid == 0) {
-      tile_pairs[((long)b * gridDim.y + tm) * NT + tn] = total;
-    }
-  }
+__device__ __forceinline__ unsigned long long qm_bits(double v) { return (unsigned long long)__double_as_longlong(v); }
+// a row that takes part in the self and the ranked matching: valid, and its prob finite
+__device__ __forceinline__ bool qm_ranked_part(const int* rows, const float* probs, int K, int b, int i) {
+  return qp_valid(rows, K, b, i) && qm_finite_bits(__float_as_uint(probs[(long)b * K + i]));
 }
 
-// SELF (the suppression): stats = kept (written by the rounds), n = the clamped count, n_valid = the rows that take part.
-// RANKED: stats (B, T, 8) words 3..7 of every threshold = n_gt (care gts), n_pred, pairs (care), the candidates at that
-// threshold, status; covered (B, N) = the OR of the tiles' cover words down the gt tiles; dc_stats (B, 3) = n_dc, dc_pairs,
-// n_covered.  Words 0..2 are the rounds'.
-template <int KIND>
-__global__ __launch_bounds__(QM_BLOCK) void qm_scan_kernel(const int* __restrict__ gt_rows, const int* __restrict__ gt_count,
-                                                            const int* __restrict__ pred_rows,
-                                                            const int* __restrict__ pred_count, int M, int N, int Mp, int NT,
-                                                            int MT, const unsigned long long* __restrict__ words,
-                                                            int* __restrict__ tpre, const int* __restrict__ tile_pairs,
-                                                            int* __restrict__ rowoff, long long* __restrict__ stats,
-                                                            int max_pairs, const float* __restrict__ probs, const QrArgs x,
-                                                            unsigned char* __restrict__ covered,
-                                                            long long* __restrict__ dc_stats) {
-  constexpr bool SELF = KIND == QM_SELF, RANKED = KIND == QM_RANKED;
-  __shared__ int s_cnt[QM_MAX];
-  __shared__ int s_wave[QM_BLOCK / 64];
-  __shared__ int s_sum[3];
-  __shared__ int s_more[3 + QR_TMAX];                  // RANKED only, as the next: n_dc, dc_pairs, n_covered, candidates at t
-  __shared__ unsigned long long s_cov[QM_MAX / QM_TILE];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, b = blockIdx.x;
-  const int ng = qm_clamp(gt_count[b], M), np = qm_clamp(pred_count[b], N);
-  if (t < 3) s_sum[t] = 0;
-  if (RANKED) {
-    if (t < 3 + QR_TMAX) s_more[t] = 0;
-    if (t < NT) {  // NT <= QM_MAX / QM_TILE
-      unsigned long long w = 0ull;
-      for (int tm = 0; tm < MT; ++tm) w |= x.cover[((long)b * MT + tm) * NT + t];
-      s_cov[t] = w;
+// stats (B, 6): words 1..5 are the scan's - n_gt, n_pred (the valid rows within the counts), pairs, candidates, status
+struct QmMatchRule : QpRule {
+  double thr;
+  long long* stats;
+  int* cand_pred;               // (B, max_pairs)
+  unsigned long long* cand_iou; // (B, max_pairs)
+  __device__ __forceinline__ long long status(int b) const { return stats[(long)b * QM_STATS + 5]; }
+  template <bool FILL>
+  __device__ __forceinline__ bool pair(Tile&, const int4&, const int4&, int, double iou, double, unsigned long long& val) const {
+    val = qm_bits(iou);
+    return iou >= thr;
+  }
+  __device__ __forceinline__ void store(long at, int pred, unsigned long long val) const {
+    cand_pred[at] = pred;
+    cand_iou[at] = val;
+  }
+  __device__ __forceinline__ bool gt_part(const QpTables& t, int b, int g) const { return qp_valid(t.gt_rows, t.M, b, g); }
+  __device__ __forceinline__ bool pred_part(const QpTables& t, int b, int p) const { return qp_valid(t.pred_rows, t.N, b, p); }
+};
+
+// stats (B, 6): kept (written by the rounds), n = the clamped count, n_valid = the rows that take part, pairs, candidates,
+// status.  M == N: one table, one count.
+struct QmSelfRule : QpRule {
+  double thr;
+  long long* stats;
+  const float* probs;  // (B, K)
+  int* cand;           // (B, max_pairs)
+  __device__ __forceinline__ void fix(int4& v, bool, int b, int M, int, int at, int part) const {
+    if (part == 3) qp_fix_prob(v, probs, (long)b * M + at);
+  }
+  __device__ __forceinline__ bool admit(const int4& g3, const int4& p3, int g, int p) const {
+    const float gprob = __int_as_float(g3.w), pprob = __int_as_float(p3.w);
+    return pprob > gprob || (pprob == gprob && p < g);
+  }
+  __device__ __forceinline__ long long status(int b) const { return stats[(long)b * QM_STATS + 5]; }
+  template <bool FILL>
+  __device__ __forceinline__ bool pair(Tile&, const int4&, const int4&, int, double iou, double, unsigned long long&) const {
+    return iou >= thr;
+  }
+  __device__ __forceinline__ void store(long at, int pred, unsigned long long) const { cand[at] = pred; }
+  __device__ __forceinline__ bool gt_part(const QpTables&, int, int) const { return true; }
+  __device__ __forceinline__ bool pred_part(const QpTables& t, int b, int p) const {
+    return qm_ranked_part(t.pred_rows, probs, t.N, b, p);
+  }
+};
+
+struct QrRule : QpRule {
+  QrArgs x;
+  const float* probs;  // (B, N)
+  long long* stats;    // (B, T, 8)
+  int* cand_pred;
+  unsigned long long* cand_iou;
+  struct Tile {
+    unsigned long long cover;
+    int dc;            // the tile's pairs with a don't-care gt
+    int ct[QR_TMAX];   // its candidates at each threshold
+  };
+  __device__ __forceinline__ void begin(Tile& s, int tid) const {
+    if (tid == 0) {
+      s.cover = 0ull;
+      s.dc = 0;
     }
-    __syncthreads();
-    int n_dc = 0, n_cov = 0;
-    for (int g = t; g < ng; g += QM_BLOCK)
-      n_dc += gt_rows[((long)b * M + g) * 16 + 14] != 0 && x.gt_care && x.gt_care[(long)b * M + g] == 0;
-    for (int p = t; p < N; p += QM_BLOCK) {
-      const int c = (int)((s_cov[p >> 6] >> (p & 63)) & 1ull);
-      covered[(long)b * N + p] = (unsigned char)c;
-      n_cov += c;
+    if (tid < QR_TMAX) s.ct[tid] = 0;
+  }
+  __device__ __forceinline__ void fix(int4& v, bool is_gt, int b, int M, int N, int at, int part) const {
+    if (part != 3) return;
+    if (is_gt) qp_fix_care(v, x.gt_care, (long)b * M + at);
+    else qp_fix_prob(v, probs, (long)b * N + at);
+  }
+  __device__ __forceinline__ long long status(int b) const { return stats[(long)b * x.T * QR_STATS + 7]; }
+  template <bool FILL>
+  __device__ __forceinline__ bool pair(Tile& s, const int4& g3, const int4& p3, int pj, double iou, double inter2,
+                                       unsigned long long& val) const {
+    if (!FILL) {
+      if (g3.w == 0) {  // a don't-care gt: the coverage test, never a candidate
+        atomicAdd(&s.dc, 1);
+        if (qp_covers(x.cover_thr, inter2, p3)) atomicOr(&s.cover, 1ull << pj);
+        return false;
+      }
+      for (int t = 0; t < x.T; ++t)
+        if (iou >= x.thr[t]) atomicAdd(&s.ct[t], 1);
     }
-    n_dc = qm_wave_sum_i(n_dc);
-    n_cov = qm_wave_sum_i(n_cov);
-    if (lane == 0) {
-      atomicAdd(&s_more[0], n_dc);
-      atomicAdd(&s_more[2], n_cov);
+    val = qm_bits(iou);
+    return iou >= x.thr[0];
+  }
+  __device__ __forceinline__ void store(long at, int pred, unsigned long long val) const {
+    cand_pred[at] = pred;
+    cand_iou[at] = val;
+  }
+  __device__ __forceinline__ int apart(const Tile& s) const { return s.dc; }  // pairs counts the care pairs alone
+  __device__ __forceinline__ void tile_out(const Tile& s, long tile, int tid) const {
+    if (tid == 0) {
+      x.cover[tile] = s.cover;
+      x.tile_info[tile * (1 + x.T)] = s.dc;
     }
-    for (int k = 0; k < 1 + x.T; ++k) {  // the tiles' don't-care pairs (k = 0) and candidates at threshold k - 1
-      int v = 0;
-      for (int i = t; i < MT * NT; i += QM_BLOCK) v += x.tile_info[((long)b * MT * NT + i) * (1 + x.T) + k];
-      v = qm_wave_sum_i(v);
-      if (lane == 0) atomicAdd(&s_more[k == 0 ? 1 : 2 + k], v);
-    }
+    if (tid < x.T) x.tile_info[tile * (1 + x.T) + 1 + tid] = s.ct[tid];
   }
-  for (int g = t; g < Mp; g += QM_BLOCK) {  // Mp <= QM_MAX
-    int run = 0;
-#pragma unroll 8
-    for (int tn = 0; tn < NT; ++tn) {
-      const long at = ((long)b * NT + tn) * Mp + g;
-      tpre[at] = run;
-      run += __popcll(words[at]);
-    }
-    s_cnt[g] = run;
-  }
-  int n_gt = 0, n_pred = 0, pairs = 0;
-  if (SELF) {
-    n_gt = t == 0 ? ng : 0;
-    for (int g = t; g < ng; g += QM_BLOCK)
-      n_pred += gt_rows[((long)b * M + g) * 16 + 14] != 0 && qm_finite_bits(__float_as_uint(probs[(long)b * M + g]));
-  } else if (RANKED) {
-    for (int g = t; g < ng; g += QM_BLOCK)
-      n_gt += gt_rows[((long)b * M + g) * 16 + 14] != 0 && (!x.gt_care || x.gt_care[(long)b * M + g] != 0);
-    for (int p = t; p < np; p += QM_BLOCK)
-      n_pred += pred_rows[((long)b * N + p) * 16 + 14] != 0 && qm_finite_bits(__float_as_uint(probs[(long)b * N + p]));
-  } else {
-    for (int g = t; g < ng; g += QM_BLOCK) n_gt += gt_rows[((long)b * M + g) * 16 + 14] != 0;
-    for (int p = t; p < np; p += QM_BLOCK) n_pred += pred_rows[((long)b * N + p) * 16 + 14] != 0;
-  }
-  for (int i = t; i < MT * NT; i += QM_BLOCK) pairs += tile_pairs[(long)b * MT * NT + i];  // <= M * N <= 2^26
-  __syncthreads();
-  n_gt = qm_wave_sum_i(n_gt);
-  n_pred = qm_wave_sum_i(n_pred);
-  pairs = qm_wave_sum_i(pairs);
-  if (lane == 0) {
-    atomicAdd(&s_sum[0], n_gt);
-    atomicAdd(&s_sum[1], n_pred);
-    atomicAdd(&s_sum[2], pairs);
-  }
-  // exclusive scan of s_cnt: each thread owns a contiguous run of gts
-  const int seg = (Mp + QM_BLOCK - 1) / QM_BLOCK;
-  const int lo = min(Mp, t * seg), hi = min(Mp, lo + seg);
-  int own = 0;
-  for (int g = lo; g < hi; ++g) own += s_cnt[g];
-  int v = own;
-  for (int d = 1; d < 64; d <<= 1) {
-    const int u = __shfl_up(v, d);
-    if (lane >= d) v += u;
-  }
-  if (lane == 63) s_wave[wave] = v;
-  __syncthreads();
-  int run = v - own, all = 0;
-  for (int w = 0; w < QM_BLOCK / 64; ++w) {
-    if (w < wave) run += s_wave[w];
-    all += s_wave[w];
-  }
-  for (int g = lo; g < hi; ++g) {
-    rowoff[(long)b * (Mp + 1) + g] = run;
-    run += s_cnt[g];
-  }
-  if (RANKED) {
-    if (t == 0) {
-      rowoff[(long)b * (Mp + 1) + Mp] = all;
-      for (int k = 0; k < 3; ++k) dc_stats[(long)b * 3 + k] = s_more[k];
-    }
-    if (t < x.T) {
-      long long* st = stats + ((long)b * x.T + t) * QR_STATS;
-      st[3] = s_sum[0];
-      st[4] = s_sum[1];
-      st[5] = s_sum[2];
-      st[6] = s_more[3 + t];
-      st[7] = all > max_pairs ? 1 : 0;
-    }
-    return;
-  }
-  if (t == 0) {
-    rowoff[(long)b * (Mp + 1) + Mp] = all;
-    long long* st = stats + (long)b * QM_STATS;
+};
+
+template <bool FILL, class Rule>
+__global__ __launch_bounds__(QM_THREADS) void qm_pair_kernel(const QpTables t, const Rule r) {
+  qp_tile<FILL>(t, r);
+}
+
+// the one-to-one and the self matching
+template <class Rule>
+__global__ __launch_bounds__(QM_BLOCK) void qm_scan_kernel(const QpTables t, const Rule r) {
+  __shared__ int s_sum[3];  // n_gt, n_pred, pairs
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const int ng = qm_clamp(t.gt_count[b], t.M), np = qm_clamp(t.pred_count[b], t.N);
+  if (tid < 3) s_sum[tid] = 0;
+  int sums[2] = {0, 0};
+  for (int g = tid; g < ng; g += QM_BLOCK) sums[0] += r.gt_part(t, b, g);
+  for (int p = tid; p < np; p += QM_BLOCK) sums[1] += r.pred_part(t, b, p);
+  const int all = qp_scan(t, b, nullptr, sums, s_sum);
+  if (tid == 0) {
+    long long* st = r.stats + (long)b * QM_STATS;
     st[0] = 0;
     st[1] = s_sum[0];
     st[2] = s_sum[1];
     st[3] = s_sum[2];
     st[4] = all;
-    st[5] = all > max_pairs ? 1 : 0;
+    st[5] = all > t.max_pairs ? 1 : 0;
+  }
+}
+
+// The ranked matching: stats (B, T, 8) words 3..7 of every threshold = n_gt (care gts), n_pred, pairs (care), the candidates
+// at that threshold, status; covered (B, N) = the OR of the tiles' cover words down the gt tiles; dc_stats (B, 3) = n_dc,
+// dc_pairs, n_covered.  Words 0..2 are the rounds'.
+__global__ __launch_bounds__(QM_BLOCK) void qm_scan_kernel(const QpTables t, const QrRule r, unsigned char* __restrict__ covered,
+                                                            long long* __restrict__ dc_stats) {
+  __shared__ int s_sum[3];              // n_gt, n_pred, pairs
+  __shared__ int s_more[3 + QR_TMAX];   // n_dc, dc_pairs, n_covered, candidates at t
+  __shared__ unsigned long long s_cov[QM_MAX / QM_TILE];
+  const QrArgs& x = r.x;
+  const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.x, M = t.M, N = t.N, tiles = t.MT * t.NT;
+  const int ng = qm_clamp(t.gt_count[b], M), np = qm_clamp(t.pred_count[b], N);
+  if (tid < 3) s_sum[tid] = 0;
+  if (tid < 3 + QR_TMAX) s_more[tid] = 0;
+  if (tid < t.NT) {  // NT <= QM_MAX / QM_TILE
+    unsigned long long w = 0ull;
+    for (int tm = 0; tm < t.MT; ++tm) w |= x.cover[((long)b * t.MT + tm) * t.NT + tid];
+    s_cov[tid] = w;
+  }
+  __syncthreads();
+  int sums[2] = {0, 0}, n_dc = 0, n_cov = 0;
+  for (int g = tid; g < ng; g += QM_BLOCK) {
+    const bool part = qp_valid(t.gt_rows, M, b, g), care = !x.gt_care || x.gt_care[(long)b * M + g] != 0;
+    sums[0] += part && care;
+    n_dc += part && !care;
+  }
+  for (int p = tid; p < np; p += QM_BLOCK) sums[1] += qm_ranked_part(t.pred_rows, r.probs, N, b, p);
+  for (int p = tid; p < N; p += QM_BLOCK) {
+    const int c = (int)((s_cov[p >> 6] >> (p & 63)) & 1ull);
+    covered[(long)b * N + p] = (unsigned char)c;
+    n_cov += c;
+  }
+  n_dc = qm_wave_sum_i(n_dc);
+  n_cov = qm_wave_sum_i(n_cov);
+  if (lane == 0) {
+    atomicAdd(&s_more[0], n_dc);
+    atomicAdd(&s_more[2], n_cov);
+  }
+  for (int k = 0; k < 1 + x.T; ++k) {  // the tiles' don't-care pairs (k = 0) and candidates at threshold k - 1
+    int v = 0;
+    for (int i = tid; i < tiles; i += QM_BLOCK) v += x.tile_info[((long)b * tiles + i) * (1 + x.T) + k];
+    v = qm_wave_sum_i(v);
+    if (lane == 0) atomicAdd(&s_more[k == 0 ? 1 : 2 + k], v);
+  }
+  const int all = qp_scan(t, b, nullptr, sums, s_sum);
+  if (tid == 0)
+    for (int k = 0; k < 3; ++k) dc_stats[(long)b * 3 + k] = s_more[k];
+  if (tid < x.T) {
+    long long* st = r.stats + ((long)b * x.T + tid) * QR_STATS;
+    st[3] = s_sum[0];
+    st[4] = s_sum[1];
+    st[5] = s_sum[2];
+    st[6] = s_more[3 + tid];
+    st[7] = all > t.max_pairs ? 1 : 0;
   }
 }
 
@@ -762,34 +632,23 @@ __global__ __launch_bounds__(256) void qm_rows_kernel(const double* __restrict__
 }
 
 
+// workspace: QpLayout's, then cand_iou (B, max_pairs) u64 (not for the self matching) and cand_pred (B, max_pairs) int
+struct QmLayout : QpLayout {
+  size_t cand_iou, cand_pred;
+};
+
 QmLayout qm_layout(int B, int M, int N, int max_pairs, bool with_iou = true) {
-  QmLayout l;
-  l.MT = (int)vkas_cdiv(M, QM_TILE);
-  l.NT = (int)vkas_cdiv(N, QM_TILE);
-  l.Mp = l.MT * QM_TILE;
-  const size_t tiles = (size_t)B * l.NT * l.Mp;
-  l.words = 0;
-  l.cand_iou = qm_align(l.words + tiles * sizeof(unsigned long long));
-  l.tpre = qm_align(l.cand_iou + (with_iou ? (size_t)B * max_pairs * sizeof(unsigned long long) : 0));
-  l.rowoff = qm_align(l.tpre + tiles * sizeof(int));
-  l.tile_pairs = qm_align(l.rowoff + (size_t)B * (l.Mp + 1) * sizeof(int));
-  l.cand_pred = qm_align(l.tile_pairs + (size_t)B * l.MT * l.NT * sizeof(int));
+  QmLayout l{qp_layout(B, M, N)};
+  l.cand_iou = l.bytes;
+  l.cand_pred = qm_align(l.cand_iou + (with_iou ? (size_t)B * max_pairs * sizeof(unsigned long long) : 0));
   l.bytes = qm_align(l.cand_pred + (size_t)B * max_pairs * sizeof(int));
   return l;
-}
-
-int qm_check_dims(const char* what, int B, int M, int N, int max_pairs) {
-  VKAS_CHECK(B >= 0 && B <= 65535, "%s: bad B=%d (0..65535)", what, B);
-  VKAS_CHECK(M >= 1 && M <= QM_MAX && N >= 1 && N <= QM_MAX, "%s: M=%d and N=%d must lie in 1..%d", what, M, N, QM_MAX);
-  VKAS_CHECK(max_pairs >= 0, "%s: max_pairs=%d must be >= 0", what, max_pairs);
-  VKAS_CHECK((long)B * max_pairs < (1L << 31), "%s: B*max_pairs = %ld must stay below 2^31", what, (long)B * max_pairs);
-  return VKAS_OK;
 }
 
 }  // namespace
 
 extern "C" long long vkas_quad_match_workspace_bytes(int B, int M, int N, int max_pairs) {
-  if (qm_check_dims("vkas_quad_match_workspace_bytes", B, M, N, max_pairs) != VKAS_OK) return -1;
+  if (qp_check_dims("vkas_quad_match_workspace_bytes", B, M, N, max_pairs) != VKAS_OK) return -1;
   return (long long)qm_layout(B, M, N, max_pairs).bytes;
 }
 
@@ -797,7 +656,7 @@ extern "C" int vkas_quad_match(const int* gt_rows, const int* gt_count, const in
                                int M, int N, double iou_thr, int max_pairs, void* workspace, size_t workspace_bytes,
                                int* gt_match, int* pred_match, double* gt_iou, long long* stats, int* rounds,
                                void* stream) {
-  const int rc = qm_check_dims("vkas_quad_match", B, M, N, max_pairs);
+  const int rc = qp_check_dims("vkas_quad_match", B, M, N, max_pairs);
   if (rc != VKAS_OK) return rc;
   VKAS_CHECK(iou_thr > 0.0 && iou_thr <= 1.0, "vkas_quad_match: iou_thr = %g must lie in (0, 1]", iou_thr);
   if (B == 0) return VKAS_OK;
@@ -809,41 +668,22 @@ extern "C" int vkas_quad_match(const int* gt_rows, const int* gt_count, const in
              "vkas_quad_match: gt_iou and stats must be 8-byte aligned");
   const QmLayout l = qm_layout(B, M, N, max_pairs);
   VKAS_CHECK(workspace_bytes >= l.bytes, "vkas_quad_match: workspace of %zu bytes, %zu needed", workspace_bytes, l.bytes);
-  // the matching pass keeps 12 bytes per pred in LDS: above the default 64 KB the kernel is opted in, once
-  const size_t lds = (size_t)N * (sizeof(unsigned long long) + sizeof(int));
-  static size_t lds_allowed = 48 * 1024;
-  if (lds > lds_allowed) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(qm_match_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)((size_t)QM_MAX * (sizeof(unsigned long long) + sizeof(int))));
-    if (e != hipSuccess) {
-      vkas_set_error("vkas_quad_match: %zu bytes of LDS for N = %d refused: %s", lds, N, hipGetErrorString(e));
-      return VKAS_E_LAUNCH;
-    }
-    lds_allowed = (size_t)QM_MAX * (sizeof(unsigned long long) + sizeof(int));
-  }
-  char* ws = static_cast<char*>(workspace);
-  unsigned long long* words = reinterpret_cast<unsigned long long*>(ws + l.words);
-  unsigned long long* cand_iou = reinterpret_cast<unsigned long long*>(ws + l.cand_iou);
-  int* tpre = reinterpret_cast<int*>(ws + l.tpre);
-  int* rowoff = reinterpret_cast<int*>(ws + l.rowoff);
-  int* tile_pairs = reinterpret_cast<int*>(ws + l.tile_pairs);
-  int* cand_pred = reinterpret_cast<int*>(ws + l.cand_pred);
+  // the matching pass keeps 12 bytes per pred in LDS
+  constexpr size_t per_pred = sizeof(unsigned long long) + sizeof(int);
+  const size_t lds = (size_t)N * per_pred;
+  if (const int e = qp_allow_lds<qm_match_kernel>("vkas_quad_match", lds, QM_MAX * per_pred)) return e;
+  const QpTables t = qp_tables(gt_rows, gt_count, pred_rows, pred_count, M, N, max_pairs, workspace, l);
+  const QmMatchRule r{{}, iou_thr, stats, qp_at<int>(workspace, l.cand_pred), qp_at<unsigned long long>(workspace, l.cand_iou)};
   hipStream_t s = vkas_stream(stream);
   const dim3 grid((unsigned)l.NT, (unsigned)l.MT, (unsigned)B);
-  qm_pair_kernel<false, QM_MATCH><<<grid, QM_THREADS, 0, s>>>(gt_rows, gt_count, pred_rows, pred_count, M, N, l.Mp, l.NT,
-                                                            iou_thr, words, tpre, tile_pairs, rowoff, stats, cand_pred,
-                                                            cand_iou, max_pairs, nullptr, QrArgs{});
+  qm_pair_kernel<false><<<grid, QM_THREADS, 0, s>>>(t, r);
   VKAS_LAUNCH_CHECK("quad_match pairs");
-  qm_scan_kernel<QM_MATCH><<<B, QM_BLOCK, 0, s>>>(gt_rows, gt_count, pred_rows, pred_count, M, N, l.Mp, l.NT, l.MT, words, tpre,
-                                               tile_pairs, rowoff, stats, max_pairs, nullptr, QrArgs{}, nullptr, nullptr);
+  qm_scan_kernel<<<B, QM_BLOCK, 0, s>>>(t, r);
   VKAS_LAUNCH_CHECK("quad_match scan");
-  qm_pair_kernel<true, QM_MATCH><<<grid, QM_THREADS, 0, s>>>(gt_rows, gt_count, pred_rows, pred_count, M, N, l.Mp, l.NT,
-                                                           iou_thr, words, tpre, tile_pairs, rowoff, stats, cand_pred,
-                                                           cand_iou, max_pairs, nullptr, QrArgs{});
+  qm_pair_kernel<true><<<grid, QM_THREADS, 0, s>>>(t, r);
   VKAS_LAUNCH_CHECK("quad_match fill");
-  qm_match_kernel<<<B, QM_BLOCK, lds, s>>>(gt_count, pred_count, M, N, l.Mp, rowoff, cand_pred, cand_iou, max_pairs, gt_match,
-                                           pred_match, gt_iou, stats, rounds);
+  qm_match_kernel<<<B, QM_BLOCK, lds, s>>>(gt_count, pred_count, M, N, l.Mp, t.rowoff, r.cand_pred, r.cand_iou, max_pairs,
+                                           gt_match, pred_match, gt_iou, stats, rounds);
   VKAS_LAUNCH_CHECK("quad_match rounds");
   return VKAS_OK;
 }
@@ -861,14 +701,14 @@ extern "C" int vkas_quad_rows(const double* quads, const unsigned char* valid, i
 }
 
 extern "C" long long vkas_quad_nms_workspace_bytes(int B, int K, int max_pairs) {
-  if (qm_check_dims("vkas_quad_nms_workspace_bytes", B, K, K, max_pairs) != VKAS_OK) return -1;
+  if (qp_check_dims("vkas_quad_nms_workspace_bytes", B, K, K, max_pairs) != VKAS_OK) return -1;
   return (long long)qm_layout(B, K, K, max_pairs, false).bytes;
 }
 
 extern "C" int vkas_quad_nms(const int* rows, const int* count, const float* probs, int B, int K, double iou_thr,
                              int max_pairs, void* workspace, size_t workspace_bytes, unsigned char* keep, int* suppressor,
                              long long* stats, int* rounds, void* stream) {
-  const int rc = qm_check_dims("vkas_quad_nms", B, K, K, max_pairs);
+  const int rc = qp_check_dims("vkas_quad_nms", B, K, K, max_pairs);
   if (rc != VKAS_OK) return rc;
   VKAS_CHECK(iou_thr > 0.0 && iou_thr <= 1.0, "vkas_quad_nms: iou_thr = %g must lie in (0, 1]", iou_thr);
   if (B == 0) return VKAS_OK;
@@ -879,24 +719,17 @@ extern "C" int vkas_quad_nms(const int* rows, const int* count, const float* pro
              "vkas_quad_nms: probs and suppressor must be 4-byte aligned, stats 8-byte aligned");
   const QmLayout l = qm_layout(B, K, K, max_pairs, false);
   VKAS_CHECK(workspace_bytes >= l.bytes, "vkas_quad_nms: workspace of %zu bytes, %zu needed", workspace_bytes, l.bytes);
-  char* ws = static_cast<char*>(workspace);
-  unsigned long long* words = reinterpret_cast<unsigned long long*>(ws + l.words);
-  int* tpre = reinterpret_cast<int*>(ws + l.tpre);
-  int* rowoff = reinterpret_cast<int*>(ws + l.rowoff);
-  int* tile_pairs = reinterpret_cast<int*>(ws + l.tile_pairs);
-  int* cand = reinterpret_cast<int*>(ws + l.cand_pred);
+  const QpTables t = qp_tables(rows, count, rows, count, K, K, max_pairs, workspace, l);
+  const QmSelfRule r{{}, iou_thr, stats, probs, qp_at<int>(workspace, l.cand_pred)};
   hipStream_t s = vkas_stream(stream);
   const dim3 grid((unsigned)l.NT, (unsigned)l.MT, (unsigned)B);
-  qm_pair_kernel<false, QM_SELF><<<grid, QM_THREADS, 0, s>>>(rows, count, rows, count, K, K, l.Mp, l.NT, iou_thr, words, tpre,
-                                                           tile_pairs, rowoff, stats, cand, nullptr, max_pairs, probs, QrArgs{});
+  qm_pair_kernel<false><<<grid, QM_THREADS, 0, s>>>(t, r);
   VKAS_LAUNCH_CHECK("quad_nms pairs");
-  qm_scan_kernel<QM_SELF><<<B, QM_BLOCK, 0, s>>>(rows, count, rows, count, K, K, l.Mp, l.NT, l.MT, words, tpre, tile_pairs,
-                                              rowoff, stats, max_pairs, probs, QrArgs{}, nullptr, nullptr);
+  qm_scan_kernel<<<B, QM_BLOCK, 0, s>>>(t, r);
   VKAS_LAUNCH_CHECK("quad_nms scan");
-  qm_pair_kernel<true, QM_SELF><<<grid, QM_THREADS, 0, s>>>(rows, count, rows, count, K, K, l.Mp, l.NT, iou_thr, words, tpre,
-                                                          tile_pairs, rowoff, stats, cand, nullptr, max_pairs, probs, QrArgs{});
+  qm_pair_kernel<true><<<grid, QM_THREADS, 0, s>>>(t, r);
   VKAS_LAUNCH_CHECK("quad_nms fill");
-  qn_rounds_kernel<<<B, QM_BLOCK, 0, s>>>(rows, count, probs, K, l.Mp, rowoff, cand, max_pairs, keep, suppressor, stats,
+  qn_rounds_kernel<<<B, QM_BLOCK, 0, s>>>(rows, count, probs, K, l.Mp, t.rowoff, r.cand, max_pairs, keep, suppressor, stats,
                                           rounds);
   VKAS_LAUNCH_CHECK("quad_nms rounds");
   return VKAS_OK;
@@ -906,23 +739,20 @@ namespace {
 
 // ---- ranked matching: the launcher ---------------------------------------------------------------------------------
 // workspace: QmLayout's, then cover (B, MT * NT) u64 and tile_info (B, MT * NT, 1 + T) int
-struct QrLayout {
-  QmLayout q;
-  size_t cover, tile_info, bytes;
+struct QrLayout : QmLayout {
+  size_t cover, tile_info;
 };
 
 QrLayout qr_layout(int B, int M, int N, int T, int max_pairs) {
-  QrLayout l;
-  l.q = qm_layout(B, M, N, max_pairs);
-  const size_t tiles = (size_t)B * l.q.MT * l.q.NT;
-  l.cover = l.q.bytes;
-  l.tile_info = qm_align(l.cover + tiles * sizeof(unsigned long long));
-  l.bytes = qm_align(l.tile_info + tiles * (1 + (size_t)T) * sizeof(int));
+  QrLayout l{qm_layout(B, M, N, max_pairs)};
+  l.cover = l.bytes;
+  l.tile_info = qm_align(l.cover + l.tiles * sizeof(unsigned long long));
+  l.bytes = qm_align(l.tile_info + l.tiles * (1 + (size_t)T) * sizeof(int));
   return l;
 }
 
 int qr_check_dims(const char* what, int B, int M, int N, int T, int max_pairs) {
-  const int rc = qm_check_dims(what, B, M, N, max_pairs);
+  const int rc = qp_check_dims(what, B, M, N, max_pairs);
   if (rc != VKAS_OK) return rc;
   VKAS_CHECK(T >= 1 && T <= QR_TMAX, "%s: T=%d thresholds must lie in 1..%d", what, T, QR_TMAX);
   VKAS_CHECK((long)B * T <= 65535, "%s: B*T = %ld above 65535", what, (long)B * T);
@@ -966,47 +796,27 @@ extern "C" int vkas_quad_match_ranked(const int* gt_rows, const int* gt_count, c
   const QrLayout l = qr_layout(B, M, N, T, max_pairs);
   VKAS_CHECK(workspace_bytes >= l.bytes, "vkas_quad_match_ranked: workspace of %zu bytes, %zu needed", workspace_bytes,
              l.bytes);
-  // the rounds keep 14 bytes per pred and 3 per gt in LDS: above the default 64 KB the kernel is opted in, once
+  // the rounds keep 14 bytes per pred and 3 per gt in LDS
   const size_t lds = qr_lds_bytes(M, N);
-  static size_t lds_allowed = 48 * 1024;
-  if (lds > lds_allowed) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(qr_rounds_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)qr_lds_bytes(QM_MAX, QM_MAX));
-    if (e != hipSuccess) {
-      vkas_set_error("vkas_quad_match_ranked: %zu bytes of LDS for M = %d, N = %d refused: %s", lds, M, N,
-                     hipGetErrorString(e));
-      return VKAS_E_LAUNCH;
-    }
-    lds_allowed = qr_lds_bytes(QM_MAX, QM_MAX);
-  }
-  char* ws = static_cast<char*>(workspace);
-  unsigned long long* words = reinterpret_cast<unsigned long long*>(ws + l.q.words);
-  unsigned long long* cand_iou = reinterpret_cast<unsigned long long*>(ws + l.q.cand_iou);
-  int* tpre = reinterpret_cast<int*>(ws + l.q.tpre);
-  int* rowoff = reinterpret_cast<int*>(ws + l.q.rowoff);
-  int* tile_pairs = reinterpret_cast<int*>(ws + l.q.tile_pairs);
-  int* cand_pred = reinterpret_cast<int*>(ws + l.q.cand_pred);
+  if (const int e = qp_allow_lds<qr_rounds_kernel>("vkas_quad_match_ranked", lds, qr_lds_bytes(QM_MAX, QM_MAX))) return e;
   x.gt_care = gt_care;
-  x.cover = reinterpret_cast<unsigned long long*>(ws + l.cover);
-  x.tile_info = reinterpret_cast<int*>(ws + l.tile_info);
+  x.cover = qp_at<unsigned long long>(workspace, l.cover);
+  x.tile_info = qp_at<int>(workspace, l.tile_info);
   x.cover_thr = cover_thr;
   x.T = T;
+  const QpTables t = qp_tables(gt_rows, gt_count, pred_rows, pred_count, M, N, max_pairs, workspace, l);
+  const QrRule r{{}, x, probs, stats, qp_at<int>(workspace, l.cand_pred), qp_at<unsigned long long>(workspace, l.cand_iou)};
   hipStream_t s = vkas_stream(stream);
-  const dim3 grid((unsigned)l.q.NT, (unsigned)l.q.MT, (unsigned)B);
-  qm_pair_kernel<false, QM_RANKED><<<grid, QM_THREADS, 0, s>>>(gt_rows, gt_count, pred_rows, pred_count, M, N, l.q.Mp, l.q.NT,
-                                                               x.thr[0], words, tpre, tile_pairs, rowoff, stats, cand_pred,
-                                                               cand_iou, max_pairs, probs, x);
+  const dim3 grid((unsigned)l.NT, (unsigned)l.MT, (unsigned)B);
+  qm_pair_kernel<false><<<grid, QM_THREADS, 0, s>>>(t, r);
   VKAS_LAUNCH_CHECK("quad_match_ranked pairs");
-  qm_scan_kernel<QM_RANKED><<<B, QM_BLOCK, 0, s>>>(gt_rows, gt_count, pred_rows, pred_count, M, N, l.q.Mp, l.q.NT, l.q.MT, words,
-                                                   tpre, tile_pairs, rowoff, stats, max_pairs, probs, x, covered, dc_stats);
+  qm_scan_kernel<<<B, QM_BLOCK, 0, s>>>(t, r, covered, dc_stats);
   VKAS_LAUNCH_CHECK("quad_match_ranked scan");
-  qm_pair_kernel<true, QM_RANKED><<<grid, QM_THREADS, 0, s>>>(gt_rows, gt_count, pred_rows, pred_count, M, N, l.q.Mp, l.q.NT,
-                                                              x.thr[0], words, tpre, tile_pairs, rowoff, stats, cand_pred,
-                                                              cand_iou, max_pairs, probs, x);
+  qm_pair_kernel<true><<<grid, QM_THREADS, 0, s>>>(t, r);
   VKAS_LAUNCH_CHECK("quad_match_ranked fill");
-  qr_rounds_kernel<<<(unsigned)(B * T), QM_BLOCK, lds, s>>>(gt_count, pred_rows, pred_count, probs, covered, M, N, l.q.Mp, x,
-                                                            rowoff, cand_pred, cand_iou, max_pairs, pred_match, pred_state,
-                                                            gt_match, pred_iou, stats, rounds);
+  qr_rounds_kernel<<<(unsigned)(B * T), QM_BLOCK, lds, s>>>(gt_count, pred_rows, pred_count, probs, covered, M, N, l.Mp, x,
+                                                            t.rowoff, r.cand_pred, r.cand_iou, max_pairs, pred_match,
+                                                            pred_state, gt_match, pred_iou, stats, rounds);
   VKAS_LAUNCH_CHECK("quad_match_ranked rounds");
   return VKAS_OK;
 }

@@ -97,6 +97,14 @@ def _ws(nbytes: int, device) -> torch.Tensor:
     return torch.empty(((nbytes + 3) // 4 + 4,), dtype=_FLOAT, device=device)
 
 
+def _workspace(what: str, nbytes: int, device) -> torch.Tensor:
+    """The byte workspace of an op whose ``*_workspace_bytes`` answered ``nbytes``; a negative answer means the library
+    refused the dimensions, and its message is raised."""
+    if nbytes < 0:
+        check(-1, what)
+    return torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=device)
+
+
 class _ZeroArena:
     """Zero-initialised fp32 scratch for the atomically accumulated weight-gradient images of one training step: the 15
     per-layer ``torch.zeros`` of a backward pass become slices of one buffer that a single fill clears once per step
@@ -2305,10 +2313,7 @@ def char_polygons(prob: torch.Tensor, offset: torch.Tensor, angle: torch.Tensor,
     _require_cuda(prob, offset, angle, dist)
     prob, offset, angle, dist = (t.contiguous() for t in (prob, offset, angle, dist))
     cap, dev = B * H * W, prob.device
-    nbytes = lib.vkas_char_polygons_workspace_bytes(B, H, W, isize)
-    if nbytes < 0:
-        check(-1, 'char_polygons')
-    ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+    ws = _workspace('char_polygons', lib.vkas_char_polygons_workspace_bytes(B, H, W, isize), dev)
     count = torch.empty((1,), dtype=torch.int32, device=dev)
     points = torch.empty((cap, 3), dtype=torch.int32, device=dev)
     probs = torch.empty((cap,), dtype=_FLOAT, device=dev)
@@ -2321,6 +2326,74 @@ def char_polygons(prob: torch.Tensor, offset: torch.Tensor, angle: torch.Tensor,
     return count, points, probs, quads
 
 
+# ---- the checks the ops over quad row tables share: every ValueError comes before the device check -------------------------
+
+def _row_table(who: str, side: str, rows: torch.Tensor, count: torch.Tensor, words: int = 16) -> Tuple[int, int]:
+    """one (B, K, words) int32 row table and its (B,) int32 count -> B, K; ``side`` is '', 'gt_' or 'pred_'"""
+    if rows.dim() != 3 or rows.shape[2] != words:
+        raise ValueError(f'{who}: {side}rows must be (B, K, {words}), got {tuple(rows.shape)}')
+    B, K = int(rows.shape[0]), int(rows.shape[1])
+    if count.shape != (B,):
+        raise ValueError(f'{who}: {side}count must be {(B,)}, got {tuple(count.shape)}')
+    if rows.dtype != torch.int32 or count.dtype != torch.int32:
+        raise ValueError(f'{who}: {side}rows and {side}count must be int32, got {rows.dtype} and {count.dtype}')
+    return B, K
+
+
+def _row_values(who: str, name: str, t: Optional[torch.Tensor], shape, dtype):
+    """an optional table with one value per row (``gt_care``, ``probs``)"""
+    if t is not None and (t.shape != shape or t.dtype != dtype):
+        raise ValueError(f'{who}: {name} must be a {shape} {dtype} tensor, got {tuple(t.shape)} {t.dtype}')
+
+
+def _one_device(who: str, *tensors, also=None):
+    """``tensors`` (None allowed) and ``also`` are on one GPU -> ``tensors``, contiguous"""
+    dev = tensors[0].device
+    for t in tensors + (also,):
+        if t is not None:
+            _require_cuda(t)
+            if t.device != dev:
+                raise ValueError(f'{who}: all tensors must be on one device')
+    return tuple(None if t is None else t.contiguous() for t in tensors)
+
+
+def _quad_limits(who: str, B: int, names: str, sizes, max_pairs, rounds, rounds_tail=(), T: int = 1) -> int:
+    """What the kernels over match rows hold a call to - 1..8192 rows a side, B * T workgroups, a (B, *rounds_tail)
+    ``rounds`` - and the one place ``max_pairs`` is resolved: 4 rows' worth by default, B * max_pairs below 2^31."""
+    if min(sizes) < 1 or max(sizes) > 8192:
+        raise ValueError(f'{who}: {names} = {sizes} must lie in 1..8192')
+    if B * T > 65535:
+        raise ValueError(f'{who}: B = {B} above 65535' if T == 1 else f'{who}: B*T = {B * T} above 65535')
+    max_pairs = 4 * max(sizes) if max_pairs is None else int(max_pairs)
+    if max_pairs < 0 or B * max_pairs >= 1 << 31:
+        raise ValueError(f'{who}: max_pairs = {max_pairs} must be >= 0 and B*max_pairs below 2^31')
+    if rounds is not None and (rounds.shape != (B,) + rounds_tail or rounds.dtype != torch.int32 or not rounds.is_contiguous()):
+        raise ValueError(f'{who}: rounds must be a contiguous {(B,) + rounds_tail} int32 tensor')
+    return max_pairs
+
+
+def _quad_tables(who: str, gt_rows, gt_count, pred_rows, pred_count, max_pairs, rounds, rounds_tail=(), gt_care=None,
+                 probs=None, T: int = 1):
+    """The tables of a two-sided call: match rows and counts, optional ``gt_care`` (B, M) uint8 and ``probs`` (B, N) float32
+    -> ``(gt_rows, gt_count, pred_rows, pred_count, gt_care, probs)`` contiguous on one GPU, ``B, M, N, max_pairs``."""
+    B, M = _row_table(who, 'gt_', gt_rows, gt_count)
+    Bp, N = _row_table(who, 'pred_', pred_rows, pred_count)
+    if Bp != B:
+        raise ValueError(f'{who}: {B} images of annotations against {Bp} of predictions')
+    _row_values(who, 'gt_care', gt_care, (B, M), torch.uint8)
+    _row_values(who, 'probs', probs, (B, N), torch.float32)
+    max_pairs = _quad_limits(who, B, '(M, N)', (M, N), max_pairs, rounds, rounds_tail, T)
+    return _one_device(who, gt_rows, gt_count, pred_rows, pred_count, gt_care, probs, also=rounds), B, M, N, max_pairs
+
+
+def _quad_table(who: str, rows, count, probs=None, max_pairs=0, rounds=None):
+    """The one-sided form -> ``(rows, count, probs)`` contiguous on one GPU, ``B, K, max_pairs``."""
+    B, K = _row_table(who, '', rows, count)
+    _row_values(who, 'probs', probs, (B, K), torch.float32)
+    max_pairs = _quad_limits(who, B, '(K,)', (K,), max_pairs, rounds)
+    return _one_device(who, rows, count, probs, also=rounds), B, K, max_pairs
+
+
 def char_label_maps(rows: torch.Tensor, count: torch.Tensor, h: int, w: int, box, sigma: float = 0.5,
                     with_owner: bool = False, with_height: bool = True, with_score: bool = True):
     """Training label maps from character quadrilaterals on the device (csrc/labels.hip; the rule and the host oracle:
@@ -2329,14 +2402,7 @@ def char_label_maps(rows: torch.Tensor, count: torch.Tensor, h: int, w: int, box
     each (B, CH, CW) cropped to the box - int32 ``index + 1`` (0 = none), and fp32 ``owner != 0``, the owner's height, ``exp(-a)``
     of the owner - with None for an output that was not asked for.  One launch; never synchronises, so it can be captured
     into a HIP graph."""
-    if rows.dim() != 3 or rows.shape[2] != 20:
-        raise ValueError(f'char_label_maps: rows must be (B, K, 20), got {tuple(rows.shape)}')
-    B, K, _ = rows.shape
-    if tuple(count.shape) != (B,):
-        raise ValueError(f'char_label_maps: count must be {(B,)}, got {tuple(count.shape)}')
-    for name, t in (('rows', rows), ('count', count)):
-        if t.dtype != torch.int32:
-            raise ValueError(f'char_label_maps: {name} must be int32, got {t.dtype}')
+    B, K = _row_table('char_label_maps', '', rows, count, words=20)
     up, down, left, right = (int(v) for v in (box if isinstance(box, (tuple, list)) else
                                               (box.up, box.down, box.left, box.right)))
     h, w = int(h), int(w)
@@ -2351,10 +2417,7 @@ def char_label_maps(rows: torch.Tensor, count: torch.Tensor, h: int, w: int, box
     sigma = float(sigma)
     if not (sigma > 0.0 and sigma < float('inf')):
         raise ValueError(f'char_label_maps: sigma must be finite and positive, got {sigma}')
-    _require_cuda(rows, count)
-    if rows.device != count.device:
-        raise ValueError(f'char_label_maps: rows are on {rows.device}, count on {count.device}')
-    rows, count = rows.contiguous(), count.contiguous()
+    rows, count = _one_device('char_label_maps', rows, count)
     CH, CW, dev = down - up + 1, right - left + 1, rows.device
     new = lambda want, dtype: torch.empty((B, CH, CW), dtype=dtype, device=dev) if want else None
     owner, mask = new(with_owner, torch.int32), new(True, _FLOAT)
@@ -2376,44 +2439,18 @@ def match_quads(gt_rows: torch.Tensor, gt_count: torch.Tensor, pred_rows: torch.
     candidates than ``max_pairs`` keeps its true ``pairs`` and ``candidates`` and gets ``status = 1``, every match -1 and
     ``tp = 0``.  ``rounds``, if given, is a (B,) int32 device tensor that receives the matching rounds of each image.  Four
     launches; never synchronises, so it can be captured into a HIP graph."""
-    for name, t, other in (('gt', gt_rows, gt_count), ('pred', pred_rows, pred_count)):
-        if t.dim() != 3 or t.shape[2] != 16:
-            raise ValueError(f'match_quads: {name}_rows must be (B, K, 16), got {tuple(t.shape)}')
-        if tuple(other.shape) != (t.shape[0],):
-            raise ValueError(f'match_quads: {name}_count must be {(t.shape[0],)}, got {tuple(other.shape)}')
-        if t.dtype != torch.int32 or other.dtype != torch.int32:
-            raise ValueError(f'match_quads: {name}_rows and {name}_count must be int32, got {t.dtype} and {other.dtype}')
-    B, M, _ = gt_rows.shape
-    N = pred_rows.shape[1]
-    if pred_rows.shape[0] != B:
-        raise ValueError(f'match_quads: {B} images of annotations against {pred_rows.shape[0]} of predictions')
-    if not (1 <= M <= 8192 and 1 <= N <= 8192):
-        raise ValueError(f'match_quads: M = {M} and N = {N} must lie in 1..8192')
-    if B > 65535:
-        raise ValueError(f'match_quads: B = {B} above 65535')
     iou_thr = float(iou_thr)
     if not (iou_thr > 0.0 and iou_thr <= 1.0):
         raise ValueError(f'match_quads: iou_thr must lie in (0, 1], got {iou_thr}')
-    max_pairs = 4 * max(M, N) if max_pairs is None else int(max_pairs)
-    if max_pairs < 0 or B * max_pairs >= 1 << 31:
-        raise ValueError(f'match_quads: max_pairs = {max_pairs} must be >= 0 and B*max_pairs below 2^31')
-    if rounds is not None and (tuple(rounds.shape) != (B,) or rounds.dtype != torch.int32 or not rounds.is_contiguous()):
-        raise ValueError(f'match_quads: rounds must be a contiguous ({B},) int32 tensor')
-    tensors = (gt_rows, gt_count, pred_rows, pred_count) + (() if rounds is None else (rounds,))
-    _require_cuda(*tensors)
-    if any(t.device != gt_rows.device for t in tensors):
-        raise ValueError('match_quads: all tensors must be on one device')
-    gt_rows, gt_count, pred_rows, pred_count = (t.contiguous() for t in (gt_rows, gt_count, pred_rows, pred_count))
+    (gt_rows, gt_count, pred_rows, pred_count, _, _), B, M, N, max_pairs = _quad_tables(
+        'match_quads', gt_rows, gt_count, pred_rows, pred_count, max_pairs, rounds)
     dev = gt_rows.device
     gt_match = torch.empty((B, M), dtype=torch.int32, device=dev)
     pred_match = torch.empty((B, N), dtype=torch.int32, device=dev)
     gt_iou = torch.empty((B, M), dtype=torch.float64, device=dev)
     stats = torch.empty((B, 6), dtype=torch.int64, device=dev)
     if B:
-        nbytes = lib.vkas_quad_match_workspace_bytes(B, M, N, max_pairs)
-        if nbytes < 0:
-            check(-1, 'match_quads')
-        ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+        ws = _workspace('match_quads', lib.vkas_quad_match_workspace_bytes(B, M, N, max_pairs), dev)
         check(lib.vkas_quad_match(_p(gt_rows), _p(gt_count), _p(pred_rows), _p(pred_count), B, M, N, iou_thr, max_pairs, _p(ws),
                                   ws.numel(), _p(gt_match), _p(pred_match), _p(gt_iou), _p(stats), _p(rounds), _stream()),
               'match_quads')
@@ -2436,49 +2473,18 @@ def match_quads_ranked(gt_rows: torch.Tensor, gt_count: torch.Tensor, gt_care: O
     given, is a (B, T) int32 device tensor that receives the rounds.  Four launches; never synchronises, so it can be captured
     into a HIP graph."""
     what = 'match_quads_ranked'
-    for name, t, other in (('gt', gt_rows, gt_count), ('pred', pred_rows, pred_count)):
-        if t.dim() != 3 or t.shape[2] != 16:
-            raise ValueError(f'{what}: {name}_rows must be (B, K, 16), got {tuple(t.shape)}')
-        if tuple(other.shape) != (t.shape[0],):
-            raise ValueError(f'{what}: {name}_count must be {(t.shape[0],)}, got {tuple(other.shape)}')
-        if t.dtype != torch.int32 or other.dtype != torch.int32:
-            raise ValueError(f'{what}: {name}_rows and {name}_count must be int32, got {t.dtype} and {other.dtype}')
-    B, M, _ = (int(v) for v in gt_rows.shape)
-    N = int(pred_rows.shape[1])
-    if pred_rows.shape[0] != B:
-        raise ValueError(f'{what}: {B} images of annotations against {pred_rows.shape[0]} of predictions')
-    if tuple(probs.shape) != (B, N) or probs.dtype != torch.float32:
-        raise ValueError(f'{what}: probs must be a {(B, N)} float32 tensor, got {tuple(probs.shape)} {probs.dtype}')
-    if gt_care is not None and (tuple(gt_care.shape) != (B, M) or gt_care.dtype != torch.uint8):
-        raise ValueError(f'{what}: gt_care must be a {(B, M)} uint8 tensor, got {tuple(gt_care.shape)} {gt_care.dtype}')
-    if not (1 <= M <= 8192 and 1 <= N <= 8192):
-        raise ValueError(f'{what}: M = {M} and N = {N} must lie in 1..8192')
     from .inferencing.ranking import check_thresholds  # the rule's own check, stated once
     thrs, cover_thr = check_thresholds(iou_thrs, cover_thr)
     T = len(thrs)
-    if B * T > 65535:
-        raise ValueError(f'{what}: B*T = {B * T} above 65535')
-    max_pairs = 4 * max(M, N) if max_pairs is None else int(max_pairs)
-    if max_pairs < 0 or B * max_pairs >= 1 << 31:
-        raise ValueError(f'{what}: max_pairs = {max_pairs} must be >= 0 and B*max_pairs below 2^31')
-    if rounds is not None and (tuple(rounds.shape) != (B, T) or rounds.dtype != torch.int32 or not rounds.is_contiguous()):
-        raise ValueError(f'{what}: rounds must be a contiguous ({B}, {T}) int32 tensor')
-    tensors = (gt_rows, gt_count, pred_rows, pred_count, probs) + tuple(t for t in (gt_care, rounds) if t is not None)
-    _require_cuda(*tensors)
-    if any(t.device != gt_rows.device for t in tensors):
-        raise ValueError(f'{what}: all tensors must be on one device')
-    gt_rows, gt_count, pred_rows, pred_count, probs = (t.contiguous() for t in (gt_rows, gt_count, pred_rows, pred_count, probs))
-    gt_care = None if gt_care is None else gt_care.contiguous()
+    (gt_rows, gt_count, pred_rows, pred_count, gt_care, probs), B, M, N, max_pairs = _quad_tables(
+        what, gt_rows, gt_count, pred_rows, pred_count, max_pairs, rounds, (T,), gt_care, probs, T)
     dev = gt_rows.device
     new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
     pred_match, pred_state = new((B, T, N), torch.int32), new((B, T, N), torch.uint8)
     gt_match, pred_iou = new((B, T, M), torch.int32), new((B, T, N), torch.float64)
     covered, stats, dc_stats = new((B, N), torch.uint8), new((B, T, 8), torch.int64), new((B, 3), torch.int64)
     if B:
-        nbytes = lib.vkas_quad_match_ranked_workspace_bytes(B, M, N, T, max_pairs)
-        if nbytes < 0:
-            check(-1, what)
-        ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+        ws = _workspace(what, lib.vkas_quad_match_ranked_workspace_bytes(B, M, N, T, max_pairs), dev)
         host_thrs = (ctypes.c_double * T)(*thrs)  # read by the launcher before it returns
         check(lib.vkas_quad_match_ranked(_p(gt_rows), _p(gt_count), _p(gt_care), _p(pred_rows), _p(pred_count), _p(probs), B, M,
                                          N, ctypes.cast(host_thrs, ctypes.c_void_p), T, cover_thr, max_pairs, _p(ws),
@@ -2501,46 +2507,17 @@ def match_lines(gt_rows: torch.Tensor, gt_count: torch.Tensor, gt_care: Optional
     that receives the split and merge rounds.  Four launches; allocates only its outputs and workspace and never
     synchronises, so it can be captured into a HIP graph."""
     what = 'match_lines'
-    for name, t, other in (('gt', gt_rows, gt_count), ('pred', pred_rows, pred_count)):
-        if t.dim() != 3 or t.shape[2] != 16:
-            raise ValueError(f'{what}: {name}_rows must be (B, K, 16), got {tuple(t.shape)}')
-        if tuple(other.shape) != (t.shape[0],):
-            raise ValueError(f'{what}: {name}_count must be {(t.shape[0],)}, got {tuple(other.shape)}')
-        if t.dtype != torch.int32 or other.dtype != torch.int32:
-            raise ValueError(f'{what}: {name}_rows and {name}_count must be int32, got {t.dtype} and {other.dtype}')
-    B, M, _ = (int(v) for v in gt_rows.shape)
-    N = int(pred_rows.shape[1])
-    if pred_rows.shape[0] != B:
-        raise ValueError(f'{what}: {B} images of annotations against {pred_rows.shape[0]} of predictions')
-    if gt_care is not None and (tuple(gt_care.shape) != (B, M) or gt_care.dtype != torch.uint8):
-        raise ValueError(f'{what}: gt_care must be a {(B, M)} uint8 tensor, got {tuple(gt_care.shape)} {gt_care.dtype}')
-    if not (1 <= M <= 8192 and 1 <= N <= 8192):
-        raise ValueError(f'{what}: M = {M} and N = {N} must lie in 1..8192')
-    if B > 65535:
-        raise ValueError(f'{what}: B = {B} above 65535')
     from .inferencing.line_evaluation import check_line_thresholds  # the rule's own check, stated once
     tr_q8, tp_q8, cover_thr = check_line_thresholds(recall_thr, precision_thr, cover_thr)
-    max_pairs = 4 * max(M, N) if max_pairs is None else int(max_pairs)
-    if max_pairs < 0 or B * max_pairs >= 1 << 31:
-        raise ValueError(f'{what}: max_pairs = {max_pairs} must be >= 0 and B*max_pairs below 2^31')
-    if rounds is not None and (tuple(rounds.shape) != (B, 2) or rounds.dtype != torch.int32 or not rounds.is_contiguous()):
-        raise ValueError(f'{what}: rounds must be a contiguous ({B}, 2) int32 tensor')
-    tensors = (gt_rows, gt_count, pred_rows, pred_count) + tuple(t for t in (gt_care, rounds) if t is not None)
-    _require_cuda(*tensors)
-    if any(t.device != gt_rows.device for t in tensors):
-        raise ValueError(f'{what}: all tensors must be on one device')
-    gt_rows, gt_count, pred_rows, pred_count = (t.contiguous() for t in (gt_rows, gt_count, pred_rows, pred_count))
-    gt_care = None if gt_care is None else gt_care.contiguous()
+    (gt_rows, gt_count, pred_rows, pred_count, gt_care, _), B, M, N, max_pairs = _quad_tables(
+        what, gt_rows, gt_count, pred_rows, pred_count, max_pairs, rounds, (2,), gt_care)
     dev = gt_rows.device
     new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
     gt_kind, gt_group = new((B, M), torch.uint8), new((B, M), torch.int32)
     pred_kind, pred_group = new((B, N), torch.uint8), new((B, N), torch.int32)
     stats = new((B, 16), torch.int64)
     if B:
-        nbytes = lib.vkas_line_match_workspace_bytes(B, M, N, max_pairs)
-        if nbytes < 0:
-            check(-1, what)
-        ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+        ws = _workspace(what, lib.vkas_line_match_workspace_bytes(B, M, N, max_pairs), dev)
         check(lib.vkas_line_match(_p(gt_rows), _p(gt_count), _p(gt_care), _p(pred_rows), _p(pred_count), B, M, N, tr_q8, tp_q8,
                                   cover_thr, max_pairs, _p(ws), ws.numel(), _p(gt_kind), _p(gt_group), _p(pred_kind),
                                   _p(pred_group), _p(stats), _p(rounds), _stream()), what)
@@ -2583,40 +2560,16 @@ def nms_quads(rows: torch.Tensor, count: torch.Tensor, probs: torch.Tensor, iou_
     true ``pairs`` and ``candidates`` and gets ``status = 1``, every quad within the count kept and every suppressor -1.
     ``rounds``, if given, is a (B,) int32 device tensor that receives the rounds of each image.  Four launches; never
     synchronises, so it can be captured into a HIP graph."""
-    if rows.dim() != 3 or rows.shape[2] != 16:
-        raise ValueError(f'nms_quads: rows must be (B, K, 16), got {tuple(rows.shape)}')
-    B, K, _ = (int(v) for v in rows.shape)
-    if tuple(count.shape) != (B,) or tuple(probs.shape) != (B, K):
-        raise ValueError(f'nms_quads: count must be {(B,)} and probs {(B, K)}, got {tuple(count.shape)} and {tuple(probs.shape)}')
-    if rows.dtype != torch.int32 or count.dtype != torch.int32 or probs.dtype != torch.float32:
-        raise ValueError(f'nms_quads: rows and count must be int32 and probs float32, got {rows.dtype}, {count.dtype}, '
-                         f'{probs.dtype}')
-    if not 1 <= K <= 8192:
-        raise ValueError(f'nms_quads: K = {K} must lie in 1..8192')
-    if B > 65535:
-        raise ValueError(f'nms_quads: B = {B} above 65535')
     iou_thr = float(iou_thr)
     if not (iou_thr > 0.0 and iou_thr <= 1.0):
         raise ValueError(f'nms_quads: iou_thr must lie in (0, 1], got {iou_thr}')
-    max_pairs = 4 * K if max_pairs is None else int(max_pairs)
-    if max_pairs < 0 or B * max_pairs >= 1 << 31:
-        raise ValueError(f'nms_quads: max_pairs = {max_pairs} must be >= 0 and B*max_pairs below 2^31')
-    if rounds is not None and (tuple(rounds.shape) != (B,) or rounds.dtype != torch.int32 or not rounds.is_contiguous()):
-        raise ValueError(f'nms_quads: rounds must be a contiguous ({B},) int32 tensor')
-    tensors = (rows, count, probs) + (() if rounds is None else (rounds,))
-    _require_cuda(*tensors)
-    if any(t.device != rows.device for t in tensors):
-        raise ValueError('nms_quads: all tensors must be on one device')
-    rows, count, probs = rows.contiguous(), count.contiguous(), probs.contiguous()
+    (rows, count, probs), B, K, max_pairs = _quad_table('nms_quads', rows, count, probs, max_pairs, rounds)
     dev = rows.device
     keep = torch.empty((B, K), dtype=torch.uint8, device=dev)
     suppressor = torch.empty((B, K), dtype=torch.int32, device=dev)
     stats = torch.empty((B, 6), dtype=torch.int64, device=dev)
     if B:
-        nbytes = lib.vkas_quad_nms_workspace_bytes(B, K, max_pairs)
-        if nbytes < 0:
-            check(-1, 'nms_quads')
-        ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+        ws = _workspace('nms_quads', lib.vkas_quad_nms_workspace_bytes(B, K, max_pairs), dev)
         check(lib.vkas_quad_nms(_p(rows), _p(count), _p(probs), B, K, iou_thr, max_pairs, _p(ws), ws.numel(), _p(keep),
                                 _p(suppressor), _p(stats), _p(rounds), _stream()), 'nms_quads')
     return keep, suppressor, stats
@@ -2631,33 +2584,16 @@ def quad_lines(rows: torch.Tensor, count: torch.Tensor, gap: float = 1.5, cross:
     then -1), (B, K, 8) int64 rows ``start, size, U_y, U_x, a_min, a_max, b_min, b_max`` (zero from the image's line count
     on), (B, 4) int64 ``n, n_part, links, lines``.  K table rows is the exact worst case: there is no overflow path.  Eight
     launches; never synchronises, so it can be captured into a HIP graph."""
-    if rows.dim() != 3 or rows.shape[2] != 16:
-        raise ValueError(f'quad_lines: rows must be (B, K, 16), got {tuple(rows.shape)}')
-    B, K, _ = (int(v) for v in rows.shape)
-    if tuple(count.shape) != (B,):
-        raise ValueError(f'quad_lines: count must be {(B,)}, got {tuple(count.shape)}')
-    if rows.dtype != torch.int32 or count.dtype != torch.int32:
-        raise ValueError(f'quad_lines: rows and count must be int32, got {rows.dtype} and {count.dtype}')
-    if not 1 <= K <= 8192:
-        raise ValueError(f'quad_lines: K = {K} must lie in 1..8192')
-    if B > 65535:
-        raise ValueError(f'quad_lines: B = {B} above 65535')
     from .inferencing.lines import line_params  # the rule's own check, stated once
     gap_q4, cross_q4, ratio_q4 = line_params(gap, cross, height_ratio)
-    _require_cuda(rows, count)
-    if count.device != rows.device:
-        raise ValueError('quad_lines: all tensors must be on one device')
-    rows, count = rows.contiguous(), count.contiguous()
+    (rows, count, _), B, K, _ = _quad_table('quad_lines', rows, count)  # no candidates: no capacity to check
     dev = rows.device
     line = torch.empty((B, K), dtype=torch.int32, device=dev)
     order = torch.empty((B, K), dtype=torch.int32, device=dev)
     table = torch.empty((B, K, 8), dtype=torch.int64, device=dev)
     stats = torch.empty((B, 4), dtype=torch.int64, device=dev)
     if B:
-        nbytes = lib.vkas_quad_lines_workspace_bytes(B, K)
-        if nbytes < 0:
-            check(-1, 'quad_lines')
-        ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+        ws = _workspace('quad_lines', lib.vkas_quad_lines_workspace_bytes(B, K), dev)
         check(lib.vkas_quad_lines(_p(rows), _p(count), B, K, gap_q4, cross_q4, ratio_q4, _p(ws), ws.numel(), _p(line),
                                   _p(order), _p(table), _p(stats), _stream()), 'quad_lines')
     return line, order, table, stats
@@ -2694,10 +2630,7 @@ def text_regions(mask: torch.Tensor, height: torch.Tensor, max_regions: int):
         raise ValueError(f'text_regions: mask is on {mask.device}, height on {height.device}')
     mask, height = mask.contiguous(), height.contiguous()
     dev = mask.device
-    nbytes = lib.vkas_text_regions_workspace_bytes(B, H, W, R)
-    if nbytes < 0:
-        check(-1, 'text_regions')
-    ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+    ws = _workspace('text_regions', lib.vkas_text_regions_workspace_bytes(B, H, W, R), dev)
     count = torch.empty((B,), dtype=torch.int32, device=dev)
     labels = torch.empty((B, H, W), dtype=torch.int32, device=dev)
     boxes = torch.empty((B, R, 4), dtype=torch.int32, device=dev)
