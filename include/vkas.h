@@ -781,6 +781,38 @@ int vkas_crop_warp_f32(const unsigned char* arena, long long arena_bytes, const 
  * (always when out, offset and slot_w are multiples of 4), byte stores otherwise. */
 int vkas_quad_strips_u8(const unsigned char* arena, long long arena_bytes, const long long* sources, int S,
                         const long long* rows, int n, int h, unsigned char* out, long long out_bytes, void* stream);
+/* Curved text lines cut into strips along their spines (inferencing/spines.py holds the rule from a line's character quads
+ * to its knots, the integer rule from knots to columns and the host oracle spine_strips_host).  Arena, source table, slots
+ * and tiles are those of vkas_quad_strips_u8.  `table` holds 13*n + 1 + 6*knots_total int64 words: n spine rows of 12 words
+ * (src, offset, slot_w, w, knot_start, knots, col_start, log2n, 0, 0, 0, 0), then tile_start (n + 1 words, as above), then
+ * knots_total knot records of 6 words (q, cy, cx, vy, vx, 0: the strip column, the centre and the down vector in Q16, an
+ * integer coordinate being a pixel centre).  Row r reads the knots knot_start .. knot_start + knots - 1 and owns the column
+ * records col_start .. col_start + w - 1 of the workspace, 6 words each (ay, ax, myy, myx, mxy, mxx).
+ * Column j: lo = 0, hi = knots; while hi - lo > 1: mid = (lo + hi) >> 1, lo = mid if q[mid] <= j else hi = mid.  It is valid
+ * iff lo + 1 < knots, q[lo] <= j < q[lo+1], n = q[lo+1] - q[lo] <= 8192, both knots have |c| < 2^39 and |v| <= 2^30 and the
+ * record is within |a| < 2^40, |m| <= 2^22.  With fdiv the floor division, rdiv(x, d) = fdiv(2x + d, 2d), a = 2*(j - q[lo]) +
+ * 1: Cy = cy_lo + fdiv((cy_hi - cy_lo) * a, 2n) (Cx, Vy, Vx likewise), myy = rdiv(Vy, h), mxy = rdiv(Vx, h), ay = Cy -
+ * fdiv((h - 1) * myy, 2) (ax likewise), myx = rdiv(cy_hi - cy_lo, n), mxx likewise.  An invalid column is six words of
+ * INT64_MIN.  Pixel (i, j) with j < w is the pixel (i, 0) of vkas_warp_pack_u8 for the warp (0, 0, h, 1, ay, ax, myy, myx,
+ * mxy, mxx, log2n) of image src, 0 in an invalid column; the columns w..slot_w-1 are 0.
+ * vkas_spine_strips_workspace_bytes(columns) = 48 * columns (-1 for columns < 0): the caller's workspace holds the sum of
+ * w records (at most out_bytes / (3*h) when the slots are disjoint).  vkas_spine_columns writes the column records alone
+ * (columns_cap: the records there is room for); vkas_spine_strips_u8 runs that launch and the strips launch on one stream.
+ * The kernels check every row themselves: a row whose slot is not defined inside out (as above) is skipped; a row that
+ * fails any other check (those of vkas_quad_strips_u8 on src, the source entry, w and log2n; knot_start < 0, knots < 2,
+ * knot_start + knots > knots_total; col_start < 0, col_start + w > the workspace's records) gets a slot of zeros and no
+ * column records.  tile_start is not trusted either (as above), and a tile reads column records only where the columns
+ * launch, which walks the same tiles by the same search, has written them - else it is dropped: no table content makes a
+ * kernel touch memory outside its buffers.  Rows whose column ranges or slots overlap give an unspecified winner (the
+ * caller's check).  Capture-safe: no allocation, no synchronisation, no atomics; bit-identical from run to run.  h in
+ * 1..256, n >= 0, knots_total >= 0, out_bytes < 2^40, ws_bytes >= 48 * n (columns_cap >= n), pointers non-null, table,
+ * source table and workspace 8-byte aligned: otherwise an error and no launch; no launch for n = 0. */
+long long vkas_spine_strips_workspace_bytes(long long columns);
+int vkas_spine_columns(const long long* table, int n, long long knots_total, int h, long long* columns,
+                       long long columns_cap, void* stream);
+int vkas_spine_strips_u8(const unsigned char* arena, long long arena_bytes, const long long* sources, int S,
+                         const long long* table, int n, long long knots_total, int h, void* ws, long long ws_bytes,
+                         unsigned char* out, long long out_bytes, void* stream);
 
 /* ---- optimizer on the flat parameter / gradient buffers: train.py:468-478 ------------------------------ */
 /* sumsq (1 double, zeroed by the call) = sum g^2 */

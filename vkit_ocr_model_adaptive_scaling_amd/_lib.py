@@ -217,7 +217,11 @@ _SIGS = {
                                         _P]),
     'vkas_crop_warp_f32': (c_int, [_P, c_longlong, _P, c_int, _P, c_int, _P, c_int, c_int, _P]),
     'vkas_quad_strips_u8': (c_int, [_P, c_longlong, _P, c_int, _P, c_int, c_int, _P, c_longlong, _P]),
-    'vkas_l2norm_sq': (c_int, [_P, c_long, _P, _P]),
+    'vkas_spine_strips_workspace_bytes': (c_longlong, [c_longlong]),
+    'vkas_spine_columns': (c_int, [_P, c_int, c_longlong, c_int, _P, c_longlong, _P]),
+    'vkas_spine_strips_u8': (c_int, [_P, c_longlong, _P, c_int, _P, c_int, c_longlong, c_int, _P, c_longlong, _P, c_longlong,
+                                     _P]),
+    'vkas_l2norm_sq':(c_int, [_P, c_long, _P, _P]),
     'vkas_adamw_step': (c_int, [_P, _P, _P, _P, c_long, _P, c_float, c_float, c_float, c_float, c_float, c_float,
                                 c_float, c_int, _P]),
 }

@@ -28,6 +28,8 @@ from .ranking import (OperatingPoint, PRCurve, RankedMatchResult, RankedPairs, R
 from .orient import (orient_regions, oriented_rects, region_directions, region_extents_host, region_moments_host, warp_row)
 from .strips import (QuadStrips, StripLayout, check_strip_rows, quad_strips_host, remap_strip_points, strip_params, strip_rows,
                      strip_table, strip_warp)
-from .line_strips import quad_strips, strips_for_results
+from .spines import (SpineLayout, SpineStrips, check_spine_rows, knot_status, spine_columns_host, spine_knots, spine_pixels_host,
+                     spine_points, spine_polygon, spine_rows, spine_strips_host, spine_table)
+from .line_strips import quad_strips, result_lines, spine_strips, spine_strips_for_results, strips_for_results
 from .line_evaluation import (LineMatchResult, LineScore, check_line_thresholds, evaluate_lines, evaluate_lines_host,
                               line_pairs, match_lines_host, match_lines_rounds_host)

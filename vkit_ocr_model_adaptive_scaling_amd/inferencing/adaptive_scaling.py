@@ -46,7 +46,7 @@ from .packing import (SIDE_MAX, check_multi_rows, check_warps, region_crops, rem
 from .orient import orient_regions, region_directions, warp_row
 from .nms import suppress_results
 from .lines import group_results
-from .line_strips import strips_for_results
+from .line_strips import spine_strips_for_results, strips_for_results
 from .strips import QuadStrips
 from .. import ops
 from .._lib import lib, check
@@ -130,6 +130,11 @@ class AdaptiveScalingInferencingConfig:
     precise_line_strip_width_max: int = 2048
     precise_line_strip_width_step: int = 64
     precise_line_strip_margin: float = 0.125
+    # Curved lines (inferencing/spines.py), read by infer and infer_batch; needs precise_line_strips: every line is cut along
+    # the spine through its characters (csrc/spines.hip) instead of along its chord rectangle, with the same height, widths
+    # and margin; ``line_strips`` is then a ``SpineStrips`` and the results gain ``line_spines``.  ``line_polygons`` stays the
+    # chord rectangle.  Off: every result is bit for bit what it is without the feature, with no extra launch or copy.
+    precise_line_strip_curved: bool = False
 
 
 @attrs.define
@@ -219,6 +224,9 @@ class AdaptiveScalingInferencingResult:
     # infer ``line_strips``, from infer_batch the batch result's ``line_strips``, which all its images share
     line_strip_ids: np.ndarray = attrs.field(factory=lambda: np.zeros((0,), np.int32))     # (L,) int32
     line_strips: Optional[QuadStrips] = None
+    # config.precise_line_strip_curved: ``line_strips`` is a ``SpineStrips`` (inferencing/spines.py), and per line the
+    # (K, 2, 2) float64 centres and down vectors of its spine in image pixels ((0, 2, 2) for a line without a strip)
+    line_spines: list = attrs.field(factory=list)
 
 
 @attrs.define
@@ -616,10 +624,12 @@ class AdaptiveScalingInferencing:
 
     def _line_strips(self, results, images_or_arena):
         """The line-strip step of ``infer`` / ``infer_batch`` (after ``group_results``): the results with ``line_strip_ids``
-        and the one ``QuadStrips`` of all their lines."""
+        and the one ``QuadStrips`` of all their lines - with ``config.precise_line_strip_curved`` also ``line_spines``, and
+        the one ``SpineStrips``."""
         c = self.config
-        return strips_for_results(results, images_or_arena, c.precise_line_strip_height, c.precise_line_strip_width_max,
-                                  c.precise_line_strip_width_step, c.precise_line_strip_margin, c.device)
+        step = spine_strips_for_results if c.precise_line_strip_curved else strips_for_results
+        return step(results, images_or_arena, c.precise_line_strip_height, c.precise_line_strip_width_max,
+                    c.precise_line_strip_width_step, c.precise_line_strip_margin, c.device)
 
     # ---- image in, characters out --------------------------------------------------------------------------------
     def infer(self, image, return_page: bool = False, return_labels: bool = False) -> AdaptiveScalingInferencingResult:
@@ -641,6 +651,8 @@ class AdaptiveScalingInferencing:
         c = self.config
         if c.precise_line_strips and not c.precise_char_lines:
             raise ValueError('precise_line_strips cuts the text lines: set precise_char_lines too')
+        if c.precise_line_strip_curved and not c.precise_line_strips:
+            raise ValueError('precise_line_strip_curved is a way to cut the line strips: set precise_line_strips too')
         mat = _as_mat(image)
         if mat.dtype != np.uint8:
             raise ValueError(f'infer takes a uint8 image, got {mat.dtype}')
@@ -747,6 +759,8 @@ class AdaptiveScalingInferencing:
             raise ValueError('infer_batch does not take oriented text regions yet: unset precise_text_region_orient or use infer')
         if c.precise_line_strips and not c.precise_char_lines:
             raise ValueError('precise_line_strips cuts the text lines: set precise_char_lines too')
+        if c.precise_line_strip_curved and not c.precise_line_strips:
+            raise ValueError('precise_line_strip_curved is a way to cut the line strips: set precise_line_strips too')
         if not len(images):
             return AdaptiveScalingInferencingBatchResult(results=[], page_shapes=[], rows=np.zeros((0, 12), np.int32),
                                                          pages=[] if return_pages else None,

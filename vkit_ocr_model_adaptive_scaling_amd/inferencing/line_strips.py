@@ -1,12 +1,15 @@
 """The device route of inferencing/strips.py: quadrilaterals of several images cut into upright strips in one launch
 (``ops.quad_strips_u8``, csrc/strips.hip), and the step of ``infer`` / ``infer_batch`` that does so for the text lines of
-their results."""
+their results.  And the device route of inferencing/spines.py: text lines cut along the spines through their characters
+(``ops.spine_strips_u8``, csrc/spines.hip), with the same step."""
 from typing import Sequence
 
 import attrs
 import numpy as np
 import torch
 
+from .evaluation import result_quads
+from .spines import SpineStrips, check_spine_rows, spine_rows, spine_strips_from_layout, spine_table
 from .strips import QuadStrips, bucket_views, check_strip_rows, strip_rows, strip_table
 
 
@@ -63,6 +66,54 @@ def quad_strips(images, quads_per_image: Sequence, height: int = 32, width_max: 
         out = torch.empty((0,), dtype=torch.uint8, device=device)
     return QuadStrips(bucket_views(out, layout.bucket_shapes), layout.image, layout.status, layout.squeezed, layout.widths,
                       layout.bucket, layout.index, layout.rows, h)
+
+
+def spine_strips(images, lines_per_image: Sequence, height: int = 32, width_max: int = 2048, width_step: int = 64,
+                 margin: float = 0.125, device='cuda') -> SpineStrips:
+    """Cuts the text lines ``lines_per_image[s]`` - a list of (m, 4, 2) ``(y, x)`` arrays, the character quads of each line of
+    image s in reading order - out of image s along their spines (inferencing/spines.py) and brings them to ``height`` rows:
+    ``images`` as ``quad_strips`` takes them, one table upload, two launches, nothing read back - the per-line arrays and
+    the knots come from the host rule (``spine_rows``).  Equal to ``spine_strips_host`` byte for byte, with device buckets."""
+    from .. import ops
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise ValueError(f'spine_strips runs on the GPU, got device {device} (host route: spine_strips_host)')
+    layout = spine_rows(lines_per_image, height, width_max, width_step, margin)
+    h = int(height)
+    if len(layout.rows):
+        arena, sources, d_sources = _arena(images, device)
+        if len(sources) != len(lines_per_image):
+            raise ValueError(f'{len(lines_per_image)} line lists for {len(sources)} images')
+        if ((sources[:, 0] < 0) | (sources[:, 0] + 3 * sources[:, 1] * sources[:, 2] > int(arena.numel()))).any():
+            raise ValueError(f'spine_strips: a source leaves the arena of {int(arena.numel())} bytes')
+        check_spine_rows(layout.rows, layout.knots, sources, h, layout.out_bytes, layout.columns)  # on the host
+        d_table = torch.from_numpy(spine_table(layout.rows, layout.knots, h)).to(arena.device, non_blocking=True)
+        out = ops.spine_strips_u8(arena, d_sources, d_table, len(layout.rows), len(layout.knots), h, layout.out_bytes,
+                                  validate=False)
+    else:
+        out = torch.empty((0,), dtype=torch.uint8, device=device)
+    return spine_strips_from_layout(layout, bucket_views(out, layout.bucket_shapes), h)
+
+
+def result_lines(result) -> list:
+    """The lines of a result as ``spine_strips`` takes them: per line the quads of its members in reading order."""
+    quads = result_quads(result)[0]
+    return [quads[np.asarray(members, dtype=np.int64)] for members in result.line_chars]
+
+
+def spine_strips_for_results(results: Sequence, images_or_arena, height: int = 32, width_max: int = 2048,
+                             width_step: int = 64, margin: float = 0.125, device='cuda'):
+    """``strips_for_results`` along the spines: the lines of all results - result i reads image i - go through ONE
+    ``spine_strips`` call.  -> the results with ``line_strip_ids`` and ``line_spines`` (per line the (K, 2, 2) centres and down
+    vectors of ``SpineStrips.spine``; (0, 2, 2) for a line without a strip) filled, and the one shared ``SpineStrips``."""
+    strips = spine_strips(images_or_arena, [result_lines(r) for r in results], height, width_max, width_step, margin, device)
+    out, first = [], 0
+    for r in results:
+        n = len(r.line_chars)
+        spines = [strips.spine(k) if strips.status[k] == 0 else np.zeros((0, 2, 2), np.float64) for k in range(first, first + n)]
+        out.append(attrs.evolve(r, line_strip_ids=np.arange(first, first + n, dtype=np.int32), line_spines=spines))
+        first += n
+    return out, strips
 
 
 def strips_for_results(results: Sequence, images_or_arena, height: int = 32, width_max: int = 2048, width_step: int = 64,

@@ -111,6 +111,25 @@ class StripLayout:
     out_bytes: int
 
 
+def slot_layout(have: np.ndarray, widths: np.ndarray, h: int, width_step: int):
+    """The slots and buckets of the module docstring for N strips of which ``have`` exist, ``widths`` columns wide ->
+    ``(slot_w (N,) int64, offset (N,) int64, bucket (N,) int32, index (N,) int32, bucket_shapes, out_bytes)``."""
+    N = len(widths)
+    slot_w = np.where(have, -(-widths.astype(np.int64) // width_step) * width_step, 0)
+    sizes = sorted(set(slot_w[have].tolist()))
+    bucket = np.full((N,), -1, np.int32)
+    index = np.full((N,), -1, np.int32)
+    offset = np.zeros((N,), np.int64)
+    shapes, total = [], 0
+    for b, sw in enumerate(sizes):
+        mine = np.flatnonzero(have & (slot_w == sw))
+        bucket[mine], index[mine] = b, np.arange(len(mine))
+        offset[mine] = total + np.arange(len(mine), dtype=np.int64) * (h * sw * 3)
+        shapes.append((len(mine), h, int(sw), 3))
+        total += len(mine) * h * sw * 3
+    return slot_w, offset, bucket, index, shapes, int(total)
+
+
 def strip_rows(quads_per_image: Sequence, h: int = 32, width_max: int = 2048, width_step: int = 64,
                margin: float = 0.125) -> StripLayout:
     """The strip rows of the quads of several images - ``quads_per_image[s]`` is an (n_s, 4, 2) array of quads of source s -
@@ -124,18 +143,7 @@ def strip_rows(quads_per_image: Sequence, h: int = 32, width_max: int = 2048, wi
     for k, quad in enumerate(q for qs in quads for q in qs):
         status[k], squeezed[k], widths[k], coefs[k] = strip_warp(quad, h, width_max, margin)
     have = status == 0
-    slot_w = np.where(have, -(-widths.astype(np.int64) // width_step) * width_step, 0)
-    sizes = sorted(set(slot_w[have].tolist()))
-    bucket = np.full((N,), -1, np.int32)
-    index = np.full((N,), -1, np.int32)
-    offset = np.zeros((N,), np.int64)
-    shapes, total = [], 0
-    for b, sw in enumerate(sizes):
-        mine = np.flatnonzero(have & (slot_w == sw))
-        bucket[mine], index[mine] = b, np.arange(len(mine))
-        offset[mine] = total + np.arange(len(mine), dtype=np.int64) * (h * sw * 3)
-        shapes.append((len(mine), h, int(sw), 3))
-        total += len(mine) * h * sw * 3
+    slot_w, offset, bucket, index, shapes, total = slot_layout(have, widths, h, width_step)
     rows = np.zeros((int(have.sum()), ROW_WORDS), np.int64)
     for r, k in enumerate(np.flatnonzero(have).tolist()):
         rows[r] = (image[k], offset[k], slot_w[k], widths[k]) + coefs[k] + (0,)

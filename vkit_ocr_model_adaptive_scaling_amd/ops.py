@@ -3070,6 +3070,90 @@ def quad_strips_u8(arena: torch.Tensor, sources, rows, h: int, out_bytes: int, v
     return out
 
 
+def _spine_table(who: str, table, n: int, knots_total: int, h: int, device, validate: bool):
+    """The 1-D int64 table of ``spines.spine_table`` (host or device, as ``_pack_table`` takes tables) on the device, and its
+    host rows and knots (None for a trusted device table)."""
+    import numpy as np
+    from .inferencing.spines import KNOT_WORDS, spine_table
+    from .inferencing.strips import HEIGHT_MAX, ROW_WORDS
+    if h != int(h) or not 1 <= int(h) <= HEIGHT_MAX:
+        raise ValueError(f'{who}: h must be an integer in [1, {HEIGHT_MAX}], got {h}')
+    n, knots_total, h = int(n), int(knots_total), int(h)
+    if n < 0 or knots_total < 0:
+        raise ValueError(f'{who}: n and knots_total must be at or above 0, got {n}, {knots_total}')
+    d_table, h_table = _pack_table(who, 'table', table, (None,), 'int64', device, validate)
+    words = (ROW_WORDS + 1) * n + 1 + KNOT_WORDS * knots_total
+    if int(d_table.numel()) != words:
+        raise ValueError(f'{who}: a table of {n} rows and {knots_total} knots holds {words} words, got {int(d_table.numel())}')
+    if h_table is None:
+        return d_table, None, None
+    h_rows = h_table[:n * ROW_WORDS].reshape(n, ROW_WORDS)
+    h_knots = h_table[(ROW_WORDS + 1) * n + 1:].reshape(knots_total, KNOT_WORDS)
+    if not np.array_equal(h_table, spine_table(h_rows, h_knots, h)):
+        raise ValueError(f'{who}: tile_start does not give each row its tiles')
+    return d_table, h_rows, h_knots
+
+
+def spine_columns(table, n: int, knots_total: int, h: int, columns: int, validate: bool = True) -> torch.Tensor:
+    """The column records of the spine rows of a table (``spines.spine_table``), as the first launch of ``spine_strips_u8``
+    writes them: a (columns, 6) int64 device tensor, row r's records at ``col_start .. col_start + w - 1``, every record no
+    row owns ``INT64_MIN``.  Equal to ``spines.spine_columns_host`` word for word.  For the tests."""
+    if not isinstance(table, torch.Tensor) or not table.is_cuda:
+        raise ValueError('spine_columns: table must be a device tensor')
+    d_table, h_rows, h_knots = _spine_table('spine_columns', table, n, knots_total, h, table.device, validate)
+    n, columns = int(n), int(columns)
+    if not n <= columns < 1 << 40:
+        raise ValueError(f'spine_columns: columns must be in [n, 2^40), got {columns}')
+    if h_rows is not None and len(h_rows) and (h_rows[:, 6].min() < 0 or (h_rows[:, 6] + h_rows[:, 3]).max() > columns):
+        raise ValueError(f'spine_columns: a row\'s columns leave the {columns} records')
+    out = torch.full((columns, 6), -(1 << 63), dtype=torch.int64, device=d_table.device)
+    if n:
+        check(lib.vkas_spine_columns(_p(d_table), n, int(knots_total), int(h), _p(out), columns, _stream()), 'spine_columns')
+    return out
+
+
+def spine_strips_u8(arena: torch.Tensor, sources, table, n: int, knots_total: int, h: int, out_bytes: int,
+                    validate: bool = True) -> torch.Tensor:
+    """Cuts curved text lines out of the images of an arena into strips of height ``h`` along their spines, two launches on
+    one stream (csrc/spines.hip; the rule, the table layout and the oracle: inferencing/spines.py).  ``arena`` and ``sources``
+    as in ``quad_strips_u8``; ``table``: the 1-D int64 table ``spines.spine_table`` lays out - ``n`` spine rows, ``tile_start``,
+    ``knots_total`` knot records.  Host tables are always checked (``check_spine_rows``), device tables when ``validate`` - a
+    synchronisation.  Returns the 1-D uint8 output of ``out_bytes`` bytes: every byte of every slot is written, a byte outside
+    the slots keeps what the allocation held.  Allocates only its output and the workspace of the column records -
+    ``out_bytes // (3*h)`` of them, which disjoint slots inside the output cannot exceed -; with device tables and
+    ``validate=False`` it never synchronises, so it can be captured into a HIP graph."""
+    from .inferencing.spines import check_spine_rows
+    if arena.dim() != 1 or arena.dtype != torch.uint8:
+        raise ValueError(f'spine_strips_u8: arena must be a 1-D uint8 tensor, got {arena.dtype} {tuple(arena.shape)}')
+    if arena.numel() < 1 or not arena.is_contiguous():
+        raise ValueError('spine_strips_u8: arena must be contiguous and not empty')
+    out_bytes = int(out_bytes)
+    if not 0 <= out_bytes < 1 << 40:
+        raise ValueError(f'spine_strips_u8: out_bytes must be in [0, 2^40), got {out_bytes}')
+    d_sources, h_sources = _pack_table('spine_strips_u8', 'sources', sources, (None, 4), 'int64', arena.device, validate)
+    if int(d_sources.shape[0]) < 1:
+        raise ValueError('spine_strips_u8: no sources')
+    d_table, h_rows, h_knots = _spine_table('spine_strips_u8', table, n, knots_total, h, arena.device, validate)
+    n, knots_total, h = int(n), int(knots_total), int(h)
+    columns = out_bytes // (3 * h)
+    if h_rows is not None:
+        if h_sources is None:
+            raise ValueError('spine_strips_u8: a host table needs a host source table (or validate=True) to be checked against')
+        if ((h_sources[:, 0] < 0) | (h_sources[:, 0] + 3 * h_sources[:, 1] * h_sources[:, 2] > int(arena.numel()))).any():
+            raise ValueError(f'spine_strips_u8: a source leaves the arena of {int(arena.numel())} bytes')
+        check_spine_rows(h_rows, h_knots, h_sources, h, out_bytes, columns)
+    if columns < n:
+        raise ValueError(f'spine_strips_u8: an output of {out_bytes} bytes has no room for the slots of {n} rows')
+    _require_cuda(arena)
+    out = torch.empty((out_bytes,), dtype=torch.uint8, device=arena.device)
+    if n:
+        ws = torch.empty((max(columns, 1) * 6,), dtype=torch.int64, device=arena.device)
+        check(lib.vkas_spine_strips_u8(_p(arena), int(arena.numel()), _p(d_sources), int(d_sources.shape[0]), _p(d_table), n,
+                                       knots_total, h, _p(ws), int(ws.numel()) * 8, _p(out), out_bytes, _stream()),
+              'spine_strips_u8')
+    return out
+
+
 def crop_warp(arena: torch.Tensor, sources, rows, size: Tuple[int, int], validate: bool = True,
               out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Training crops of annotated pages: one affine map and one photometric jitter per output image, in one launch
