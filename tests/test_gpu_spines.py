@@ -4,8 +4,8 @@ word (``spine_columns_host``), strips byte for byte (``spine_strips_host``).  An
 odd row bytes, 1 x 1); the quarter circle and tight arcs at ``log2n`` 0 .. 3, straight lines of w = 1, 63, 64, 65 and 300 columns,
 a line of two knots, hand-made rows with a knot at every column and with 300 knots, lines partly and wholly outside their
 image; h = 1, 16, 17, 32; n = 0; slots at odd addresses with canary bytes between them and around the output, guard words
-around the workspace, canaries around the arena; hostile rows, knots and tile tables against the rule's defined answer; the
-argument errors; eager = replayed graph = second eager run."""
+around the workspace, canaries around the arena; hostile rows, knots and tile tables against the rule's defined answer; more
+tiles than either kernel's grid takes in one trip; the argument errors; eager = replayed graph = second eager run."""
 import ctypes
 
 import numpy as np
@@ -202,6 +202,41 @@ def test_c_abi_equals_the_oracle_between_canaries(h):
     assert dev.run(rows, knots, h) == 0
     dev.check_columns(rows, knots, h, ('spaced', h))
     dev.check(answer(S, rows, knots, h, size), ('spaced', h))
+
+
+def test_tiles_beyond_both_grids_take_a_second_trip():
+    """More tiles than the columns kernel has waves (8192) and four times what the strips kernel has workgroups (2048): 65
+    hand-made rows of h = 1 and two knots in slots of 8192 pixels, 128 tiles each.  Narrow rows, and wide ones at the end:
+    the last row's columns are all written on a wave's second trip, its pixels on a workgroup's fifth."""
+    ops, _, S, _ = mods()
+    h, slot_w, n = 1, 8192, 65
+    widths = [3 + k % 40 for k in range(n - 3)] + [5000, 8191, 8192]
+    rows, knots, col_at = [], [], 0
+    for k, w in enumerate(widths):
+        angle, length = 0.3 * k, min(0.9 * w, 300.0)
+        d = np.array([np.sin(angle), np.cos(angle)])                       # along the line, (y, x)
+        c = np.array([210.0, 215.0])[None] + np.array([[-0.5], [0.5]]) * length * d[None]
+        v = np.array([d[1], -d[0]]) * (0.9 if k % 2 else 2.0)              # down: 0.9 or 2 source pixels per strip row
+        t = np.concatenate([[[0], [w]], np.rint(65536 * (c - 0.5)), np.tile(np.rint(65536 * v), (2, 1)), [[0], [0]]], axis=1).astype(np.int64)
+        assert S.knot_status(t, h) == 0
+        rows.append([0, 0, slot_w, w, 2 * k, 2, col_at, S.knots_log2n(t, h), 0, 0, 0, 0])
+        knots.append(t)
+        col_at += w
+    rows, knots = np.array(rows, np.int64), np.concatenate(knots)
+    rows, size, columns = spaced(rows, h, col_at)
+    S.check_spine_rows(rows, knots, np.array([[0, 420, 430, 0], [0, 33, 47, 0], [0, 1, 1, 0]]), h, size, columns)
+    table = S.spine_table(rows, knots, h)
+    assert table[13 * n] == 128 * n > 8192 and table[12 * n + n - 1] == 8192 and {0, 1} <= set(rows[:, 7].tolist())
+    want = answer(S, rows, knots, h, size)
+    last = rows[-1].tolist()
+    assert want[last[1]:last[1] + 3 * slot_w].reshape(-1, 3).any(axis=1).mean() > 0.9
+    dev = Device(size, columns)
+    assert dev.run(rows, knots, h) == 0
+    dev.check_columns(rows, knots, h, 'second trip')
+    dev.check(want, 'second trip')
+    cols = ops.spine_columns(dev.d_table, n, len(knots), h, columns, validate=False).cpu().numpy()
+    for r in rows.tolist():
+        assert np.array_equal(cols[r[6]:r[6] + r[3]], S.spine_columns_host(knots[r[4]:r[4] + r[5]], r[3], h)), r[:8]
 
 
 def test_ops_equal_the_oracle_and_n_0():

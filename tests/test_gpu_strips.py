@@ -3,7 +3,7 @@ inferencing/strips.py::quad_strips_host on the MI355X, byte for byte: an arena o
 bytes, 1 x 1); exact cuts, slanted quads shrunk by 1, 3 and 10, quads partly and wholly outside their image, w = 1, slot_w
 and slot_w - 1, several bucket widths; h = 1, 8, 32, 37; n = 0, 1, 65, 300; rows in scrambled order; slots at odd addresses
 with canary bytes between them and around the output and the arena; every kind of invalid row next to valid neighbours;
-hostile tile tables; the argument errors; eager = replayed graph = second eager run."""
+hostile tile tables; more tiles than the grid has workgroups; the argument errors; eager = replayed graph = second eager run."""
 import ctypes
 
 import numpy as np
@@ -195,6 +195,36 @@ def test_invalid_rows_next_to_valid_neighbours():
         full = host_bytes(S, valid, h, size)
         assert ((got == full) | (got == CANARY)).all(), name  # a byte is the rule's or untouched
         dev.check(got, name)
+
+
+def test_tiles_beyond_the_grid_take_a_second_trip():
+    """More tiles than the grid has workgroups (2048): 18 hand-made rows of h = 1 in slots of 8192 pixels, 128 tiles each, so
+    the rows from the 17th on are cut wholly on a workgroup's second trip over the tiles - narrow rows, and at the end wide
+    ones along and across the source's rows, whose tiles carry picture bytes and the zeros beyond w."""
+    _, _, S, _ = mods()
+    h, slot_w = 1, 8192
+    widths = [5 + 3 * k for k in range(14)] + [8192, 4100, 5000, 8191]
+    rows = []
+    for k, w in enumerate(widths):
+        src = k % 2
+        Hs, Ws = IMAGES[src].shape[:2]
+        along, across = 65536 * (Ws - 1) // w, 65536 * (Hs - 1) // w      # the diagonal of the image in w steps
+        if k == len(widths) - 2:                                             # one wide row runs down the image: lanes along i
+            rows.append([src, 0, slot_w, w, 0, 65536 * (Ws // 2), 65536, 65536 * (Hs - 1) // w, 0, 7, 0, 0])
+        else:
+            rows.append([src, 0, slot_w, w, 65536, 0, 65536 if k % 3 else 3 * 65536, across, 0, along, 0 if k % 3 else 2, 0])
+    rows, size = spaced(np.array(rows, np.int64), h)
+    sources = mods()[0].image_arena(IMAGES, torch.device('cuda'))[1]
+    S.check_strip_rows(rows, sources, h, size)
+    table = S.strip_table(rows, h)
+    assert table[-1] == 128 * len(rows) > 2048 and table[12 * len(rows) + 16] == 2048
+    assert (np.abs(rows[:, 9]) < np.abs(rows[:, 7])).any() and {0, 2} <= set(rows[:, 10].tolist())
+    want = host_bytes(S, rows, h, size)
+    for r in rows[-3:].tolist():  # the second trip writes picture bytes, and zeros beyond w in the narrower row
+        assert want[r[1]:r[1] + 3 * r[3]].any() and not want[r[1] + 3 * r[3]:r[1] + 3 * slot_w].any()
+    dev = Device(size)
+    assert dev.run(rows, h) == 0
+    dev.check(want, 'second trip')
 
 
 def test_argument_errors_launch_nothing():

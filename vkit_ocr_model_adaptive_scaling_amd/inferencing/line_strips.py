@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from .evaluation import result_quads
-from .spines import SpineStrips, check_spine_rows, spine_rows, spine_strips_from_layout, spine_table
+from .spines import SpineStrips, check_spine_rows, spine_rows, spine_table
 from .strips import QuadStrips, bucket_views, check_strip_rows, strip_rows, strip_table
 
 
@@ -41,6 +41,30 @@ def _arena(images, device):
     return ops.image_arena(mats, device)
 
 
+def _cut(cls, who: str, what: str, rule, check, table, launch, images, items_per_image: Sequence, height, width_max, width_step,
+         margin, device):
+    """The body of ``quad_strips`` and ``spine_strips``: the layout by ``rule``; then, unless it has no rows, the arena and
+    its bounds, ``check(layout, sources, h)`` on the host (the launch needs no copy back), the one upload of ``table(layout,
+    h)`` and ``launch(layout, h, arena, d_sources, d_table)``.  -> ``cls`` with device buckets."""
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise ValueError(f'{who} runs on the GPU, got device {device} (host route: {who}_host)')
+    layout = rule(items_per_image, height, width_max, width_step, margin)
+    h = int(height)
+    if len(layout.rows):
+        arena, sources, d_sources = _arena(images, device)
+        if len(sources) != len(items_per_image):
+            raise ValueError(f'{len(items_per_image)} {what} for {len(sources)} images')
+        if ((sources[:, 0] < 0) | (sources[:, 0] + 3 * sources[:, 1] * sources[:, 2] > int(arena.numel()))).any():
+            raise ValueError(f'{who}: a source leaves the arena of {int(arena.numel())} bytes')
+        check(layout, sources, h)
+        d_table = torch.from_numpy(table(layout, h)).to(arena.device, non_blocking=True)
+        out = launch(layout, h, arena, d_sources, d_table)
+    else:
+        out = torch.empty((0,), dtype=torch.uint8, device=device)
+    return cls.of(layout, bucket_views(out, layout.bucket_shapes), h)
+
+
 def quad_strips(images, quads_per_image: Sequence, height: int = 32, width_max: int = 2048, width_step: int = 64,
                 margin: float = 0.125, device='cuda') -> QuadStrips:
     """Cuts the quadrilaterals ``quads_per_image[s]`` ((n_s, 4, 2) ``(y, x)`` pixels) out of image s, turns them upright and
@@ -48,24 +72,10 @@ def quad_strips(images, quads_per_image: Sequence, height: int = 32, width_max: 
     upload, one launch, nothing read back - the per-quad arrays come from the host rule (``strip_rows``).  Equal to
     ``quad_strips_host`` byte for byte, with device buckets."""
     from .. import ops
-    device = torch.device(device)
-    if device.type != 'cuda':
-        raise ValueError(f'quad_strips runs on the GPU, got device {device} (host route: quad_strips_host)')
-    layout = strip_rows(quads_per_image, height, width_max, width_step, margin)
-    h = int(height)
-    if len(layout.rows):
-        arena, sources, d_sources = _arena(images, device)
-        if len(sources) != len(quads_per_image):
-            raise ValueError(f'{len(quads_per_image)} quad arrays for {len(sources)} images')
-        if ((sources[:, 0] < 0) | (sources[:, 0] + 3 * sources[:, 1] * sources[:, 2] > int(arena.numel()))).any():
-            raise ValueError(f'quad_strips: a source leaves the arena of {int(arena.numel())} bytes')
-        check_strip_rows(layout.rows, sources, h, layout.out_bytes)  # on the host: the launch needs no copy back
-        d_table = torch.from_numpy(strip_table(layout.rows, h)).to(arena.device, non_blocking=True)
-        out = ops.quad_strips_u8(arena, d_sources, d_table, h, layout.out_bytes, validate=False)
-    else:
-        out = torch.empty((0,), dtype=torch.uint8, device=device)
-    return QuadStrips(bucket_views(out, layout.bucket_shapes), layout.image, layout.status, layout.squeezed, layout.widths,
-                      layout.bucket, layout.index, layout.rows, h)
+    return _cut(QuadStrips, 'quad_strips', 'quad arrays', strip_rows,
+                lambda l, sources, h: check_strip_rows(l.rows, sources, h, l.out_bytes), lambda l, h: strip_table(l.rows, h),
+                lambda l, h, arena, d_sources, d_table: ops.quad_strips_u8(arena, d_sources, d_table, h, l.out_bytes, validate=False),
+                images, quads_per_image, height, width_max, width_step, margin, device)
 
 
 def spine_strips(images, lines_per_image: Sequence, height: int = 32, width_max: int = 2048, width_step: int = 64,
@@ -75,24 +85,12 @@ def spine_strips(images, lines_per_image: Sequence, height: int = 32, width_max:
     ``images`` as ``quad_strips`` takes them, one table upload, two launches, nothing read back - the per-line arrays and
     the knots come from the host rule (``spine_rows``).  Equal to ``spine_strips_host`` byte for byte, with device buckets."""
     from .. import ops
-    device = torch.device(device)
-    if device.type != 'cuda':
-        raise ValueError(f'spine_strips runs on the GPU, got device {device} (host route: spine_strips_host)')
-    layout = spine_rows(lines_per_image, height, width_max, width_step, margin)
-    h = int(height)
-    if len(layout.rows):
-        arena, sources, d_sources = _arena(images, device)
-        if len(sources) != len(lines_per_image):
-            raise ValueError(f'{len(lines_per_image)} line lists for {len(sources)} images')
-        if ((sources[:, 0] < 0) | (sources[:, 0] + 3 * sources[:, 1] * sources[:, 2] > int(arena.numel()))).any():
-            raise ValueError(f'spine_strips: a source leaves the arena of {int(arena.numel())} bytes')
-        check_spine_rows(layout.rows, layout.knots, sources, h, layout.out_bytes, layout.columns)  # on the host
-        d_table = torch.from_numpy(spine_table(layout.rows, layout.knots, h)).to(arena.device, non_blocking=True)
-        out = ops.spine_strips_u8(arena, d_sources, d_table, len(layout.rows), len(layout.knots), h, layout.out_bytes,
-                                  validate=False)
-    else:
-        out = torch.empty((0,), dtype=torch.uint8, device=device)
-    return spine_strips_from_layout(layout, bucket_views(out, layout.bucket_shapes), h)
+    return _cut(SpineStrips, 'spine_strips', 'line lists', spine_rows,
+                lambda l, sources, h: check_spine_rows(l.rows, l.knots, sources, h, l.out_bytes, l.columns),
+                lambda l, h: spine_table(l.rows, l.knots, h),
+                lambda l, h, arena, d_sources, d_table: ops.spine_strips_u8(arena, d_sources, d_table, len(l.rows), len(l.knots), h,
+                                                                            l.out_bytes, validate=False),
+                images, lines_per_image, height, width_max, width_step, margin, device)
 
 
 def result_lines(result) -> list:

@@ -48,14 +48,14 @@ are ``knots`` records from ``knot_start`` of the knot table, its column records 
 workspace (``col_start`` is the exclusive scan of ``w``).  The device reads ONE table (``spine_table``): the rows, then
 ``tile_start`` as in ``strip_table``, then the knot records."""
 import math
-from typing import List, Sequence, Tuple
+from typing import Sequence
 
 import attrs
 import numpy as np
 
 from .packing import SIDE_MAX, WARP_A_MAX, WARP_M_MAX, _warp_samples
-from .strips import (HEIGHT_MAX, ROW_WORDS, SOURCE_SIDE_MAX, TILE_H, TILE_W, bucket_views, log2n_of, slot_layout,
-                     strip_params)
+from .strips import (ROW_WORDS, QuadStrips, StripLayout, bucket_views, check_slot_rows, int_rows, log2n_of, slot_layout,
+                     strip_params, tile_starts)
 
 KNOT_WORDS = 6
 COLUMN_WORDS = 6
@@ -238,19 +238,10 @@ def spine_polygon(knots) -> np.ndarray:
 
 
 @attrs.define
-class SpineLayout:
-    """``spine_rows``: K spine rows in input order of the lines that have a strip, their knots, and per line (N of them, image
-    after image) what became of it - the fields of ``StripLayout``."""
-    rows: np.ndarray       # (K, 12) int64 spine rows
+class SpineLayout(StripLayout):
+    """``spine_rows``: ``StripLayout`` with K spine rows in input order of the lines that have a strip, per line (N of them,
+    image after image) what became of it, and the rows' knots."""
     knots: np.ndarray      # (knots_total, 6) int64
-    image: np.ndarray      # (N,) int32
-    status: np.ndarray     # (N,) int32: 0, or 1 / 2 for a line without a strip
-    squeezed: np.ndarray   # (N,) bool
-    widths: np.ndarray     # (N,) int32: w, 0 without a strip
-    bucket: np.ndarray     # (N,) int32
-    index: np.ndarray      # (N,) int32
-    bucket_shapes: List[Tuple[int, int, int, int]]
-    out_bytes: int
     columns: int           # the sum of w: the column records of the workspace
 
 
@@ -274,94 +265,56 @@ def spine_rows(lines_per_image: Sequence, h: int = 32, width_max: int = 2048, wi
         rows[r, :8] = (image[k], offset[k], slot_w[k], widths[k], knot_at, len(knots[k]), col_at, log2n[k])
         knot_at, col_at = knot_at + len(knots[k]), col_at + int(widths[k])
     table = np.concatenate([knots[k] for k in np.flatnonzero(have).tolist()] + [np.zeros((0, KNOT_WORDS), np.int64)])
-    return SpineLayout(rows, np.ascontiguousarray(table), image, status, squeezed, widths, bucket, index, shapes, total, col_at)
+    return SpineLayout(rows, image, status, squeezed, widths, bucket, index, shapes, total, np.ascontiguousarray(table), col_at)
 
 
 def check_spine_rows(rows, knots, sources, h: int, out_bytes: int, columns: int) -> np.ndarray:
     """Validates a (K, 12) spine table against its (T, 6) knot table, the (S, 4) source table, the height, the output size and
-    a workspace of ``columns`` records - integer tables, ``src`` in range and its source's sides in 1..32768, ``1 <= w <=
-    slot_w <= 8192``, ``log2n`` in 0..3, ``knots >= 2`` and ``knot_start + knots`` inside the knot table, every row's ``q``
-    strictly increasing from 0 to ``w``, its columns inside the workspace and disjoint from the other rows', every slot inside
-    the output and the slots pairwise disjoint - and returns the rows as contiguous int64.  Raises ValueError."""
-    r, t = np.asarray(rows), np.asarray(knots)
-    if r.ndim != 2 or r.shape[1] != ROW_WORDS or not np.issubdtype(r.dtype, np.integer):
-        raise ValueError(f'spines: rows must be a (K, {ROW_WORDS}) integer table, got {r.dtype} {r.shape}')
+    a workspace of ``columns`` records - ``strips.check_slot_rows``, an integer knot table, ``log2n`` in 0..3, ``knots >= 2``
+    and ``knot_start + knots`` inside the knot table, every row's ``q`` strictly increasing from 0 to ``w``, its columns inside
+    the workspace and disjoint from the other rows' - and returns the rows as contiguous int64.  Raises ValueError."""
+    r, t = int_rows('spines', rows), np.asarray(knots)
     if t.ndim != 2 or t.shape[1] != KNOT_WORDS or not np.issubdtype(t.dtype, np.integer):
         raise ValueError(f'spines: knots must be a (T, {KNOT_WORDS}) integer table, got {t.dtype} {t.shape}')
-    r, t = np.ascontiguousarray(r.astype(np.int64)), t.astype(np.int64)
-    s = np.asarray(sources)
-    if s.ndim != 2 or s.shape[1] != 4 or not np.issubdtype(s.dtype, np.integer):
-        raise ValueError(f'spines: sources must be an (S, 4) integer table, got {s.dtype} {s.shape}')
-    h, out_bytes, columns = int(h), int(out_bytes), int(columns)
-    if not 1 <= h <= HEIGHT_MAX:
-        raise ValueError(f'spines: height must be in [1, {HEIGHT_MAX}], got {h}')
-    if ((s[:, 1:3] < 1) | (s[:, 1:3] > SOURCE_SIDE_MAX)).any() or (s[:, 0] < 0).any():
-        raise ValueError(f'spines: source sides must be in [1, {SOURCE_SIDE_MAX}] and offsets at or above 0')
-    if ((r[:, 0] < 0) | (r[:, 0] >= len(s))).any():
-        raise ValueError(f'spines: a row names a source outside 0..{len(s) - 1}')
-    if ((r[:, 3] < 1) | (r[:, 3] > r[:, 2]) | (r[:, 2] > SIDE_MAX)).any():
-        raise ValueError(f'spines: every row needs 1 <= w <= slot_w <= {SIDE_MAX}')
-    if ((r[:, 7] < 0) | (r[:, 7] > 3)).any():
-        raise ValueError('spines: log2n must be in [0, 3]')
-    if ((r[:, 4] < 0) | (r[:, 5] < 2) | (r[:, 4] > len(t)) | (r[:, 5] > len(t) - r[:, 4])).any():
-        raise ValueError(f'spines: a row needs at least 2 knots inside the knot table of {len(t)} records')
-    for _, _, _, w, at, count, *_ in r.tolist():
-        q = t[at:at + count, 0]
-        if q[0] != 0 or q[-1] != w or (np.diff(q) <= 0).any():
-            raise ValueError('spines: the knot columns of a row must rise strictly from 0 to w')
-    first, last = r[:, 6], r[:, 6] + r[:, 3]
-    if ((first < 0) | (last > columns)).any():
-        raise ValueError(f'spines: a row\'s columns leave the workspace of {columns} records')
-    order = np.argsort(first, kind='stable')
-    if (last[order][:-1] > first[order][1:]).any():
-        raise ValueError('spines: two rows share column records')
-    start, end = r[:, 1], r[:, 1] + 3 * h * r[:, 2]
-    if ((start < 0) | (end > out_bytes)).any():
-        raise ValueError(f'spines: a slot leaves the output of {out_bytes} bytes')
-    order = np.argsort(start, kind='stable')
-    if (end[order][:-1] > start[order][1:]).any():
-        raise ValueError('spines: two slots overlap')
-    return r
+    t, columns = t.astype(np.int64), int(columns)
+
+    def own(r):
+        if ((r[:, 7] < 0) | (r[:, 7] > 3)).any():
+            raise ValueError('spines: log2n must be in [0, 3]')
+        if ((r[:, 4] < 0) | (r[:, 5] < 2) | (r[:, 4] > len(t)) | (r[:, 5] > len(t) - r[:, 4])).any():
+            raise ValueError(f'spines: a row needs at least 2 knots inside the knot table of {len(t)} records')
+        for _, _, _, w, at, count, *_ in r.tolist():
+            q = t[at:at + count, 0]
+            if q[0] != 0 or q[-1] != w or (np.diff(q) <= 0).any():
+                raise ValueError('spines: the knot columns of a row must rise strictly from 0 to w')
+        first, last = r[:, 6], r[:, 6] + r[:, 3]
+        if ((first < 0) | (last > columns)).any():
+            raise ValueError(f'spines: a row\'s columns leave the workspace of {columns} records')
+        order = np.argsort(first, kind='stable')
+        if (last[order][:-1] > first[order][1:]).any():
+            raise ValueError('spines: two rows share column records')
+    return check_slot_rows('spines', r, sources, h, out_bytes, own)
 
 
 def spine_table(rows, knots, h: int) -> np.ndarray:
-    """What the device reads (csrc/spines.hip): the (K, 12) rows flattened, then ``tile_start``, K + 1 words as in
-    ``strip_table`` (tiles of 16 x 64 pixels), then the (T, 6) knot records flattened."""
+    """What the device reads (csrc/spines.hip): the (K, 12) rows flattened, then ``strips.tile_starts``, then the (T, 6) knot
+    records flattened."""
     r = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, ROW_WORDS))
     t = np.ascontiguousarray(np.asarray(knots, dtype=np.int64).reshape(-1, KNOT_WORDS))
-    tiles = -(-int(h) // TILE_H) * (-(-np.clip(r[:, 2], 0, SIDE_MAX) // TILE_W))
-    return np.concatenate([r.reshape(-1), [0], np.cumsum(tiles), t.reshape(-1)]).astype(np.int64)
+    return np.concatenate([r.reshape(-1), tile_starts(r[:, 2], h), t.reshape(-1)])
 
 
 @attrs.define
-class SpineStrips:
-    """The strips of N lines (image after image, each image's lines in input order): the fields of ``QuadStrips`` with spine
-    rows, and the knot table.  ``buckets`` are views of one allocation: device tensors from ``inferencing.spine_strips``,
-    numpy arrays from ``spine_strips_host``."""
-    buckets: list
-    image: np.ndarray      # (N,) int32
-    status: np.ndarray     # (N,) int32: 0, 1 (degenerate line) or 2 (knots out of range)
-    squeezed: np.ndarray   # (N,) bool
-    widths: np.ndarray     # (N,) int32: w; 0 without a strip
-    bucket: np.ndarray     # (N,) int32; -1 without a strip
-    index: np.ndarray      # (N,) int32; -1 without a strip
-    rows: np.ndarray       # (K, 12) int64 spine rows of the lines with status 0, in input order
-    height: int
+class SpineStrips(QuadStrips):
+    """The strips of N lines (image after image, each image's lines in input order): ``QuadStrips`` with spine rows - status 1
+    is a degenerate line, 2 knots out of range -, and the knot table.  ``buckets`` are views of one allocation: device tensors
+    from ``inferencing.spine_strips``, numpy arrays from ``spine_strips_host``."""
     knots: np.ndarray      # (T, 6) int64: the knot table the rows point into
-
-    def _row(self, k: int) -> np.ndarray:
-        if self.status[k] != 0:
-            raise ValueError(f'line {k} has no strip (status {int(self.status[k])})')
-        return self.rows[int(np.count_nonzero(self.status[:k] == 0))]
+    _item = 'line'
 
     def _knots(self, k: int) -> np.ndarray:
         row = self._row(k)
         return self.knots[int(row[4]):int(row[4] + row[5])]
-
-    def strip(self, k: int):
-        """The (h, w, 3) view of line k's strip (without the slot's zero columns)."""
-        self._row(k)
-        return self.buckets[int(self.bucket[k])][int(self.index[k])][:, :int(self.widths[k])]
 
     def remap(self, k: int, points) -> np.ndarray:
         """(..., 2) (y, x) positions in line k's strip (pixel k covers ``[k, k + 1)``) -> float64 positions in its image,
@@ -384,11 +337,6 @@ class SpineStrips:
         return np.stack([t[:, 1:3] / 65536 + 0.5, t[:, 3:5] / 65536], axis=1)
 
 
-def spine_strips_from_layout(layout: SpineLayout, buckets: list, h: int) -> SpineStrips:
-    return SpineStrips(buckets, layout.image, layout.status, layout.squeezed, layout.widths, layout.bucket, layout.index,
-                       layout.rows, h, layout.knots)
-
-
 def spine_bytes_host(images: Sequence[np.ndarray], rows, knots, h: int, out: np.ndarray) -> np.ndarray:
     """Writes the slots of valid spine rows into the 1-D uint8 ``out`` (in place): each slot its strip and zeros beyond w."""
     for src, offset, slot_w, w, at, count, _, log2n, *_ in np.asarray(rows, dtype=np.int64).reshape(-1, ROW_WORDS).tolist():
@@ -407,4 +355,4 @@ def spine_strips_host(images: Sequence[np.ndarray], lines_per_image: Sequence, h
     layout = spine_rows(lines_per_image, height, width_max, width_step, margin)
     h = int(height)
     out = spine_bytes_host(images, layout.rows, layout.knots, h, np.zeros((layout.out_bytes,), np.uint8))
-    return spine_strips_from_layout(layout, bucket_views(out, layout.bucket_shapes), h)
+    return SpineStrips.of(layout, bucket_views(out, layout.bucket_shapes), h)

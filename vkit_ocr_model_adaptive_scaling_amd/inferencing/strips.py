@@ -42,7 +42,7 @@ from .packing import SIDE_MAX, WARP_A_MAX, WARP_M_MAX, remap_polygons_affine, wa
 
 ROW_WORDS = 12
 HEIGHT_MAX = 256
-TILE_H, TILE_W = 16, 64     # csrc/strips.hip: the pixels of one workgroup's tile
+TILE_H, TILE_W = 16, 64     # csrc/strip_tiles.h: the pixels of one workgroup's tile
 SOURCE_SIDE_MAX = 32768
 
 
@@ -150,46 +150,63 @@ def strip_rows(quads_per_image: Sequence, h: int = 32, width_max: int = 2048, wi
     return StripLayout(rows, image, status, squeezed, widths, bucket, index, shapes, int(total))
 
 
-def check_strip_rows(rows, sources, h: int, out_bytes: int) -> np.ndarray:
-    """Validates a (K, 12) strip table against the (S, 4) source table, the height and the output size - integer rows,
-    ``src`` in range and its source's sides in 1..32768, ``1 <= w <= slot_w <= 8192``, the coefficients within the warp
-    bounds, ``log2n`` in 0..3, every slot inside the output and the slots pairwise disjoint - and returns it as contiguous
-    int64.  Raises ValueError."""
+def int_rows(who: str, rows) -> np.ndarray:
+    """A (K, 12) integer row table as contiguous int64.  Raises ValueError."""
     r = np.asarray(rows)
     if r.ndim != 2 or r.shape[1] != ROW_WORDS or not np.issubdtype(r.dtype, np.integer):
-        raise ValueError(f'strips: rows must be a (K, {ROW_WORDS}) integer table, got {r.dtype} {r.shape}')
-    r = np.ascontiguousarray(r.astype(np.int64))
+        raise ValueError(f'{who}: rows must be a (K, {ROW_WORDS}) integer table, got {r.dtype} {r.shape}')
+    return np.ascontiguousarray(r.astype(np.int64))
+
+
+def check_slot_rows(who: str, r: np.ndarray, sources, h: int, out_bytes: int, own) -> np.ndarray:
+    """What strip rows and spine rows (``r`` from ``int_rows``) are checked for alike, their words 0 .. 3 meaning the same: the
+    (S, 4) integer source table with sides in 1..32768, the height, ``src`` in range, ``1 <= w <= slot_w <= 8192``; then
+    ``own(r)``, the checks of the rows' other words; then every slot inside the output and the slots pairwise disjoint.
+    ``who`` begins the messages.  Returns ``r``; raises ValueError."""
     s = np.asarray(sources)
     if s.ndim != 2 or s.shape[1] != 4 or not np.issubdtype(s.dtype, np.integer):
-        raise ValueError(f'strips: sources must be an (S, 4) integer table, got {s.dtype} {s.shape}')
+        raise ValueError(f'{who}: sources must be an (S, 4) integer table, got {s.dtype} {s.shape}')
     h, out_bytes = int(h), int(out_bytes)
     if not 1 <= h <= HEIGHT_MAX:
-        raise ValueError(f'strips: height must be in [1, {HEIGHT_MAX}], got {h}')
+        raise ValueError(f'{who}: height must be in [1, {HEIGHT_MAX}], got {h}')
     if ((s[:, 1:3] < 1) | (s[:, 1:3] > SOURCE_SIDE_MAX)).any() or (s[:, 0] < 0).any():
-        raise ValueError(f'strips: source sides must be in [1, {SOURCE_SIDE_MAX}] and offsets at or above 0')
+        raise ValueError(f'{who}: source sides must be in [1, {SOURCE_SIDE_MAX}] and offsets at or above 0')
     if ((r[:, 0] < 0) | (r[:, 0] >= len(s))).any():
-        raise ValueError(f'strips: a row names a source outside 0..{len(s) - 1}')
+        raise ValueError(f'{who}: a row names a source outside 0..{len(s) - 1}')
     if ((r[:, 3] < 1) | (r[:, 3] > r[:, 2]) | (r[:, 2] > SIDE_MAX)).any():
-        raise ValueError(f'strips: every row needs 1 <= w <= slot_w <= {SIDE_MAX}')
-    if (np.abs(r[:, 6:10]) > WARP_M_MAX).any() or (np.abs(r[:, 4:6]) >= WARP_A_MAX).any():
-        raise ValueError('strips: a coefficient exceeds 2^22 or an anchor reaches 2^40')
-    if ((r[:, 10] < 0) | (r[:, 10] > 3)).any():
-        raise ValueError('strips: log2n must be in [0, 3]')
+        raise ValueError(f'{who}: every row needs 1 <= w <= slot_w <= {SIDE_MAX}')
+    own(r)
     start, end = r[:, 1], r[:, 1] + 3 * h * r[:, 2]
     if ((start < 0) | (end > out_bytes)).any():
-        raise ValueError(f'strips: a slot leaves the output of {out_bytes} bytes')
+        raise ValueError(f'{who}: a slot leaves the output of {out_bytes} bytes')
     order = np.argsort(start, kind='stable')
     if (end[order][:-1] > start[order][1:]).any():
-        raise ValueError('strips: two slots overlap')
+        raise ValueError(f'{who}: two slots overlap')
     return r
 
 
+def check_strip_rows(rows, sources, h: int, out_bytes: int) -> np.ndarray:
+    """Validates a (K, 12) strip table against the (S, 4) source table, the height and the output size - ``check_slot_rows``,
+    the coefficients within the warp bounds and ``log2n`` in 0..3 - and returns it as contiguous int64.  Raises ValueError."""
+    def own(r):
+        if (np.abs(r[:, 6:10]) > WARP_M_MAX).any() or (np.abs(r[:, 4:6]) >= WARP_A_MAX).any():
+            raise ValueError('strips: a coefficient exceeds 2^22 or an anchor reaches 2^40')
+        if ((r[:, 10] < 0) | (r[:, 10] > 3)).any():
+            raise ValueError('strips: log2n must be in [0, 3]')
+    return check_slot_rows('strips', int_rows('strips', rows), sources, h, out_bytes, own)
+
+
+def tile_starts(slot_w, h: int) -> np.ndarray:
+    """``tile_start``, K + 1 int64 words for K slots: row r owns the tiles ``tile_start[r] .. tile_start[r + 1] - 1`` of 16 x 64
+    pixels, ``ceil(h/16) * ceil(slot_w/64)`` of them (csrc/strip_tiles.h)."""
+    tiles = -(-int(h) // TILE_H) * (-(-np.clip(np.asarray(slot_w, dtype=np.int64), 0, SIDE_MAX) // TILE_W))
+    return np.concatenate([[0], np.cumsum(tiles)]).astype(np.int64)
+
+
 def strip_table(rows, h: int) -> np.ndarray:
-    """What the device reads (csrc/strips.hip): the (K, 12) rows flattened, followed by ``tile_start``, K + 1 words - row r
-    owns the tiles ``tile_start[r] .. tile_start[r + 1] - 1`` of 16 x 64 pixels: ``ceil(h/16) * ceil(slot_w/64)`` of them."""
+    """What the device reads (csrc/strips.hip): the (K, 12) rows flattened, followed by ``tile_starts``."""
     r = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, ROW_WORDS))
-    tiles = -(-int(h) // TILE_H) * (-(-np.clip(r[:, 2], 0, SIDE_MAX) // TILE_W))
-    return np.concatenate([r.reshape(-1), [0], np.cumsum(tiles)]).astype(np.int64)
+    return np.concatenate([r.reshape(-1), tile_starts(r[:, 2], h)])
 
 
 @attrs.define
@@ -205,14 +222,22 @@ class QuadStrips:
     index: np.ndarray      # (N,) int32; -1 without a strip
     rows: np.ndarray       # (K, 12) int64 strip rows of the quads with status 0, in input order
     height: int
+    _item = 'quad'         # what a strip is cut from, for the messages
+
+    @classmethod
+    def of(cls, layout: StripLayout, buckets: list, h: int):
+        """The strips of a layout with their buckets; the fields a subclass adds come from the layout by name."""
+        more = {f.name: getattr(layout, f.name) for f in attrs.fields(cls)[len(attrs.fields(QuadStrips)):]}
+        return cls(buckets, layout.image, layout.status, layout.squeezed, layout.widths, layout.bucket, layout.index,
+                   layout.rows, h, **more)
 
     def _row(self, k: int) -> np.ndarray:
         if self.status[k] != 0:
-            raise ValueError(f'quad {k} has no strip (status {int(self.status[k])})')
+            raise ValueError(f'{self._item} {k} has no strip (status {int(self.status[k])})')
         return self.rows[int(np.count_nonzero(self.status[:k] == 0))]
 
     def strip(self, k: int):
-        """The (h, w, 3) view of quad k's strip (without the slot's zero columns)."""
+        """The (h, w, 3) view of strip k (without the slot's zero columns)."""
         self._row(k)
         return self.buckets[int(self.bucket[k])][int(self.index[k])][:, :int(self.widths[k])]
 
@@ -226,11 +251,6 @@ def remap_strip_points(points, row) -> np.ndarray:
     ``remap_polygons_affine`` with the destination at (0, 0)."""
     row = np.asarray(row, dtype=np.int64).reshape(ROW_WORDS)
     return remap_polygons_affine(points, np.concatenate([np.zeros((4,), np.int64), row[4:]]))
-
-
-def _strips(layout: StripLayout, buckets: list, h: int) -> QuadStrips:
-    return QuadStrips(buckets, layout.image, layout.status, layout.squeezed, layout.widths, layout.bucket, layout.index,
-                      layout.rows, h)
 
 
 def bucket_views(out, bucket_shapes) -> list:
@@ -255,4 +275,4 @@ def quad_strips_host(images: Sequence[np.ndarray], quads_per_image: Sequence, he
     for src, offset, slot_w, w, *coef in layout.rows.tolist():
         page = warp_host(images[src], [[0, 0, h, w] + coef], np.zeros((h, w, 3), np.uint8))
         out[offset:offset + h * slot_w * 3].reshape(h, slot_w, 3)[:, :w] = page
-    return _strips(layout, bucket_views(out, layout.bucket_shapes), h)
+    return QuadStrips.of(layout, bucket_views(out, layout.bucket_shapes), h)

@@ -3015,6 +3015,37 @@ def image_arena(mats, device):
     return host.to(device, non_blocking=True), table, torch.from_numpy(table).to(device, non_blocking=True)
 
 
+def _strip_height(who: str, h) -> int:
+    from .inferencing.strips import HEIGHT_MAX
+    if h != int(h) or not 1 <= int(h) <= HEIGHT_MAX:
+        raise ValueError(f'{who}: h must be an integer in [1, {HEIGHT_MAX}], got {h}')
+    return int(h)
+
+
+def _strip_args(who: str, arena: torch.Tensor, sources, h, out_bytes, validate: bool):
+    """What the strip ops take alike, checked: the arena, the height, the output size and the source table (as ``_pack_table``
+    takes tables) -> ``(h, out_bytes, device sources, host sources or None)``."""
+    if arena.dim() != 1 or arena.dtype != torch.uint8:
+        raise ValueError(f'{who}: arena must be a 1-D uint8 tensor, got {arena.dtype} {tuple(arena.shape)}')
+    if arena.numel() < 1 or not arena.is_contiguous():
+        raise ValueError(f'{who}: arena must be contiguous and not empty')
+    h, out_bytes = _strip_height(who, h), int(out_bytes)
+    if not 0 <= out_bytes < 1 << 40:
+        raise ValueError(f'{who}: out_bytes must be in [0, 2^40), got {out_bytes}')
+    d_sources, h_sources = _pack_table(who, 'sources', sources, (None, 4), 'int64', arena.device, validate)
+    if int(d_sources.shape[0]) < 1:
+        raise ValueError(f'{who}: no sources')
+    return h, out_bytes, d_sources, h_sources
+
+
+def _strip_host_sources(who: str, need: str, arena: torch.Tensor, h_sources) -> None:
+    """Before host rows are checked against their sources: these are on the host as well and stay inside the arena."""
+    if h_sources is None:
+        raise ValueError(f'{who}: {need} a host source table (or validate=True) to be checked against')
+    if ((h_sources[:, 0] < 0) | (h_sources[:, 0] + 3 * h_sources[:, 1] * h_sources[:, 2] > int(arena.numel()))).any():
+        raise ValueError(f'{who}: a source leaves the arena of {int(arena.numel())} bytes')
+
+
 def quad_strips_u8(arena: torch.Tensor, sources, rows, h: int, out_bytes: int, validate: bool = True) -> torch.Tensor:
     """Cuts text lines out of the images of an arena into upright strips of height ``h``, all in one launch (csrc/strips.hip;
     the rule, the row layout and the oracle: inferencing/strips.py).  ``arena``: a 1-D uint8 device tensor that holds the
@@ -3026,19 +3057,8 @@ def quad_strips_u8(arena: torch.Tensor, sources, rows, h: int, out_bytes: int, v
     cover the output -, a byte outside the slots keeps what the allocation held.  Allocates only its output (and the small
     table); with device tables and ``validate=False`` it never synchronises, so it can be captured into a HIP graph."""
     import numpy as np
-    from .inferencing.strips import ROW_WORDS, TILE_H, TILE_W, HEIGHT_MAX, check_strip_rows, strip_table
-    if arena.dim() != 1 or arena.dtype != torch.uint8:
-        raise ValueError(f'quad_strips_u8: arena must be a 1-D uint8 tensor, got {arena.dtype} {tuple(arena.shape)}')
-    if arena.numel() < 1 or not arena.is_contiguous():
-        raise ValueError('quad_strips_u8: arena must be contiguous and not empty')
-    if h != int(h) or not 1 <= int(h) <= HEIGHT_MAX:
-        raise ValueError(f'quad_strips_u8: h must be an integer in [1, {HEIGHT_MAX}], got {h}')
-    h, out_bytes = int(h), int(out_bytes)
-    if not 0 <= out_bytes < 1 << 40:
-        raise ValueError(f'quad_strips_u8: out_bytes must be in [0, 2^40), got {out_bytes}')
-    d_sources, h_sources = _pack_table('quad_strips_u8', 'sources', sources, (None, 4), 'int64', arena.device, validate)
-    if int(d_sources.shape[0]) < 1:
-        raise ValueError('quad_strips_u8: no sources')
+    from .inferencing.strips import ROW_WORDS, TILE_H, TILE_W, check_strip_rows, strip_table
+    h, out_bytes, d_sources, h_sources = _strip_args('quad_strips_u8', arena, sources, h, out_bytes, validate)
     flat = isinstance(rows, torch.Tensor) and rows.is_cuda and rows.dim() == 1
     if flat:
         if (int(rows.numel()) - 1) % (ROW_WORDS + 1):
@@ -3057,10 +3077,7 @@ def quad_strips_u8(arena: torch.Tensor, sources, rows, h: int, out_bytes: int, v
         else:
             d_table = torch.from_numpy(strip_table(h_rows, h)).to(arena.device, non_blocking=True)
     if h_rows is not None:
-        if h_sources is None:
-            raise ValueError('quad_strips_u8: host rows need a host source table (or validate=True) to be checked against')
-        if ((h_sources[:, 0] < 0) | (h_sources[:, 0] + 3 * h_sources[:, 1] * h_sources[:, 2] > int(arena.numel()))).any():
-            raise ValueError(f'quad_strips_u8: a source leaves the arena of {int(arena.numel())} bytes')
+        _strip_host_sources('quad_strips_u8', 'host rows need', arena, h_sources)
         check_strip_rows(h_rows, h_sources, h, out_bytes)
     _require_cuda(arena)
     out = torch.empty((out_bytes,), dtype=torch.uint8, device=arena.device)
@@ -3072,13 +3089,11 @@ def quad_strips_u8(arena: torch.Tensor, sources, rows, h: int, out_bytes: int, v
 
 def _spine_table(who: str, table, n: int, knots_total: int, h: int, device, validate: bool):
     """The 1-D int64 table of ``spines.spine_table`` (host or device, as ``_pack_table`` takes tables) on the device, and its
-    host rows and knots (None for a trusted device table)."""
+    host rows and knots (None for a trusted device table).  ``h`` is checked (``_strip_height``)."""
     import numpy as np
     from .inferencing.spines import KNOT_WORDS, spine_table
-    from .inferencing.strips import HEIGHT_MAX, ROW_WORDS
-    if h != int(h) or not 1 <= int(h) <= HEIGHT_MAX:
-        raise ValueError(f'{who}: h must be an integer in [1, {HEIGHT_MAX}], got {h}')
-    n, knots_total, h = int(n), int(knots_total), int(h)
+    from .inferencing.strips import ROW_WORDS
+    n, knots_total = int(n), int(knots_total)
     if n < 0 or knots_total < 0:
         raise ValueError(f'{who}: n and knots_total must be at or above 0, got {n}, {knots_total}')
     d_table, h_table = _pack_table(who, 'table', table, (None,), 'int64', device, validate)
@@ -3100,6 +3115,7 @@ def spine_columns(table, n: int, knots_total: int, h: int, columns: int, validat
     row owns ``INT64_MIN``.  Equal to ``spines.spine_columns_host`` word for word.  For the tests."""
     if not isinstance(table, torch.Tensor) or not table.is_cuda:
         raise ValueError('spine_columns: table must be a device tensor')
+    h = _strip_height('spine_columns', h)
     d_table, h_rows, h_knots = _spine_table('spine_columns', table, n, knots_total, h, table.device, validate)
     n, columns = int(n), int(columns)
     if not n <= columns < 1 << 40:
@@ -3108,7 +3124,7 @@ def spine_columns(table, n: int, knots_total: int, h: int, columns: int, validat
         raise ValueError(f'spine_columns: a row\'s columns leave the {columns} records')
     out = torch.full((columns, 6), -(1 << 63), dtype=torch.int64, device=d_table.device)
     if n:
-        check(lib.vkas_spine_columns(_p(d_table), n, int(knots_total), int(h), _p(out), columns, _stream()), 'spine_columns')
+        check(lib.vkas_spine_columns(_p(d_table), n, int(knots_total), h, _p(out), columns, _stream()), 'spine_columns')
     return out
 
 
@@ -3123,24 +3139,12 @@ def spine_strips_u8(arena: torch.Tensor, sources, table, n: int, knots_total: in
     ``out_bytes // (3*h)`` of them, which disjoint slots inside the output cannot exceed -; with device tables and
     ``validate=False`` it never synchronises, so it can be captured into a HIP graph."""
     from .inferencing.spines import check_spine_rows
-    if arena.dim() != 1 or arena.dtype != torch.uint8:
-        raise ValueError(f'spine_strips_u8: arena must be a 1-D uint8 tensor, got {arena.dtype} {tuple(arena.shape)}')
-    if arena.numel() < 1 or not arena.is_contiguous():
-        raise ValueError('spine_strips_u8: arena must be contiguous and not empty')
-    out_bytes = int(out_bytes)
-    if not 0 <= out_bytes < 1 << 40:
-        raise ValueError(f'spine_strips_u8: out_bytes must be in [0, 2^40), got {out_bytes}')
-    d_sources, h_sources = _pack_table('spine_strips_u8', 'sources', sources, (None, 4), 'int64', arena.device, validate)
-    if int(d_sources.shape[0]) < 1:
-        raise ValueError('spine_strips_u8: no sources')
+    h, out_bytes, d_sources, h_sources = _strip_args('spine_strips_u8', arena, sources, h, out_bytes, validate)
     d_table, h_rows, h_knots = _spine_table('spine_strips_u8', table, n, knots_total, h, arena.device, validate)
-    n, knots_total, h = int(n), int(knots_total), int(h)
+    n, knots_total = int(n), int(knots_total)
     columns = out_bytes // (3 * h)
     if h_rows is not None:
-        if h_sources is None:
-            raise ValueError('spine_strips_u8: a host table needs a host source table (or validate=True) to be checked against')
-        if ((h_sources[:, 0] < 0) | (h_sources[:, 0] + 3 * h_sources[:, 1] * h_sources[:, 2] > int(arena.numel()))).any():
-            raise ValueError(f'spine_strips_u8: a source leaves the arena of {int(arena.numel())} bytes')
+        _strip_host_sources('spine_strips_u8', 'a host table needs', arena, h_sources)
         check_spine_rows(h_rows, h_knots, h_sources, h, out_bytes, columns)
     if columns < n:
         raise ValueError(f'spine_strips_u8: an output of {out_bytes} bytes has no room for the slots of {n} rows')
