@@ -341,6 +341,47 @@ int vkas_adaptive_avgpool_fwd(const void* x, long ldx, void* y, long ldy, int B,
 int vkas_adaptive_avgpool_bwd(const void* dy, long lddy, void* dx, long lddx, int B, int H, int W, int s, int Cp,
                               int accumulate, int dtype, void* stream);
 
+/* ---- the pooled branches of the pyramid-pooling block as one set of kernels (csrc/ppm.hip): upernext.py:48-84 ----------
+ * cat (B, H, W, >= C + nb Cb):  cat[..., :C] = x,  cat[..., C + k Cb : C + (k+1) Cb] = bilinear(gelu(LN(pool_{s_k}(x) W_k^T +
+ * b_k)) -> H x W) for the nb scales s_k.  16-bit storage only (VKAS_BF16 / VKAS_F16), C and Cb multiples of 8, H and W
+ * arbitrary (H < s included); limits below.  params: 4 nb device pointers, per branch W_k (Cb, C), b_k, gamma_k, beta_k (Cb),
+ * all fp32 as the modules hold them (W_k is rounded to the storage type on load).  Pooled rows are branch-major: branch k owns
+ * rows [B cell0_k, B cell0_{k+1}) of the (B S, .) buffers, cell0_k = sum_{j<k} s_j^2, S = cell0_nb; row = B cell0_k + b s_k^2 +
+ * bi s_k + bj.  SS = sum s_k.  Three forward launches, four backward launches, no atomics, fixed summation order. */
+#define VKAS_PPM_MAX_BRANCHES 4
+#define VKAS_PPM_MAX_SCALE 16
+#define VKAS_PPM_MAX_CELLS 256 /* S */
+#define VKAS_PPM_MAX_C 2048
+#define VKAS_PPM_MAX_CB 512
+/* row groups of the two row kernels (4 rows of one branch each): the partial rows vkas_ppm_rows_bwd leaves; < 0: bad arguments */
+long vkas_ppm_row_groups(int B, int nb, const int* scales);
+/* forward 1: cat[..., :C] = x and rowsum (B, H, SS, C) fp32 = the sums of every image row over the x bins of every branch */
+int vkas_ppm_pool_fwd(const void* x, long ldx, void* cat, long ldcat, float* rowsum, int B, int H, int W, int C, int Cb,
+                      int nb, const int* scales, int dtype, void* stream);
+/* forward 2: pooled P (B S, C), Linear output lin (B S, Cb), stats (B S, 2) fp32 [mean, rstd] - all three NULL when nothing is
+ * kept for a backward - and act (B S, Cb) = gelu(LN(lin)); P, lin and act are each rounded once to `dtype` */
+int vkas_ppm_rows_fwd(const float* rowsum, const float* const* params, void* pooled, void* lin, float* stats, void* act, int B,
+                      int H, int W, int C, int Cb, int nb, const int* scales, int dtype, void* stream);
+/* forward 3: every branch of act resized (vkas_resize_fwd's bilinear arithmetic) into its channel slice of cat */
+int vkas_ppm_resize_fwd(const void* act, void* cat, long ldcat, int B, int H, int W, int C, int Cb, int nb, const int* scales,
+                        int dtype, void* stream);
+/* backward 1: tx (B, H, SS, Cb) fp32 = the x half of the resize adjoint of the branch slices of dcat (read in place, pixel
+ * stride lddcat) */
+int vkas_ppm_resize_bwd_x(const void* dcat, long lddcat, float* tx, int B, int H, int W, int C, int Cb, int nb,
+                          const int* scales, int dtype, void* stream);
+/* backward 2: the y half, LN + GELU backward -> dz (B S, Cb) in `dtype`, partial (vkas_ppm_row_groups, 2 Cb) fp32 rows of
+ * dgamma | dbeta, and dp (B S, C) fp32 = dz W_k (NULL: no input gradient wanted) */
+int vkas_ppm_rows_bwd(const float* tx, const float* const* params, const void* lin, const float* stats, void* dz,
+                      float* partial, float* dp, int B, int H, int W, int C, int Cb, int nb, const int* scales, int dtype,
+                      void* stream);
+/* backward 3: grads[4 k + 0 .. 3] = dW_k (Cb, C), db_k, dgamma_k, dbeta_k (fp32, contiguous); accumulate[i] != 0: added onto
+ * what grads[i] holds (a parameter's gradient view), else written */
+int vkas_ppm_param_grads(const void* dz, const void* pooled, const float* partial, float* const* grads, const int* accumulate,
+                         int B, int C, int Cb, int nb, const int* scales, int dtype, void* stream);
+/* backward 4: dx = dcat[..., :C] + sum_k pool_k^T(dp_k), rounded once */
+int vkas_ppm_pool_bwd(const void* dcat, long lddcat, const float* dp, void* dx, long lddx, int B, int H, int W, int C, int Cb,
+                      int nb, const int* scales, int dtype, void* stream);
+
 /* ---- elementwise ------------------------------------------------------------------------------------ */
 /* y[m][0..Cp) = x[m][0..Cp) (+ y if accumulate): channel-slice copies for concat / its backward */
 int vkas_copy_channels(const void* x, long ldx, void* y, long ldy, long M, int Cp, int accumulate, int dtype,

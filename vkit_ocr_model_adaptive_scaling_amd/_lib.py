@@ -157,6 +157,14 @@ _SIGS = {
     'vkas_upconv_adj_unpack_wgrad': (c_int, [_P, _P, c_int, c_int, _P]),
     'vkas_adaptive_avgpool_fwd':(c_int, [_P, c_long, _P, c_long, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     'vkas_adaptive_avgpool_bwd': (c_int, [_P, c_long, _P, c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    'vkas_ppm_row_groups': (c_long, [c_int, c_int, POINTER(c_int)]),
+    'vkas_ppm_pool_fwd': (c_int, [_P, c_long, _P, c_long, _P] + [c_int] * 6 + [POINTER(c_int), c_int, _P]),
+    'vkas_ppm_rows_fwd': (c_int, [_P, POINTER(c_void_p), _P, _P, _P, _P] + [c_int] * 6 + [POINTER(c_int), c_int, _P]),
+    'vkas_ppm_resize_fwd': (c_int, [_P, _P, c_long] + [c_int] * 6 + [POINTER(c_int), c_int, _P]),
+    'vkas_ppm_resize_bwd_x': (c_int, [_P, c_long, _P] + [c_int] * 6 + [POINTER(c_int), c_int, _P]),
+    'vkas_ppm_rows_bwd': (c_int, [_P, POINTER(c_void_p), _P, _P, _P, _P, _P] + [c_int] * 6 + [POINTER(c_int), c_int, _P]),
+    'vkas_ppm_param_grads': (c_int, [_P, _P, _P, POINTER(c_void_p), POINTER(c_int)] + [c_int] * 4 + [POINTER(c_int), c_int, _P]),
+    'vkas_ppm_pool_bwd': (c_int, [_P, c_long, _P, _P, c_long] + [c_int] * 6 + [POINTER(c_int), c_int, _P]),
     'vkas_copy_channels': (c_int, [_P, c_long, _P, c_long, c_long, c_int, c_int, c_int, _P]),
     'vkas_copy_channel_range': (c_int, [_P, c_long, c_int, _P, c_long, c_int, c_long, c_int, c_int, c_int, _P]),
     'vkas_softplus_fwd': (c_int, [_P, _P, c_long, _P]),

@@ -95,7 +95,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const T* __restrict_
     }
   }
 #pragma unroll
-  for (int r = 0; r < R; ++r) s[r] = group_sum(s[r], G) / (float)C;  // mean
+  for (int r = 0; r < R; ++r) s[r] = ln_mean(group_sum(s[r], G), C);
   float q[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
@@ -111,7 +111,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const T* __restrict_
     }
   }
 #pragma unroll
-  for (int r = 0; r < R; ++r) q[r] = rsqrtf(group_sum(q[r], G) / (float)C + 1e-6f);  // rstd
+  for (int r = 0; r < R; ++r) q[r] = ln_rstd(group_sum(q[r], G), C);
   // gamma / beta are zero padded to Cp, so pad channels come out as act(0) = 0 without a branch
   float gv[MAXV][8], bv[MAXV][8];
 #pragma unroll
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const T* __restrict_
       float o[8];
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
-        float u = (v[r][i][c] - s[r]) * q[r] * gv[i][c] + bv[i][c];
+        float u = ln_affine(v[r][i][c], s[r], q[r], gv[i][c], bv[i][c]);
         if (act_gelu) u = gelu_t<T>(u);
         o[c] = u;
       }

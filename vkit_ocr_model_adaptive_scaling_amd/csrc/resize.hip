@@ -5,42 +5,9 @@
 // the destination pixels that referenced it, enumerated from the same index function as the forward), so
 // no float atomics and bit-reproducible results.
 #include "vkas_common.h"
+#include "resize_index.h"
 
 namespace {
-
-// source coordinate of F.interpolate(bilinear, align_corners=False): src = max((dst+0.5)*in/out-0.5, 0)
-__device__ __forceinline__ void bilinear_src(int dst, float scale, int n_in, int& i0, int& i1, float& w1) {
-  float src = ((float)dst + 0.5f) * scale - 0.5f;
-  src = src < 0.f ? 0.f : src;
-  i0 = (int)src;
-  if (i0 > n_in - 1) i0 = n_in - 1;
-  i1 = i0 + 1 < n_in ? i0 + 1 : n_in - 1;
-  w1 = src - (float)i0;
-}
-// a * (1 - w) + b * w with the contraction spelled out: one rounded product, one fused multiply-add.  Left to the compiler,
-// the generic and the x2 forward contracted these sums differently (mul + fma for some outputs, mul + mul + add for others)
-// and about a sixth of their fp32 outputs differed in the last bit (the 16-bit types rounded it away; the backwards agreed);
-// written this way both round the same products in the same places (tests/test_gpu_resize.py compares them).
-__device__ __forceinline__ float lerp2(float a, float b, float w) { return fmaf(b, w, __fmul_rn(a, 1.f - w)); }
-// nearest: src = min((int)floorf(dst * scale), in-1) with the float32 scale = (float)in / out, as F.interpolate evaluates it
-// (one rounded division, one rounded product: where dst * in / out is an integer the product may fall just below it, and
-// the integer form floor(dst * in / out) would then pick the next source index)
-__device__ __forceinline__ int nearest_src(int dst, int n_in, int n_out) {
-  const float scale = __fdiv_rn((float)n_in, (float)n_out);
-  const int s = (int)floorf(__fmul_rn((float)dst, scale));
-  return s < n_in - 1 ? s : n_in - 1;
-}
-
-// weight with which destination index `dst` reads source index `src_i` along one axis (0 if it does not)
-__device__ __forceinline__ float axis_weight(int dst, float scale, int n_in, int n_out, int src_i, int mode) {
-  if (mode == 0) {
-    int i0, i1;
-    float w1;
-    bilinear_src(dst, scale, n_in, i0, i1, w1);
-    return (i0 == src_i ? 1.f - w1 : 0.f) + (i1 == src_i ? w1 : 0.f);
-  }
-  return nearest_src(dst, n_in, n_out) == src_i ? 1.f : 0.f;
-}
 
 // Workgroups are dealt round-robin over the 8 XCDs (private L2s) in launch order, x fastest: neighbouring image rows read
 // the same source rows, so give every XCD one contiguous run of rows instead of every 8th row (any grid: a bijection).
@@ -93,23 +60,6 @@ __global__ __launch_bounds__(256) void resize_fwd_kernel(const T* __restrict__ x
     for (int k = 0; k < 8; ++k) o[k] += t[k];
   }
   store8(dst, o);
-}
-
-// destination range [lo, hi] along one axis that reads source index i (tight; empty if lo > hi)
-__device__ __forceinline__ void dst_range(int i, int n_in, int n_out, float scale, int mode, int& lo, int& hi) {
-  const float r = (float)n_out / (float)n_in;
-  if (mode == 0) {
-    lo = (int)floorf(((float)i - 1.f) * r) - 2;
-    hi = (int)ceilf(((float)i + 1.5f) * r) + 2;
-  } else {
-    lo = (int)floorf((float)i * r) - 2;
-    hi = (int)ceilf(((float)i + 1.f) * r) + 2;
-  }
-  if (i == n_in - 1) hi = n_out - 1;  // the last source index also collects every clamped destination
-  if (lo < 0) lo = 0;
-  if (hi > n_out - 1) hi = n_out - 1;
-  while (lo <= hi && axis_weight(lo, scale, n_in, n_out, i, mode) == 0.f) ++lo;
-  while (hi >= lo && axis_weight(hi, scale, n_in, n_out, i, mode) == 0.f) --hi;
 }
 
 // dx[b,iy,ix] (+)= sum over destination pixels (oy,ox) of weight(oy->iy) * weight(ox->ix) * dy[b,oy,ox]
@@ -452,12 +402,6 @@ __global__ __launch_bounds__(256) void resize_bwd_small_kernel(const T* __restri
     }
     store8(dst, acc);
   }
-}
-
-// bin i of AdaptiveAvgPool: [floor(i*n/s), ceil((i+1)*n/s))
-__device__ __forceinline__ void pool_bin(int i, int n, int s, int& lo, int& hi) {
-  lo = (i * n) / s;
-  hi = ((i + 1) * n + s - 1) / s;
 }
 
 // one workgroup per (b, bin, group of vb channel vectors): the bin's pixels are spread over 256 / vb lanes per vector and

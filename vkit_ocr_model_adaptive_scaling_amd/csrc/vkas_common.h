@@ -213,6 +213,12 @@ template <> __device__ __forceinline__ float dgelu_t<bf16_t>(float x) {
   return fmaf(xc, p, 0.5f);
 }
 
+// LayerNorm over C channels (eps 1e-6, helper.py:96-97): mean from the row sum, rstd from the sum of centred squares, and the
+// affine map of one element - stated once for layernorm_fwd_kernel (norm.hip) and the pooled rows of ppm.hip
+__device__ __forceinline__ float ln_mean(float sum, int C) { return sum / (float)C; }
+__device__ __forceinline__ float ln_rstd(float sq, int C) { return rsqrtf(sq / (float)C + 1e-6f); }
+__device__ __forceinline__ float ln_affine(float v, float mean, float rstd, float g, float b) { return (v - mean) * rstd * g + b; }
+
 // Two elements per instruction (round 4): CDNA3/4 issue v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32 at the rate of their scalar forms,
 // i.e. a polynomial on a PAIR costs what it costs on one element; the constants ride in SGPRs (op_sel broadcast).  Same operations in
 // the same order per component as gelu_t / dgelu_t: bit-identical results.  fp32 storage keeps the exact (erf) forms per component.

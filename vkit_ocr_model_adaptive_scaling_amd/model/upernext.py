@@ -53,12 +53,21 @@ class PpmBlock(nn.Module):
     def _refresh_script_spec(self):
         scripting.refresh_module_spec(self)
 
-    def forward_act(self, x: torch.Tensor) -> torch.Tensor:
+    def branches_cat(self, x: torch.Tensor) -> torch.Tensor:
+        """x with the pooled branches, resized to x, concatenated behind it."""
+        if (ops.ppm_fused_eligible(x.dtype, self.in_channels, self.branch_channels, self.ppm_scales)
+                and x.shape[3] == self.in_channels and not ops.ppm_unfused_forced()):
+            params = []
+            for branch in self.ap_conv_blocks:  # parameter slots 1 = Linear, 2 = LayerNorm of the 1x1 block
+                params.extend([branch[1][1].weight, branch[1][1].bias, branch[1][2].weight, branch[1][2].bias])
+            return ops.PpmBranchesCat.apply(x, torch.is_grad_enabled(), self.ppm_scales, *params)  # csrc/ppm.hip
         pooled = ops.AdaptiveAvgPools.apply(x, *self.ppm_scales)  # one node: its backward sums the branches' gradients
         parts = [helper.conv_block(f, branch[1][1], branch[1][2]) for f, branch in zip(pooled, self.ap_conv_blocks)]
         widths = [self.in_channels] + [self.branch_channels] * len(parts)
-        cat = ops.ResizeCat.apply(BILINEAR, widths, x, *parts)  # the pooled branches resized to x and concatenated behind it
-        return helper.conv_block(cat, self.final_conv_block[0], self.final_conv_block[2], 1, 1)
+        return ops.ResizeCat.apply(BILINEAR, widths, x, *parts)
+
+    def forward_act(self, x: torch.Tensor) -> torch.Tensor:
+        return helper.conv_block(self.branches_cat(x), self.final_conv_block[0], self.final_conv_block[2], 1, 1)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if torch.jit.is_scripting():

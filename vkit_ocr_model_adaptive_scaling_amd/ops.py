@@ -1989,6 +1989,130 @@ class ResizeCat(Function):
         return (None, None, *grads)
 
 
+# limits of csrc/ppm.hip (VKAS_PPM_* of include/vkas.h; its entry points check them again)
+PPM_MAX_BRANCHES, PPM_MAX_SCALE, PPM_MAX_CELLS, PPM_MAX_C, PPM_MAX_CB = 4, 16, 256, 2048, 512
+
+
+def ppm_fused_eligible(dtype: torch.dtype, C: int, Cb: int, scales: Sequence[int]) -> bool:
+    """Whether PpmBranchesCat runs a pyramid-pooling block of C input and Cb branch channels at these scales: 16-bit
+    storage, channel counts that are their own padded widths, and the kernels' limits.  The map size is free."""
+    scales = tuple(scales)
+    return (dtype in _MFMA_DTYPES and C % 8 == 0 and Cb % 8 == 0 and 0 < C <= PPM_MAX_C and 0 < Cb <= PPM_MAX_CB
+            and 1 <= len(scales) <= PPM_MAX_BRANCHES and all(1 <= s <= PPM_MAX_SCALE for s in scales)
+            and sum(s * s for s in scales) <= PPM_MAX_CELLS)
+
+
+def ppm_unfused_forced() -> bool:
+    """VKAS_PPM_UNFUSED: A/B switch, read at every call - the block takes AdaptiveAvgPools + 4 x conv_block + ResizeCat."""
+    return os.environ.get('VKAS_PPM_UNFUSED') is not None
+
+
+class PpmBranchesCat(Function):
+    """The pooled branches of the pyramid-pooling block and their concatenation behind x (model/upernext.py:58-82) as one node:
+    cat[..., :C] = x, cat[..., C + k Cb : C + (k+1) Cb] = bilinear(gelu(LN(pool_{s_k}(x) W_k^T + b_k)) -> H x W).
+    ``params`` = W_k, b_k, gamma_k, beta_k per branch (fp32, as the modules hold them).  Three launches forward, four backward
+    (csrc/ppm.hip); ``keep`` false: nothing is saved and the Linear output / statistics are not written.
+    Parameter gradients are added onto the flat gradient views where the parameters have them (grad_sink) by the kernel that
+    forms them, and go back to autograd as tensors of their own otherwise."""
+
+    @staticmethod
+    def forward(ctx, x, keep: bool, scales, *params):
+        _require_cuda(x, *params)
+        x = as_act(x)
+        B, H, W, C = x.shape
+        scales = tuple(int(s) for s in scales)
+        nb = len(scales)
+        if len(params) != 4 * nb or params[0].dim() != 2:
+            raise ValueError('PpmBranchesCat: expected W, b, gamma, beta per scale')
+        Cb = params[0].shape[0]
+        if not ppm_fused_eligible(x.dtype, C, Cb, scales):
+            raise ValueError(f'PpmBranchesCat: not eligible (dtype {x.dtype}, C {C}, Cb {Cb}, scales {scales})')
+        for i, p in enumerate(params):
+            if p.dtype != _FLOAT or tuple(p.shape) != ((Cb, C) if i % 4 == 0 else (Cb,)):
+                raise ValueError(f'PpmBranchesCat: parameter {i} has shape {tuple(p.shape)} / dtype {p.dtype}')
+        params = [p.contiguous() for p in params]
+        sc = (ctypes.c_int * nb)(*scales)
+        ptrs = (ctypes.c_void_p * (4 * nb))(*[p.data_ptr() for p in params])
+        S, SS = sum(s * s for s in scales), sum(scales)
+        M, dev, es, dt = B * S, x.device, x.element_size(), _dt(x)
+        cat = new_act(B, H, W, C + nb * Cb, x)
+        rowsum = torch.empty((B * H * SS * C,), dtype=_FLOAT, device=dev)
+        act = torch.empty((M, Cb), dtype=x.dtype, device=dev)
+        pooled = torch.empty((M, C), dtype=x.dtype, device=dev) if keep else None
+        lin = torch.empty((M, Cb), dtype=x.dtype, device=dev) if keep else None
+        stats = torch.empty((M, 2), dtype=_FLOAT, device=dev) if keep else None
+        px = B * H * W
+        _timed('ppm_pool_fwd_kernel', x, 0.0, px, C, 0,
+               lambda: check(lib.vkas_ppm_pool_fwd(_p(x), act_ld(x), _p(cat), act_ld(cat), _p(rowsum), B, H, W, C, Cb, nb, sc, dt,
+                                                   _stream()), 'ppm_pool_fwd'), 2.0 * px * C * es + 4.0 * rowsum.numel())
+        _timed('ppm_rows_fwd_kernel', x, 2.0 * M * Cb * C, M, Cb, C,
+               lambda: check(lib.vkas_ppm_rows_fwd(_p(rowsum), ptrs, _p(pooled), _p(lin), _p(stats), _p(act), B, H, W, C, Cb, nb, sc,
+                                                   dt, _stream()), 'ppm_rows_fwd'), 4.0 * rowsum.numel() + 4.0 * nb * Cb * C)
+        _timed('ppm_resize_fwd_kernel', x, 0.0, px, nb * Cb, 0,
+               lambda: check(lib.vkas_ppm_resize_fwd(_p(act), _p(cat), act_ld(cat), B, H, W, C, Cb, nb, sc, dt, _stream()),
+                             'ppm_resize_fwd'), float(px * nb * Cb * es))
+        if keep:
+            ctx.save_for_backward(pooled, lin, stats, *params)
+            ctx.cfg = (B, H, W, C, Cb, scales)
+        return cat
+
+    @staticmethod
+    def backward(ctx, dcat):
+        pooled, lin, stats, *params = ctx.saved_tensors
+        B, H, W, C, Cb, scales = ctx.cfg
+        dcat = as_act(dcat)
+        nb = len(scales)
+        sc = (ctypes.c_int * nb)(*scales)
+        ptrs = (ctypes.c_void_p * (4 * nb))(*[p.data_ptr() for p in params])
+        S, SS = sum(s * s for s in scales), sum(scales)
+        M, dev, es, dt = B * S, dcat.device, dcat.element_size(), _dt(dcat)
+        px = B * H * W
+        tx = torch.empty((B * H * SS * Cb,), dtype=_FLOAT, device=dev)
+        dz = torch.empty((M, Cb), dtype=dcat.dtype, device=dev)
+        groups = lib.vkas_ppm_row_groups(B, nb, sc)
+        if groups < 0:
+            check(-1, 'ppm_row_groups')
+        partial = torch.empty((max(groups, 1) * 2 * Cb,), dtype=_FLOAT, device=dev)
+        want_dx = ctx.needs_input_grad[0]
+        dp = torch.empty((M, C), dtype=_FLOAT, device=dev) if want_dx else None
+        _timed('ppm_resize_bwd_x_kernel', dcat, 0.0, px, nb * Cb, 0,
+               lambda: check(lib.vkas_ppm_resize_bwd_x(_p(dcat), act_ld(dcat), _p(tx), B, H, W, C, Cb, nb, sc, dt, _stream()),
+                             'ppm_resize_bwd_x'), float(px * nb * Cb * es) + 4.0 * tx.numel())
+        _timed('ppm_rows_bwd_kernel', dcat, 2.0 * M * Cb * C * int(want_dx), M, C, Cb,
+               lambda: check(lib.vkas_ppm_rows_bwd(_p(tx), ptrs, _p(lin), _p(stats), _p(dz), _p(partial), _p(dp), B, H, W, C, Cb, nb,
+                                                   sc, dt, _stream()), 'ppm_rows_bwd'),
+               4.0 * tx.numel() + 4.0 * nb * Cb * C + 4.0 * M * C * int(want_dx))
+        # every parameter gradient has one writer in the kernel: it adds onto the flat gradient view where there is one (no
+        # delivery launch), and fills a tensor of its own otherwise (never a slice of the step's zero arena)
+        dsts, accs, outs, sinks = [], [], [], []
+        for i, p in enumerate(params):
+            s = grad_sink(p) if ctx.needs_input_grad[3 + i] else None
+            if s is not None and p.grad.is_contiguous() and p.grad.dtype == _FLOAT and p.grad.numel() == p.numel():
+                dsts.append(p.grad)
+                accs.append(1)
+                outs.append(None)
+                sinks.append(s)
+            else:
+                g = torch.empty(p.shape, dtype=_FLOAT, device=dev)
+                dsts.append(g)
+                accs.append(0)
+                outs.append(g if ctx.needs_input_grad[3 + i] else None)
+        gp = (ctypes.c_void_p * (4 * nb))(*[g.data_ptr() for g in dsts])
+        ga = (ctypes.c_int * (4 * nb))(*accs)
+        _timed('ppm_param_grads_kernel', dcat, 2.0 * M * Cb * C, Cb, C, M,
+               lambda: check(lib.vkas_ppm_param_grads(_p(dz), _p(pooled), _p(partial), gp, ga, B, C, Cb, nb, sc, dt, _stream()),
+                             'ppm_param_grads'), 4.0 * nb * Cb * C + float(M * (C + Cb) * es))
+        for s in sinks:
+            s[0].grad_delivered(s[1])
+        dx = None
+        if want_dx:
+            dx = new_act(B, H, W, C, dcat)
+            _timed('ppm_pool_bwd_kernel', dcat, 0.0, px, C, 0,
+                   lambda: check(lib.vkas_ppm_pool_bwd(_p(dcat), act_ld(dcat), _p(dp), _p(dx), act_ld(dx), B, H, W, C, Cb, nb, sc,
+                                                       dt, _stream()), 'ppm_pool_bwd'), 2.0 * px * C * es)
+        return (dx, None, None, *outs)
+
+
 class SplitBatch(Function):
     """x -> (x[:b0], x[b0:]) as views of one NHWC activation; backward writes the two gradients into the halves of one
     buffer (no zero-fill + add, which is what slicing through autograd would do).  Used by the merged pass schedule
