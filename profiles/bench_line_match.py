@@ -76,12 +76,10 @@ def line_page(n, seed):
 
 
 def tables_of(n):
-    from vkit_ocr_model_adaptive_scaling_amd.inferencing.line_evaluation import _padded
-    from vkit_ocr_model_adaptive_scaling_amd.inferencing import match_rows
+    from vkit_ocr_model_adaptive_scaling_amd.inferencing import padded_sides, quad_rows_host
     pages = [line_page(n, 100 + b) for b in range(B)]
-    h_gt, gt_count, care, h_pred, pred_count = _padded([p[2] for p in pages], [p[0] for p in pages], [p[1] for p in pages])
-    rows = lambda q: match_rows(q.reshape(-1, 4, 2))[0].reshape(q.shape[0], q.shape[1], 16)
-    return rows(h_gt), gt_count, care, rows(h_pred), pred_count
+    h_gt, gt_count, care, h_pred, pred_count = padded_sides([p[2] for p in pages], [p[0] for p in pages], [p[1] for p in pages])
+    return quad_rows_host(h_gt), gt_count, care, quad_rows_host(h_pred), pred_count
 
 
 def workload(kind, n, iters):

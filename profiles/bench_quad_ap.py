@@ -52,13 +52,11 @@ def ranked_page(n, seed):
 
 
 def tables_of(n):
-    from vkit_ocr_model_adaptive_scaling_amd.inferencing.ranking import _padded
-    from vkit_ocr_model_adaptive_scaling_amd.inferencing import match_rows
+    from vkit_ocr_model_adaptive_scaling_amd.inferencing import padded_sides, quad_rows_host
     pages = [ranked_page(n, 100 + b) for b in range(B)]
-    h_gt, gt_count, care, h_pred, pred_count, probs = _padded([p[2] for p in pages], [p[0] for p in pages],
-                                                              [p[3] for p in pages], [p[1] for p in pages])
-    rows = lambda q: match_rows(q.reshape(-1, 4, 2))[0].reshape(q.shape[0], q.shape[1], 16)
-    return rows(h_gt), gt_count, care, rows(h_pred), pred_count, probs
+    h_gt, gt_count, care, h_pred, pred_count, probs = padded_sides([p[2] for p in pages], [p[0] for p in pages],
+                                                                   [p[1] for p in pages], [p[3] for p in pages])
+    return quad_rows_host(h_gt), gt_count, care, quad_rows_host(h_pred), pred_count, probs
 
 
 def workload(kind, n, iters):

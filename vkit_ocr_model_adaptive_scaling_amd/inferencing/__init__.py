@@ -15,8 +15,10 @@ from .regions import region_scales, text_regions_host
 from .packing import (SIDE_MAX, axis_weights, check_placements, pack_region_labels_host, region_crops, remap_polygons,
                       resample_host, stack_regions, check_warps, remap_polygons_affine, warp_host, warp_region_labels_host,
                       check_multi_rows, pack_region_labels_multi_host, resample_pack_multi_host, stack_regions_pages)
-from .evaluation import (DetectionScore, QuadMatchResult, evaluate_quads, evaluate_quads_host, evaluation_tables,
-                         match_quads_host, match_rows, quad_iou_host, result_quads)
+from .quad_tables import (clamped, host_table, host_tables, pad_quads, pad_rows, pad_values, padded_sides, quad_lists,
+                          require_gpu, with_capacity)
+from .evaluation import (DetectionScore, QuadMatchResult, care_pairs, check_iou_thr, evaluate_quads, evaluate_quads_host,
+                         evaluation_tables, match_quads_host, match_rows, quad_iou_host, quad_rows_host, result_quads)
 from .nms import (QuadNmsResult, filter_result, greedy_suppression, nms_pairs, nms_quads, nms_quads_host,
                   nms_quads_lists_host, nms_tables, suppress_results)
 from .lines import (QuadLinesResult, group_results, line_params, line_quads, link_pairs, quad_frames, quad_lines,

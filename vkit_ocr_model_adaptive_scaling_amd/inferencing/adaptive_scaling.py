@@ -631,6 +631,28 @@ class AdaptiveScalingInferencing:
         return step(results, images_or_arena, c.precise_line_strip_height, c.precise_line_strip_width_max,
                     c.precise_line_strip_width_step, c.precise_line_strip_margin, c.device)
 
+    def _check_line_flags(self):
+        c = self.config
+        if c.precise_line_strips and not c.precise_char_lines:
+            raise ValueError('precise_line_strips cuts the text lines: set precise_char_lines too')
+        if c.precise_line_strip_curved and not c.precise_line_strips:
+            raise ValueError('precise_line_strip_curved is a way to cut the line strips: set precise_line_strips too')
+
+    def _finish(self, results, strip_source):
+        """The tail of ``infer`` / ``infer_batch``, each step one call for all images and only with its switch: suppress
+        duplicates, group into lines, cut the lines' strips out of ``strip_source`` (what ``_line_strips`` takes) ->
+        ``(results, strips)``, ``strips`` None without ``config.precise_line_strips``."""
+        c = self.config
+        if c.precise_char_nms_iou_thr:
+            results = suppress_results(results, c.precise_char_nms_iou_thr, c.device)
+        if c.precise_char_lines:
+            results = group_results(results, c.precise_char_line_gap, c.precise_char_line_cross,
+                                    c.precise_char_line_height_ratio, c.device)
+        strips = None
+        if c.precise_line_strips:
+            results, strips = self._line_strips(results, strip_source)
+        return results, strips
+
     # ---- image in, characters out --------------------------------------------------------------------------------
     def infer(self, image, return_page: bool = False, return_labels: bool = False) -> AdaptiveScalingInferencingResult:
         """Both passes and the step between them (:92-525 on pixels): the uint8 image is uploaded once; the 720 rule's shrink
@@ -649,10 +671,7 @@ class AdaptiveScalingInferencing:
         ``ops.warp_pack_u8`` / ``ops.warp_region_labels`` write the oriented regions into the page and the label page after
         the axis-aligned ones; their characters go back through ``remap_polygons_affine``."""
         c = self.config
-        if c.precise_line_strips and not c.precise_char_lines:
-            raise ValueError('precise_line_strips cuts the text lines: set precise_char_lines too')
-        if c.precise_line_strip_curved and not c.precise_line_strips:
-            raise ValueError('precise_line_strip_curved is a way to cut the line strips: set precise_line_strips too')
+        self._check_line_flags()
         mat = _as_mat(image)
         if mat.dtype != np.uint8:
             raise ValueError(f'infer takes a uint8 image, got {mat.dtype}')
@@ -723,14 +742,9 @@ class AdaptiveScalingInferencing:
             polygons=polygons)
         if orient:
             result.oriented, result.warps, result.warp_regions = oriented, warps, warp_ids
-        if c.precise_char_nms_iou_thr:
-            result = suppress_results([result], c.precise_char_nms_iou_thr, c.device)[0]
-        if c.precise_char_lines:
-            result = group_results([result], c.precise_char_line_gap, c.precise_char_line_cross,
-                                   c.precise_char_line_height_ratio, c.device)[0]
-        if c.precise_line_strips:  # the image is on the device already: a one-entry source table
-            (result,), strips = self._line_strips([result], (src.reshape(-1), np.array([[0, *image_shape, 0]], np.int64)))
-            result.line_strips = strips
+        # the image is on the device already: a one-entry source table
+        (result,), strips = self._finish([result], (src.reshape(-1), np.array([[0, *image_shape, 0]], np.int64)))
+        result.line_strips = strips
         return result
 
     def infer_batch(self, images: Sequence, return_pages: bool = False,
@@ -757,10 +771,7 @@ class AdaptiveScalingInferencing:
         c = self.config
         if c.precise_text_region_orient:
             raise ValueError('infer_batch does not take oriented text regions yet: unset precise_text_region_orient or use infer')
-        if c.precise_line_strips and not c.precise_char_lines:
-            raise ValueError('precise_line_strips cuts the text lines: set precise_char_lines too')
-        if c.precise_line_strip_curved and not c.precise_line_strips:
-            raise ValueError('precise_line_strip_curved is a way to cut the line strips: set precise_line_strips too')
+        self._check_line_flags()
         if not len(images):
             return AdaptiveScalingInferencingBatchResult(results=[], page_shapes=[], rows=np.zeros((0, 12), np.int32),
                                                          pages=[] if return_pages else None,
@@ -835,14 +846,7 @@ class AdaptiveScalingInferencing:
                 page=pages[page] if return_pages and len(mine) else None,
                 region_labels=region_labels[page] if return_labels and len(mine) else None, points=points, probs=probs,
                 polygons=polygons, placement_pages=placement_pages))
-        if c.precise_char_nms_iou_thr:
-            results = suppress_results(results, c.precise_char_nms_iou_thr, c.device)  # one call for all images
-        if c.precise_char_lines:
-            results = group_results(results, c.precise_char_line_gap, c.precise_char_line_cross,
-                                    c.precise_char_line_height_ratio, c.device)  # one call for all images
-        strips = None
-        if c.precise_line_strips:  # one launch for the lines of all images, out of the arena
-            results, strips = self._line_strips(results, (arena, sources, d_sources))
+        results, strips = self._finish(results, (arena, sources, d_sources))  # the strips: one launch, out of the arena
         return AdaptiveScalingInferencingBatchResult(
             results=results, page_shapes=page_shapes, rows=rows, pages=pages if return_pages else None,
             region_labels=region_labels if return_labels else None, line_strips=strips)

@@ -49,20 +49,24 @@ Per image: ``gt_match`` (M,) int32 pred index or -1, ``pred_match`` (N,) int32, 
 unmatched), ``tp``, ``n_gt`` / ``n_pred`` (the valid rows within the count), ``pairs`` (box-overlapping valid pairs),
 ``candidates`` (those at or above iou_thr).  fp = n_pred - tp, fn = n_gt - tp.
 
+Lists of per-image quads -> padded tables, the checker of the oracles' tables and the two ends of the device wrappers are
+shared with the other routes over match rows: inferencing/quad_tables.py.
+
 Average precision over the scores, several IoU thresholds at once and don't-care annotations: inferencing/ranking.py.
 
 Text lines and words, scored with one-to-many splits and many-to-one merges: inferencing/line_evaluation.py."""
+import math
 from typing import List, Optional, Sequence, Tuple
 
 import attrs
 import numpy as np
 import torch
 
-ROW_WORDS = 16
+from .quad_tables import (MAX_QUADS, ROW_WORDS, clamped, host_tables, pad_rows, quad_lists, require_gpu, with_capacity)
+
 ROW_BOX, ROW_AREA, ROW_VALID = 8, 12, 14
 COORD_MAX = 1 << 19
 RING_MAX = 8
-MAX_QUADS = 8192  # per image and side: QM_MAX of csrc/quadmatch.hip
 
 
 def match_rows(quads, valid=None) -> Tuple[np.ndarray, np.ndarray]:
@@ -96,6 +100,12 @@ def match_rows(quads, valid=None) -> Tuple[np.ndarray, np.ndarray]:
     return rows, ok
 
 
+def quad_rows_host(quads: np.ndarray) -> np.ndarray:
+    """``ops.quad_rows`` on the host: padded quads (B, K, 4, 2) -> (B, K, 16) int32 match rows"""
+    B, K = quads.shape[:2]
+    return match_rows(quads.reshape(-1, 4, 2))[0].reshape(B, K, ROW_WORDS)
+
+
 def _area2(row: np.ndarray) -> int:
     return int(np.ascontiguousarray(row[ROW_AREA:ROW_AREA + 2], dtype='<i4').view('<i8')[0])
 
@@ -125,13 +135,14 @@ def _clip(ring: List[Tuple[float, float]], ay: float, ax: float, by: float, bx: 
     return out
 
 
-def quad_iou_host(g_row, p_row) -> float:
-    """The oracle of the pair IoU: two match rows (16 int32 each), both taken as valid -> the rule's binary64 IoU (0.0 when
-    the rows' boxes do not overlap).  Everything is read from the rows as they are, as the device does."""
+def quad_inter2_host(g_row, p_row) -> Tuple[float, float]:
+    """The oracle of the pair quantities: two match rows (16 int32 each), both taken as valid -> ``(inter2, iou)``: twice the
+    area of the intersection after the rule's clamp and the rule's binary64 IoU, from one clip (``(0.0, 0.0)`` when the rows'
+    boxes do not overlap).  Everything is read from the rows as they are, as the device does."""
     g = [int(v) for v in np.asarray(g_row).reshape(ROW_WORDS)]
     p = [int(v) for v in np.asarray(p_row).reshape(ROW_WORDS)]
     if g[8] > p[10] or p[8] > g[10] or g[9] > p[11] or p[9] > g[11]:
-        return 0.0
+        return 0.0, 0.0
     oy, ox = min(g[8], p[8]), min(g[9], p[9])
     gq = [(float(g[2 * k] - oy), float(g[2 * k + 1] - ox)) for k in range(4)]
     ring = [(float(p[2 * k] - oy), float(p[2 * k + 1] - ox)) for k in range(4)]
@@ -153,7 +164,12 @@ def quad_iou_host(g_row, p_row) -> float:
     if inter2 < 0.0:
         inter2 = 0.0
     den = (ag + ap) - inter2
-    return inter2 / den if den > 0.0 else 0.0
+    return inter2, (inter2 / den if den > 0.0 else 0.0)
+
+
+def quad_iou_host(g_row, p_row) -> float:
+    """The oracle of the pair IoU: the second result of ``quad_inter2_host``."""
+    return quad_inter2_host(g_row, p_row)[1]
 
 
 def box_pairs(gt_rows: np.ndarray, pred_rows: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
@@ -167,10 +183,34 @@ def box_pairs(gt_rows: np.ndarray, pred_rows: np.ndarray) -> Tuple[np.ndarray, n
     return np.nonzero(hit)
 
 
-def _check_thr(iou_thr) -> float:
+def care_pairs(g: np.ndarray, p: np.ndarray, care: np.ndarray, cover_thr: float):
+    """The don't-care pass over one image, every box pair clipped once: ``g`` (m, 16) and ``p`` (n, 16) cut to their counts,
+    ``care`` (m,) bool, ``cover_thr`` binary64 -> ``(pairs, covered, cover_margin, dc_pairs)``.  ``pairs`` are the pairs of a
+    care gt as ``(a, c, inter2, iou)``, gt-major ascending; ``covered`` (n,) bool marks the preds for which some don't-care gt
+    has ``inter2 >= cover_thr * area2_p`` (the product rounded once, the comparison inclusive); ``cover_margin`` is the least
+    ``|inter2 - cover_thr * area2_p| / area2_p`` over the ``dc_pairs`` pairs of a don't-care gt (inf without one)."""
+    gi, pi = box_pairs(g, p)
+    pairs, covered, margin, dc_pairs = [], np.zeros((len(p),), bool), math.inf, 0
+    for a, c in zip(gi.tolist(), pi.tolist()):
+        inter2, iou = quad_inter2_host(g[a], p[c])
+        if care[a]:
+            pairs.append((a, c, inter2, iou))
+        else:
+            dc_pairs += 1
+            ap = float(_area2(p[c]))
+            need = cover_thr * ap
+            if inter2 >= need:
+                covered[c] = True
+            if ap > 0:
+                margin = min(margin, abs(inter2 - need) / ap)
+    return pairs, covered, margin, dc_pairs
+
+
+def check_iou_thr(iou_thr, who: str = '') -> float:
+    """an IoU threshold of the rule: binary64 in (0, 1]; ``who`` names the caller in the error"""
     thr = float(iou_thr)
     if not (thr > 0.0 and thr <= 1.0):
-        raise ValueError(f'iou_thr must lie in (0, 1], got {iou_thr}')
+        raise ValueError(f'{who + ": " if who else ""}iou_thr must lie in (0, 1], got {iou_thr}')
     return thr
 
 
@@ -190,23 +230,14 @@ def match_quads_host(gt_rows, gt_count, pred_rows, pred_count, iou_thr: float = 
     ``pred_count`` (B,) -> ``(gt_match (B, M) int32, pred_match (B, N) int32, gt_iou (B, M) float64, stats (B, 6) int64)``
     with ``stats`` = tp, n_gt, n_pred, pairs, candidates, status (always 0 here: the host has no capacity).  As on the device
     the counts are clamped to [0, K], a row with ``valid == 0`` takes no part and every field of a row is used as it is."""
-    gt_rows = np.ascontiguousarray(gt_rows, dtype=np.int32)
-    pred_rows = np.ascontiguousarray(pred_rows, dtype=np.int32)
-    if gt_rows.ndim != 3 or gt_rows.shape[2] != ROW_WORDS or pred_rows.ndim != 3 or pred_rows.shape[2] != ROW_WORDS:
-        raise ValueError(f'rows must be (B, K, {ROW_WORDS}), got {gt_rows.shape} and {pred_rows.shape}')
-    B, M, _ = gt_rows.shape
-    N = pred_rows.shape[1]
-    gt_count, pred_count = np.asarray(gt_count).reshape(-1), np.asarray(pred_count).reshape(-1)
-    if pred_rows.shape[0] != B or len(gt_count) != B or len(pred_count) != B:
-        raise ValueError('tables and counts must share the batch size')
-    thr = _check_thr(iou_thr)
+    (gt_rows, gt_count, pred_rows, pred_count, _, _), B, M, N = host_tables(gt_rows, gt_count, pred_rows, pred_count)
+    thr = check_iou_thr(iou_thr)
     gt_match = np.full((B, M), -1, dtype=np.int32)
     pred_match = np.full((B, N), -1, dtype=np.int32)
     gt_iou = np.zeros((B, M), dtype=np.float64)
     stats = np.zeros((B, 6), dtype=np.int64)
     for b in range(B):
-        ng, npred = min(max(int(gt_count[b]), 0), M), min(max(int(pred_count[b]), 0), N)
-        g, p = gt_rows[b, :ng], pred_rows[b, :npred]
+        g, p = gt_rows[b, :clamped(gt_count[b], M)], pred_rows[b, :clamped(pred_count[b], N)]
         gi, pi = box_pairs(g, p)
         edges = []
         for a, c in zip(gi.tolist(), pi.tolist()):
@@ -281,37 +312,28 @@ def result_quads(result) -> Tuple[np.ndarray, np.ndarray]:
     return np.concatenate(polys, axis=0), np.concatenate(probs, axis=0)
 
 
+def fitting_quads(results: Sequence) -> Tuple[list, List[int]]:
+    """What the steps of ``infer`` / ``infer_batch`` over a result's characters start from: ``result_quads`` of every result,
+    and the indices of those with at most ``MAX_QUADS`` characters (the others keep their step's status 2)."""
+    tabs = [result_quads(r) for r in results]
+    return tabs, [i for i, (q, _) in enumerate(tabs) if len(q) <= MAX_QUADS]
+
+
 def evaluation_tables(pred: Sequence, gt: Sequence, pred_scores: Optional[Sequence] = None,
                       score_thr: Optional[float] = None):
     """The host half of ``evaluate_quads``: per-image quad arrays -> ``(gt_rows (B, M, 16), gt_count (B,), pred_rows
     (B, N, 16), pred_count (B,), gt_valid, pred_valid)`` with M, N the batch's largest counts (at least 1)."""
-    pred, gt = list(pred), list(gt)
-    if len(pred) != len(gt):
-        raise ValueError(f'{len(pred)} images of predictions against {len(gt)} of annotations')
+    pq, gq = quad_lists(pred, gt)
     if (pred_scores is None) != (score_thr is None):
         raise ValueError('pred_scores and score_thr go together')
-    if pred_scores is not None and len(pred_scores) != len(pred):
+    if pred_scores is not None and len(pred_scores) != len(pq):
         raise ValueError(f'pred_scores must have one entry per image, got {len(pred_scores)}')
-    g_tabs = [match_rows(q) for q in gt]
-    p_tabs = []
-    for i, q in enumerate(pred):
-        keep = None
-        if pred_scores is not None:
-            s = np.asarray(pred_scores[i], dtype=np.float64).reshape(-1)
-            keep = s >= float(score_thr)  # NaN compares false
-        p_tabs.append(match_rows(q, keep))
-    B = len(gt)
-    M = max([1] + [len(r) for r, _ in g_tabs])
-    N = max([1] + [len(r) for r, _ in p_tabs])
-    if M > MAX_QUADS or N > MAX_QUADS:
-        raise ValueError(f'at most {MAX_QUADS} quads per image and side, got {M} annotations / {N} predictions')
-    gt_rows, pred_rows = np.zeros((B, M, ROW_WORDS), np.int32), np.zeros((B, N, ROW_WORDS), np.int32)
-    for b in range(B):
-        gt_rows[b, :len(g_tabs[b][0])] = g_tabs[b][0]
-        pred_rows[b, :len(p_tabs[b][0])] = p_tabs[b][0]
-    gt_count = np.array([len(r) for r, _ in g_tabs], dtype=np.int32)
-    pred_count = np.array([len(r) for r, _ in p_tabs], dtype=np.int32)
-    return gt_rows, gt_count, pred_rows, pred_count, [v for _, v in g_tabs], [v for _, v in p_tabs]
+    # compared in binary64: NaN compares false
+    keep = [None if pred_scores is None else np.asarray(pred_scores[i], dtype=np.float64).reshape(-1) >= float(score_thr)
+            for i in range(len(pq))]
+    g_tabs, p_tabs = [match_rows(q) for q in gq], [match_rows(q, k) for q, k in zip(pq, keep)]
+    return (*pad_rows([r for r, _ in g_tabs]), *pad_rows([r for r, _ in p_tabs]), [v for _, v in g_tabs],
+            [v for _, v in p_tabs])
 
 
 def _results(tables, outs, iou_dtype=np.float64) -> Tuple[List[QuadMatchResult], DetectionScore]:
@@ -343,19 +365,12 @@ def evaluate_quads(pred: Sequence, gt: Sequence, iou_thr: float = 0.5, pred_scor
     once and the statistics are read back; if an image reports ``status`` the call is repeated once with the reported
     candidate count as capacity.  Returns ``(per-image QuadMatchResult list, DetectionScore over the batch)``."""
     from .. import ops
-    device = torch.device(device)
-    if device.type != 'cuda':
-        raise ValueError(f'evaluate_quads runs on the GPU, got device {device} (host route: evaluate_quads_host)')
-    _check_thr(iou_thr)
+    device = require_gpu('evaluate_quads', device, 'evaluate_quads_host')
+    check_iou_thr(iou_thr)
     tables = evaluation_tables(pred, gt, pred_scores, score_thr)
     if len(tables[1]) == 0:
         return [], DetectionScore()
     dev = [torch.from_numpy(t).to(device, non_blocking=True) for t in tables[:4]]
-    outs = ops.match_quads(*dev, iou_thr=iou_thr)
-    stats = outs[3].cpu().numpy()
-    if stats[:, 5].any():
-        outs = ops.match_quads(*dev, iou_thr=iou_thr, max_pairs=int(stats[:, 4].max()))
-        stats = outs[3].cpu().numpy()
-        if stats[:, 5].any():
-            raise RuntimeError('evaluate_quads: the retry with the reported capacity overflowed again')
+    outs, stats = with_capacity('evaluate_quads', lambda cap: ops.match_quads(*dev, iou_thr=iou_thr, max_pairs=cap),
+                                lambda o: o[3].cpu().numpy(), np.s_[:, 5], np.s_[:, 4])
     return _results(tables, (outs[0].cpu().numpy(), outs[1].cpu().numpy(), outs[2].cpu().numpy(), stats))

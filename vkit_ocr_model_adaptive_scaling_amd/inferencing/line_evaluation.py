@@ -98,8 +98,8 @@ import attrs
 import numpy as np
 import torch
 
-from .evaluation import MAX_QUADS, ROW_VALID, ROW_WORDS, _area2, box_pairs, match_rows
-from .ranking import quad_inter2_host
+from .evaluation import ROW_VALID, _area2, care_pairs, quad_rows_host
+from .quad_tables import clamped, host_tables, padded_sides, require_gpu, with_capacity
 
 ABSENT, UNMATCHED, ONE_TO_ONE, SPLIT, MERGE, APART = 0, 1, 2, 3, 4, 5  # SPLIT: a split gt / a split part; APART: 5
 AREA_MAX = 1 << 41
@@ -148,32 +148,16 @@ class LinePairs:
     cover_margin: float    # the least |inter2 - cover_thr * area2_p| / area2_p over the don't-care pairs (inf without one)
 
 
-def _check_tables(gt_rows, gt_count, gt_care, pred_rows, pred_count):
-    gt_rows = np.ascontiguousarray(gt_rows, dtype=np.int32)
-    pred_rows = np.ascontiguousarray(pred_rows, dtype=np.int32)
-    if gt_rows.ndim != 3 or gt_rows.shape[2] != ROW_WORDS or pred_rows.ndim != 3 or pred_rows.shape[2] != ROW_WORDS:
-        raise ValueError(f'rows must be (B, K, {ROW_WORDS}), got {gt_rows.shape} and {pred_rows.shape}')
-    B, M, _ = gt_rows.shape
-    gt_count, pred_count = np.asarray(gt_count).reshape(-1), np.asarray(pred_count).reshape(-1)
-    gt_care = np.ones((B, M), np.uint8) if gt_care is None else np.ascontiguousarray(gt_care, dtype=np.uint8)
-    if pred_rows.shape[0] != B or len(gt_count) != B or len(pred_count) != B:
-        raise ValueError('tables and counts must share the batch size')
-    if gt_care.shape != (B, M):
-        raise ValueError(f'gt_care must be ({B}, {M}), got {gt_care.shape}')
-    return gt_rows, gt_count, gt_care, pred_rows, pred_count
-
-
 def line_pairs(gt_rows, gt_count, gt_care, pred_rows, pred_count, recall_thr=0.8, precision_thr=0.4, cover_thr=0.5
                ) -> List[LinePairs]:
     """The clip of every box pair, once: per image phase 0 and the candidates.  Both oracles take its result as ``pairs=``
     so that a test computes it once."""
-    gt_rows, gt_count, gt_care, pred_rows, pred_count = _check_tables(gt_rows, gt_count, gt_care, pred_rows, pred_count)
+    (gt_rows, gt_count, pred_rows, pred_count, gt_care, _), B, M, N = host_tables(gt_rows, gt_count, pred_rows, pred_count,
+                                                                                  gt_care)
     tr, tp, cover_thr = check_line_thresholds(recall_thr, precision_thr, cover_thr)
-    B, M, _ = gt_rows.shape
-    N = pred_rows.shape[1]
     out = []
     for b in range(B):
-        ng, npred = min(max(int(gt_count[b]), 0), M), min(max(int(pred_count[b]), 0), N)
+        ng, npred = clamped(gt_count[b], M), clamped(pred_count[b], N)
         g, p = gt_rows[b, :ng], pred_rows[b, :npred]
         care = gt_care[b, :ng] != 0
         gt_kind, pred_kind = np.zeros((M,), np.uint8), np.zeros((N,), np.uint8)
@@ -181,25 +165,15 @@ def line_pairs(gt_rows, gt_count, gt_care, pred_rows, pred_count, recall_thr=0.8
         pred_kind[:npred] = np.where(p[:, ROW_VALID] != 0, UNMATCHED, ABSENT)
         area_g = [clamp_area(_area2(r)) for r in gt_rows[b]]
         area_p = [clamp_area(_area2(r)) for r in pred_rows[b]]
-        gi, pi = box_pairs(g, p)
-        care_pairs, margin = [], float('inf')
-        for a, c in zip(gi.tolist(), pi.tolist()):
-            inter2, _ = quad_inter2_host(g[a], p[c])
-            if care[a]:
-                care_pairs.append((a, c, inter_floor(inter2)))
-            else:
-                ap = float(_area2(p[c]))
-                need = cover_thr * ap
-                if inter2 >= need:
-                    pred_kind[c] = APART
-                if ap > 0:
-                    margin = min(margin, abs(inter2 - need) / ap)
+        pairs, covered, margin, dc_pairs = care_pairs(g, p, care, cover_thr)
+        pred_kind[:npred][covered] = APART
+        floors = [(a, c, inter_floor(inter2)) for a, c, inter2, _ in pairs]
         edges = []
-        for a, c, I in care_pairs:
+        for a, c, I in floors:
             rec, prec = 256 * I >= tr * area_g[a], 256 * I >= tp * area_p[c]
             if pred_kind[c] == UNMATCHED and I > 0 and (rec or prec):
                 edges.append((a, c, I, rec, prec))
-        out.append(LinePairs(gt_kind, pred_kind, area_g, area_p, edges, len(gi), care_pairs, margin))
+        out.append(LinePairs(gt_kind, pred_kind, area_g, area_p, edges, len(pairs) + dc_pairs, floors, margin))
     return out
 
 
@@ -314,12 +288,11 @@ def line_stats(pairs: LinePairs, gk, pk, rounds=(0, 0)) -> np.ndarray:
 
 
 def _lines_host(with_rounds, gt_rows, gt_count, gt_care, pred_rows, pred_count, recall_thr, precision_thr, cover_thr, pairs):
-    gt_rows, gt_count, gt_care, pred_rows, pred_count = _check_tables(gt_rows, gt_count, gt_care, pred_rows, pred_count)
+    (gt_rows, gt_count, pred_rows, pred_count, gt_care, _), B, M, N = host_tables(gt_rows, gt_count, pred_rows, pred_count,
+                                                                                  gt_care)
     tr, tp, cover_thr = check_line_thresholds(recall_thr, precision_thr, cover_thr)
     if pairs is None:
         pairs = line_pairs(gt_rows, gt_count, gt_care, pred_rows, pred_count, recall_thr, precision_thr, cover_thr)
-    B, M, _ = gt_rows.shape
-    N = pred_rows.shape[1]
     gt_kind, gt_group = np.zeros((B, M), np.uint8), np.full((B, M), -1, np.int32)
     pred_kind, pred_group = np.zeros((B, N), np.uint8), np.full((B, N), -1, np.int32)
     stats, rounds = np.zeros((B, STATS), np.int64), np.zeros((B, 2), np.int32)
@@ -406,29 +379,6 @@ class LineMatchResult:
         return int(self.stats[STAT_NAMES.index(name)])
 
 
-def _padded(pred: Sequence, gt: Sequence, gt_care: Optional[Sequence]):
-    pred, gt = list(pred), list(gt)
-    if len(pred) != len(gt):
-        raise ValueError(f'{len(pred)} images of predictions against {len(gt)} of annotations')
-    if gt_care is not None and len(gt_care) != len(gt):
-        raise ValueError(f'gt_care must have one entry per image, got {len(gt_care)}')
-    gq = [np.asarray(a, dtype=np.float64).reshape(-1, 4, 2) for a in gt]
-    pq = [np.asarray(a, dtype=np.float64).reshape(-1, 4, 2) for a in pred]
-    gc = [np.ones((len(a),), bool) if gt_care is None else np.asarray(gt_care[i]).reshape(-1) != 0 for i, a in enumerate(gq)]
-    if any(len(a) != len(c) for a, c in zip(gq, gc)):
-        raise ValueError('annotations must pair up with their care flags image by image')
-    B, M, N = len(gq), max([1] + [len(a) for a in gq]), max([1] + [len(a) for a in pq])
-    if M > MAX_QUADS or N > MAX_QUADS:
-        raise ValueError(f'at most {MAX_QUADS} quads per image and side, got {M} annotations / {N} predictions')
-    h_gt, h_pred, h_care = np.zeros((B, M, 4, 2), np.float64), np.zeros((B, N, 4, 2), np.float64), np.zeros((B, M), np.uint8)
-    for b in range(B):
-        h_gt[b, :len(gq[b])], h_care[b, :len(gq[b])] = gq[b], gc[b]
-        h_pred[b, :len(pq[b])] = pq[b]
-    gt_count = np.array([len(a) for a in gq], dtype=np.int32)
-    pred_count = np.array([len(a) for a in pq], dtype=np.int32)
-    return h_gt, gt_count, h_care, h_pred, pred_count
-
-
 def _line_results(gt_count, pred_count, outs, split_credit, merge_credit) -> Tuple[List[LineMatchResult], LineScore]:
     gt_kind, gt_group, pred_kind, pred_group, stats = (np.asarray(o) for o in outs[:5])
     score, results = LineScore(float(split_credit), float(merge_credit)), []
@@ -446,11 +396,9 @@ def evaluate_lines_host(pred: Sequence, gt: Sequence, gt_care: Optional[Sequence
     """What ``evaluate_lines`` returns, through ``match_rows`` and ``match_lines_host``: the slow route, for checks and for
     timing against."""
     check_line_thresholds(recall_thr, precision_thr, cover_thr)
-    h_gt, gt_count, care, h_pred, pred_count = _padded(pred, gt, gt_care)
-    B, M, N = h_gt.shape[0], h_gt.shape[1], h_pred.shape[1]
-    gt_rows = match_rows(h_gt.reshape(-1, 4, 2))[0].reshape(B, M, ROW_WORDS)
-    pred_rows = match_rows(h_pred.reshape(-1, 4, 2))[0].reshape(B, N, ROW_WORDS)
-    outs = match_lines_host(gt_rows, gt_count, care, pred_rows, pred_count, recall_thr, precision_thr, cover_thr)
+    h_gt, gt_count, care, h_pred, pred_count = padded_sides(pred, gt, gt_care)
+    outs = match_lines_host(quad_rows_host(h_gt), gt_count, care, quad_rows_host(h_pred), pred_count, recall_thr,
+                            precision_thr, cover_thr)
     return _line_results(gt_count, pred_count, outs, split_credit, merge_credit)
 
 
@@ -464,22 +412,14 @@ def evaluate_lines(pred: Sequence, gt: Sequence, gt_care: Optional[Sequence] = N
     are read back; if an image reports ``status`` the call is repeated once with the reported candidate count as capacity.
     Returns ``(per-image LineMatchResult list, LineScore over the batch)``."""
     from .. import ops
-    device = torch.device(device)
-    if device.type != 'cuda':
-        raise ValueError(f'evaluate_lines runs on the GPU, got device {device} (host route: evaluate_lines_host)')
+    device = require_gpu('evaluate_lines', device, 'evaluate_lines_host')
     check_line_thresholds(recall_thr, precision_thr, cover_thr)
-    tables = _padded(pred, gt, gt_care)
+    tables = padded_sides(pred, gt, gt_care)
     if len(tables[1]) == 0:
         return [], LineScore(float(split_credit), float(merge_credit))
     d_gt, d_gt_count, d_care, d_pred, d_pred_count = (torch.from_numpy(t).to(device, non_blocking=True) for t in tables)
     d_gt_rows, d_pred_rows = ops.quad_rows(d_gt), ops.quad_rows(d_pred)
     call = lambda cap: ops.match_lines(d_gt_rows, d_gt_count, d_care, d_pred_rows, d_pred_count, recall_thr, precision_thr,
                                        cover_thr, max_pairs=cap)
-    outs = call(None)
-    stats = outs[4].cpu().numpy()
-    if stats[:, 11].any():
-        outs = call(int(stats[:, 10].max()))
-        stats = outs[4].cpu().numpy()
-        if stats[:, 11].any():
-            raise RuntimeError('evaluate_lines: the retry with the reported capacity overflowed again')
+    outs, stats = with_capacity('evaluate_lines', call, lambda o: o[4].cpu().numpy(), np.s_[:, 11], np.s_[:, 10])
     return _line_results(tables[1], tables[4], [o.cpu().numpy() for o in outs[:4]] + [stats], split_credit, merge_credit)

@@ -59,7 +59,8 @@ import attrs
 import numpy as np
 import torch
 
-from .evaluation import MAX_QUADS, ROW_VALID, ROW_WORDS, match_rows, result_quads
+from .evaluation import ROW_VALID, ROW_WORDS, fitting_quads, match_rows
+from .quad_tables import capacity, clamped, host_table, pad_quads, pad_rows, quad_lists, require_gpu
 
 GAP_RANGE, CROSS_RANGE, RATIO_RANGE = (1, 4096), (1, 4096), (16, 256)
 TABLE_WORDS, STATS_WORDS = 8, 4
@@ -173,19 +174,13 @@ def quad_lines_host(rows, count, gap: float = 1.5, cross: float = 0.5, height_ra
     (B, K, 8) int64, stats (B, 4) int64)`` as the rule states them.  Every field of a row is used as it is, as on the
     device."""
     q = line_params(gap, cross, height_ratio)
-    rows = np.ascontiguousarray(rows, dtype=np.int32)
-    if rows.ndim != 3 or rows.shape[2] != ROW_WORDS:
-        raise ValueError(f'rows must be (B, K, {ROW_WORDS}), got {rows.shape}')
-    B, K, _ = rows.shape
-    count = np.asarray(count).reshape(-1)
-    if len(count) != B:
-        raise ValueError(f'count must be ({B},), got {count.shape}')
+    (rows, count, _), B, K = host_table(rows, count)
     line = np.full((B, K), -1, dtype=np.int32)
     order = np.full((B, K), -1, dtype=np.int32)
     table = np.zeros((B, K, TABLE_WORDS), dtype=np.int64)
     stats = np.zeros((B, STATS_WORDS), dtype=np.int64)
     for b in range(B):
-        n = min(max(int(count[b]), 0), K)
+        n = clamped(count[b], K)
         part, li, lj = link_pairs(rows[b, :n], *q)
         ln, od, tb = lines_of_links(rows[b, :n], part, li, lj)
         line[b, :n] = ln
@@ -221,13 +216,6 @@ class QuadLinesResult:
     valid: np.ndarray         # (n,) bool: the rule's validity
 
 
-def _lists(quads: Sequence) -> List[np.ndarray]:
-    q = [np.asarray(a, dtype=np.float64).reshape(-1, 4, 2) for a in quads]
-    if max([0] + [len(a) for a in q]) > MAX_QUADS:
-        raise ValueError(f'at most {MAX_QUADS} quads per image, got {max(len(a) for a in q)}')
-    return q
-
-
 def _line_results(counts, valid, line, order, table, stats):
     results = []
     for b, n in enumerate(int(c) for c in counts):
@@ -241,15 +229,11 @@ def _line_results(counts, valid, line, order, table, stats):
 def quad_lines_lists_host(quads: Sequence, gap: float = 1.5, cross: float = 0.5, height_ratio: float = 2.0):
     """What ``quad_lines`` returns, through ``match_rows`` and ``quad_lines_host``: the slow route, for checks and for timing
     against."""
-    q = _lists(quads)
+    q = quad_lists(quads)
     line_params(gap, cross, height_ratio)
     tabs = [match_rows(a) for a in q]
-    B, K = len(q), max([1] + [len(a) for a in q])
-    rows = np.zeros((B, K, ROW_WORDS), np.int32)
-    for b in range(B):
-        rows[b, :len(q[b])] = tabs[b][0]
-    count = np.array([len(a) for a in q], dtype=np.int32)
-    if B == 0:
+    rows, count = pad_rows([r for r, _ in tabs])
+    if len(q) == 0:
         return [], np.zeros((STATS_WORDS,), np.int64)
     return _line_results(count, [v for _, v in tabs], *quad_lines_host(rows, count, gap, cross, height_ratio))
 
@@ -260,19 +244,14 @@ def quad_lines(quads: Sequence, gap: float = 1.5, cross: float = 0.5, height_rat
     their outputs come back in one buffer.  Returns ``(per-image QuadLinesResult list, stats (4,) int64 summed over the
     images: n, n_part, links, lines)``."""
     from .. import ops
-    device = torch.device(device)
-    if device.type != 'cuda':
-        raise ValueError(f'quad_lines runs on the GPU, got device {device} (host route: quad_lines_lists_host)')
+    device = require_gpu('quad_lines', device, 'quad_lines_lists_host')
     line_params(gap, cross, height_ratio)
-    q = _lists(quads)
-    B, K = len(q), max([1] + [len(a) for a in q])
+    q = quad_lists(quads)
+    B, K = len(q), capacity(q)
     if B == 0:
         return [], np.zeros((STATS_WORDS,), np.int64)
-    up = np.zeros((B * K * 64 + B * 4,), np.uint8)
-    h_quads, count = up[:B * K * 64].view(np.float64).reshape(B, K, 4, 2), up[B * K * 64:].view(np.int32)
-    for b in range(B):
-        h_quads[b, :len(q[b])] = q[b]
-        count[b] = len(q[b])
+    up = np.zeros((B * K * 64 + B * 4,), np.uint8)  # quads and counts go up in one buffer: the builder fills its two views
+    _, count = pad_quads(q, up[:B * K * 64].view(np.float64).reshape(B, K, 4, 2), up[B * K * 64:].view(np.int32))
     d_up = torch.from_numpy(up).to(device, non_blocking=True)
     d_quads, d_count = d_up[:B * K * 64].view(torch.float64).view(B, K, 4, 2), d_up[B * K * 64:].view(torch.int32)
     d_rows = ops.quad_rows(d_quads)
@@ -292,10 +271,9 @@ def group_results(results: Sequence, gap: float = 1.5, cross: float = 0.5, heigh
     together, go through ONE ``quad_lines`` call, each image on its own; the results come back with ``char_lines``,
     ``line_chars`` and ``line_polygons`` filled.  An image with more than ``MAX_QUADS`` characters gets ``lines_status = 2``
     and no lines."""
-    tabs = [result_quads(r)[0] for r in results]
-    fits = [i for i, t in enumerate(tabs) if len(t) <= MAX_QUADS]
+    tabs, fits = fitting_quads(results)
     out = [attrs.evolve(r, lines_status=2) for r in results]
-    res, _ = quad_lines([tabs[i] for i in fits], gap, cross, height_ratio, device=device)
+    res, _ = quad_lines([tabs[i][0] for i in fits], gap, cross, height_ratio, device=device)
     for i, r in zip(fits, res):
         out[i] = attrs.evolve(results[i], char_lines=r.line, line_chars=r.lines, line_polygons=r.polygons, lines_status=0)
     return out

@@ -40,7 +40,8 @@ import attrs
 import numpy as np
 import torch
 
-from .evaluation import MAX_QUADS, ROW_VALID, ROW_WORDS, _check_thr, match_rows, quad_iou_host, result_quads
+from .evaluation import ROW_VALID, ROW_WORDS, check_iou_thr, fitting_quads, match_rows, quad_iou_host
+from .quad_tables import clamped, host_table, pad_quads, pad_rows, pad_values, quad_lists, require_gpu, with_capacity
 
 
 def nms_pairs(rows: np.ndarray, probs: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -85,20 +86,13 @@ def nms_quads_host(rows, count, probs, iou_thr: float = 0.5):
     """The oracle of ``ops.nms_quads``: ``rows`` (B, K, 16), ``count`` (B,), ``probs`` (B, K) -> ``(keep (B, K) uint8,
     suppressor (B, K) int32, stats (B, 6) int64)`` with ``stats`` = kept, n, n_valid, pairs, candidates, status (always 0
     here: the host has no capacity).  Every field of a row is used as it is, as on the device."""
-    rows = np.ascontiguousarray(rows, dtype=np.int32)
-    if rows.ndim != 3 or rows.shape[2] != ROW_WORDS:
-        raise ValueError(f'rows must be (B, K, {ROW_WORDS}), got {rows.shape}')
-    B, K, _ = rows.shape
-    count = np.asarray(count).reshape(-1)
-    probs = np.ascontiguousarray(probs, dtype=np.float32)
-    if len(count) != B or probs.shape != (B, K):
-        raise ValueError(f'count must be ({B},) and probs ({B}, {K}), got {count.shape} and {probs.shape}')
-    thr = _check_thr(iou_thr)
+    (rows, count, probs), B, K = host_table(rows, count, probs)
+    thr = check_iou_thr(iou_thr)
     keep = np.zeros((B, K), dtype=np.uint8)
     suppressor = np.full((B, K), -1, dtype=np.int32)
     stats = np.zeros((B, 6), dtype=np.int64)
     for b in range(B):
-        n = min(max(int(count[b]), 0), K)
+        n = clamped(count[b], K)
         r, p = rows[b, :n], probs[b, :n]
         part, pi, pj = nms_pairs(r, p)
         edges = [(i, j) for i, j in zip(pi.tolist(), pj.tolist()) if quad_iou_host(r[i], r[j]) >= thr]
@@ -118,35 +112,25 @@ class QuadNmsResult:
 def nms_tables(quads: Sequence, probs: Sequence, score_thr: Optional[float] = None):
     """The host half of ``nms_quads_lists_host`` (the device route builds its rows on the device): per-image arrays ->
     ``(rows (B, K, 16), count (B,), probs (B, K) float32, valid)`` with K the batch's largest count (at least 1)."""
-    q, p, present = _lists(quads, probs, score_thr)
-    tabs = [match_rows(a, v) for a, v in zip(q, present)]
-    B, K = len(q), max([1] + [len(a) for a in q])
-    rows, pr = np.zeros((B, K, ROW_WORDS), np.int32), np.zeros((B, K), np.float32)
-    for b in range(B):
-        rows[b, :len(q[b])], pr[b, :len(q[b])] = tabs[b][0], p[b]
-    return rows, np.array([len(a) for a in q], dtype=np.int32), pr, [v for _, v in tabs]
+    q, pr, present = _scored(quads, probs, score_thr)
+    tabs = [match_rows(a, None if present is None else present[b]) for b, a in enumerate(q)]
+    return (*pad_rows([r for r, _ in tabs]), pr, [v for _, v in tabs])
 
 
-def _lists(quads: Sequence, probs: Sequence, score_thr: Optional[float]):
-    quads, probs = list(quads), list(probs)
-    if len(quads) != len(probs):
-        raise ValueError(f'{len(quads)} images of quads against {len(probs)} of probs')
-    q = [np.asarray(a, dtype=np.float64).reshape(-1, 4, 2) for a in quads]
-    p = [np.asarray(a, dtype=np.float32).reshape(-1) for a in probs]
-    if any(len(a) != len(s) for a, s in zip(q, p)):
-        raise ValueError('quads and probs of an image must pair up')
-    if max([0] + [len(a) for a in q]) > MAX_QUADS:
-        raise ValueError(f'at most {MAX_QUADS} quads per image, got {max(len(a) for a in q)}')
+def _scored(quads: Sequence, probs: Sequence, score_thr: Optional[float]):
+    """-> ``(quad lists, probs (B, K) float32, present)``: per image the quads at or above ``score_thr``, None without one"""
+    q = quad_lists(quads)
+    pr = pad_values(q, probs, np.float32, 'probs')
     # as in evaluation_tables: compared in binary64, NaN compares false
-    present = [None if score_thr is None else s.astype(np.float64) >= float(score_thr) for s in p]
-    return q, p, present
+    present = None if score_thr is None else [pr[b, :len(a)].astype(np.float64) >= float(score_thr) for b, a in enumerate(q)]
+    return q, pr, present
 
 
 def _nms_results(counts, present, valid, keep, suppressor, stats):
     results = []
     for b, n in enumerate(int(c) for c in counts):
         k = keep[b, :n].astype(bool)
-        if present[b] is not None:  # below the score threshold: absent, not passed through
+        if present is not None:  # below the score threshold: absent, not passed through
             k &= present[b]
         results.append(QuadNmsResult(k, suppressor[b, :n].copy(), np.asarray(valid[b], dtype=bool)))
     total = stats.sum(axis=0) if len(stats) else np.zeros((6,), np.int64)
@@ -159,8 +143,7 @@ def nms_quads_lists_host(quads: Sequence, probs: Sequence, iou_thr: float = 0.5,
     """What ``nms_quads`` returns, through ``match_rows`` and ``nms_quads_host``: the slow route, for checks and for timing
     against."""
     rows, count, pr, valid = nms_tables(quads, probs, score_thr)
-    present = _lists(quads, probs, score_thr)[2]
-    return _nms_results(count, present, valid, *nms_quads_host(rows, count, pr, iou_thr))
+    return _nms_results(count, _scored(quads, probs, score_thr)[2], valid, *nms_quads_host(rows, count, pr, iou_thr))
 
 
 def nms_quads(quads: Sequence, probs: Sequence, iou_thr: float = 0.5, score_thr: Optional[float] = None, device='cuda'):
@@ -171,31 +154,19 @@ def nms_quads(quads: Sequence, probs: Sequence, iou_thr: float = 0.5, score_thr:
     ``status`` the suppression is repeated once with the reported candidate count as capacity.  Returns ``(per-image
     QuadNmsResult list, stats (6,) int64 summed over the images: kept, n, n_valid, pairs, candidates, status)``."""
     from .. import ops
-    device = torch.device(device)
-    if device.type != 'cuda':
-        raise ValueError(f'nms_quads runs on the GPU, got device {device} (host route: nms_quads_lists_host)')
-    _check_thr(iou_thr)
-    q, p, present = _lists(quads, probs, score_thr)
-    B, K = len(q), max([1] + [len(a) for a in q])
+    device = require_gpu('nms_quads', device, 'nms_quads_lists_host')
+    check_iou_thr(iou_thr)
+    q, h_probs, present = _scored(quads, probs, score_thr)
+    B = len(q)
     if B == 0:
         return [], np.zeros((6,), np.int64)
-    h_quads, h_probs = np.zeros((B, K, 4, 2), np.float64), np.zeros((B, K), np.float32)
-    h_valid = np.zeros((B, K), np.uint8)
-    for b in range(B):
-        n = len(q[b])
-        h_quads[b, :n], h_probs[b, :n] = q[b], p[b]
-        h_valid[b, :n] = 1 if present[b] is None else present[b]
-    count = np.array([len(a) for a in q], dtype=np.int32)
+    h_quads, count = pad_quads(q)
+    h_valid = pad_values(q, present, np.uint8, 'valid')
     d_quads, d_probs, d_valid, d_count = (torch.from_numpy(t).to(device, non_blocking=True)
                                           for t in (h_quads, h_probs, h_valid, count))
     d_rows = ops.quad_rows(d_quads, d_valid)
-    outs = ops.nms_quads(d_rows, d_count, d_probs, iou_thr=iou_thr)
-    stats = outs[2].cpu().numpy()
-    if stats[:, 5].any():
-        outs = ops.nms_quads(d_rows, d_count, d_probs, iou_thr=iou_thr, max_pairs=int(stats[:, 4].max()))
-        stats = outs[2].cpu().numpy()
-        if stats[:, 5].any():
-            raise RuntimeError('nms_quads: the retry with the reported capacity overflowed again')
+    outs, stats = with_capacity('nms_quads', lambda cap: ops.nms_quads(d_rows, d_count, d_probs, iou_thr=iou_thr, max_pairs=cap),
+                                lambda o: o[2].cpu().numpy(), np.s_[:, 5], np.s_[:, 4])
     valid = (d_rows[:, :, ROW_VALID] != 0).cpu().numpy()
     return _nms_results(count, present, [valid[b, :count[b]] for b in range(B)], outs[0].cpu().numpy(),
                         outs[1].cpu().numpy(), stats)
@@ -223,8 +194,7 @@ def filter_result(result, keep):
 def suppress_results(results: Sequence, iou_thr: float, device='cuda') -> list:
     """The step of ``infer`` / ``infer_batch``: the characters of every result go through ONE ``nms_quads`` call, each image
     on its own; an image with more than ``MAX_QUADS`` characters is left as it is with ``nms_status = 2``."""
-    tabs = [result_quads(r) for r in results]
-    fits = [i for i, (q, _) in enumerate(tabs) if len(q) <= MAX_QUADS]
+    tabs, fits = fitting_quads(results)
     out = [attrs.evolve(r, nms_status=2) for r in results]
     if any(len(tabs[i][0]) for i in fits):
         res, _ = nms_quads([tabs[i][0] for i in fits], [tabs[i][1] for i in fits], iou_thr, device=device)

@@ -18,7 +18,8 @@ order of inferencing/nms.py.
 
 Pair quantities, for the pairs whose Q4 boxes overlap (the inclusive test of ``box_pairs``, both rows taking part): ONE clip
 of p against g in ``quad_iou_host``'s order of operations gives ``inter2`` after its clamp, and
-``iou = inter2 / ((area2_g + area2_p) - inter2)``: ``quad_inter2_host``, whose iou is ``quad_iou_host``'s bit for bit.
+``iou = inter2 / ((area2_g + area2_p) - inter2)``: ``quad_inter2_host`` of inferencing/evaluation.py, whose second result
+``quad_iou_host`` is.  The pass over the pairs (``care_pairs``) is shared with inferencing/line_evaluation.py.
 
 Covered: pred p is covered iff some don't-care gt g has ``inter2(g, p) >= cover_thr * area2_p`` (the product rounded once,
 the comparison inclusive).  Coverage does not depend on the IoU threshold.  A don't-care gt is never matched and does not
@@ -70,43 +71,12 @@ import attrs
 import numpy as np
 import torch
 
-from .evaluation import (MAX_QUADS, ROW_VALID, ROW_WORDS, _area2, _clip, box_pairs, match_rows)
+from .evaluation import ROW_VALID, care_pairs, quad_inter2_host, quad_rows_host  # noqa: F401 (the clip: importable here too)
+from .quad_tables import clamped, host_tables, padded_sides, require_gpu, with_capacity
 
 ABSENT, TP, FP, IGNORED = 0, 1, 2, 3
 MAX_THRS = 16
 DEFAULT_IOU_THRS = tuple(0.5 + 0.05 * i for i in range(10))
-
-
-def quad_inter2_host(g_row, p_row) -> Tuple[float, float]:
-    """Two match rows (16 int32 each), both taken as valid -> ``(inter2, iou)``: twice the area of the intersection after
-    the rule's clamp and the rule's IoU, from one clip (``(0.0, 0.0)`` when the boxes do not overlap).  The iou is
-    ``quad_iou_host``'s bit for bit: the same operations in the same order."""
-    g = [int(v) for v in np.asarray(g_row).reshape(ROW_WORDS)]
-    p = [int(v) for v in np.asarray(p_row).reshape(ROW_WORDS)]
-    if g[8] > p[10] or p[8] > g[10] or g[9] > p[11] or p[9] > g[11]:
-        return 0.0, 0.0
-    oy, ox = min(g[8], p[8]), min(g[9], p[9])
-    gq = [(float(g[2 * k] - oy), float(g[2 * k + 1] - ox)) for k in range(4)]
-    ring = [(float(p[2 * k] - oy), float(p[2 * k + 1] - ox)) for k in range(4)]
-    for k in range(4):
-        (ay, ax), (by, bx) = gq[k], gq[(k + 1) % 4]
-        ring = _clip(ring, ay, ax, by, bx)
-    acc = 0.0
-    n = len(ring)
-    for k in range(n):
-        (y0, x0), (y1, x1) = ring[k], ring[(k + 1) % n]
-        m0 = x0 * y1
-        m1 = x1 * y0
-        acc = acc + (m0 - m1)
-    ag, ap = float(_area2(np.asarray(g_row))), float(_area2(np.asarray(p_row)))
-    hi = ap if ap < ag else ag
-    inter2 = acc
-    if inter2 > hi:
-        inter2 = hi
-    if inter2 < 0.0:
-        inter2 = 0.0
-    den = (ag + ap) - inter2
-    return inter2, (inter2 / den if den > 0.0 else 0.0)
 
 
 def check_thresholds(iou_thrs, cover_thr=0.5) -> Tuple[Tuple[float, ...], float]:
@@ -210,70 +180,38 @@ class RankedPairs:
     dc_pairs: int
 
 
-def _check_tables(gt_rows, gt_count, gt_care, pred_rows, pred_count, probs):
-    gt_rows = np.ascontiguousarray(gt_rows, dtype=np.int32)
-    pred_rows = np.ascontiguousarray(pred_rows, dtype=np.int32)
-    if gt_rows.ndim != 3 or gt_rows.shape[2] != ROW_WORDS or pred_rows.ndim != 3 or pred_rows.shape[2] != ROW_WORDS:
-        raise ValueError(f'rows must be (B, K, {ROW_WORDS}), got {gt_rows.shape} and {pred_rows.shape}')
-    B, M, _ = gt_rows.shape
-    N = pred_rows.shape[1]
-    gt_count, pred_count = np.asarray(gt_count).reshape(-1), np.asarray(pred_count).reshape(-1)
-    probs = np.ascontiguousarray(probs, dtype=np.float32)
-    gt_care = np.ones((B, M), np.uint8) if gt_care is None else np.ascontiguousarray(gt_care, dtype=np.uint8)
-    if pred_rows.shape[0] != B or len(gt_count) != B or len(pred_count) != B:
-        raise ValueError('tables and counts must share the batch size')
-    if probs.shape != (B, N) or gt_care.shape != (B, M):
-        raise ValueError(f'probs must be ({B}, {N}) and gt_care ({B}, {M}), got {probs.shape} and {gt_care.shape}')
-    return gt_rows, gt_count, gt_care, pred_rows, pred_count, probs
-
-
 def ranked_pairs(gt_rows, gt_count, gt_care, pred_rows, pred_count, probs, iou_thrs, cover_thr: float = 0.5
                  ) -> List[RankedPairs]:
     """The clip of every box pair, once: per image the preds that take part, the coverage and the care candidates.  Both
     oracles take its result as ``pairs=`` so that a test computes it once."""
-    gt_rows, gt_count, gt_care, pred_rows, pred_count, probs = _check_tables(gt_rows, gt_count, gt_care, pred_rows,
-                                                                             pred_count, probs)
+    (gt_rows, gt_count, pred_rows, pred_count, gt_care, probs), B, M, N = host_tables(gt_rows, gt_count, pred_rows, pred_count,
+                                                                                      gt_care, probs)
     thrs, cover_thr = check_thresholds(iou_thrs, cover_thr)
-    B, M, _ = gt_rows.shape
-    N = pred_rows.shape[1]
     out = []
     for b in range(B):
-        ng, npred = min(max(int(gt_count[b]), 0), M), min(max(int(pred_count[b]), 0), N)
+        ng, npred = clamped(gt_count[b], M), clamped(pred_count[b], N)
         g, care = gt_rows[b, :ng], gt_care[b, :ng] != 0
         part = np.zeros((N,), dtype=bool)
         part[:npred] = (pred_rows[b, :npred, ROW_VALID] != 0) & np.isfinite(probs[b, :npred])
         p = pred_rows[b, :npred].copy()
-        p[~part[:npred], ROW_VALID] = 0
-        gi, pi = box_pairs(g, p)
-        covered, edges, ious, margin, dc_pairs = np.zeros((N,), np.uint8), [], [], math.inf, 0
-        for a, c in zip(gi.tolist(), pi.tolist()):
-            inter2, iou = quad_inter2_host(g[a], p[c])
-            if care[a]:
-                ious.append(iou)
-                if iou >= thrs[0]:
-                    edges.append((a, c, iou))
-            else:
-                dc_pairs += 1
-                ap = float(_area2(p[c]))
-                need = cover_thr * ap
-                if inter2 >= need:
-                    covered[c] = 1
-                if ap > 0:
-                    margin = min(margin, abs(inter2 - need) / ap)
+        p[~part[:npred], ROW_VALID] = 0  # a pred without a finite prob takes no part: before the box pairs
+        pairs, cover, margin, dc_pairs = care_pairs(g, p, care, cover_thr)
+        covered = np.zeros((N,), np.uint8)
+        covered[:npred] = cover
         valid_g = g[:, ROW_VALID] != 0
-        out.append(RankedPairs(part, covered, edges, np.array(ious, np.float64), margin, int((valid_g & care).sum()),
-                               int((valid_g & ~care).sum()), len(ious), dc_pairs))
+        out.append(RankedPairs(part, covered, [(a, c, iou) for a, c, _, iou in pairs if iou >= thrs[0]],
+                               np.array([iou for _, _, _, iou in pairs], np.float64), margin, int((valid_g & care).sum()),
+                               int((valid_g & ~care).sum()), len(pairs), dc_pairs))
     return out
 
 
 def _ranked_host(matching, with_rounds, gt_rows, gt_count, gt_care, pred_rows, pred_count, probs, iou_thrs, cover_thr, pairs):
-    gt_rows, gt_count, gt_care, pred_rows, pred_count, probs = _check_tables(gt_rows, gt_count, gt_care, pred_rows,
-                                                                             pred_count, probs)
+    (gt_rows, gt_count, pred_rows, pred_count, gt_care, probs), B, M, N = host_tables(gt_rows, gt_count, pred_rows, pred_count,
+                                                                                      gt_care, probs)
     thrs, cover_thr = check_thresholds(iou_thrs, cover_thr)
     if pairs is None:
         pairs = ranked_pairs(gt_rows, gt_count, gt_care, pred_rows, pred_count, probs, thrs, cover_thr)
-    B, M, _ = gt_rows.shape
-    N, T = pred_rows.shape[1], len(thrs)
+    T = len(thrs)
     pred_match, gt_match = np.full((B, T, N), -1, np.int32), np.full((B, T, M), -1, np.int32)
     pred_state, pred_iou = np.zeros((B, T, N), np.uint8), np.zeros((B, T, N), np.float64)
     covered, stats, dc_stats = np.zeros((B, N), np.uint8), np.zeros((B, T, 8), np.int64), np.zeros((B, 3), np.int64)
@@ -409,31 +347,6 @@ class RankedMatchResult:
     dc_stats: np.ndarray    # (3,) int64
 
 
-def _padded(pred: Sequence, gt: Sequence, pred_scores: Sequence, gt_care: Optional[Sequence]):
-    pred, gt, pred_scores = list(pred), list(gt), list(pred_scores)
-    if len(pred) != len(gt) or len(pred_scores) != len(pred):
-        raise ValueError(f'{len(pred)} images of predictions and {len(pred_scores)} of scores against {len(gt)} of annotations')
-    if gt_care is not None and len(gt_care) != len(gt):
-        raise ValueError(f'gt_care must have one entry per image, got {len(gt_care)}')
-    gq = [np.asarray(a, dtype=np.float64).reshape(-1, 4, 2) for a in gt]
-    pq = [np.asarray(a, dtype=np.float64).reshape(-1, 4, 2) for a in pred]
-    ps = [np.asarray(a, dtype=np.float32).reshape(-1) for a in pred_scores]
-    gc = [np.ones((len(a),), bool) if gt_care is None else np.asarray(gt_care[i]).reshape(-1) != 0 for i, a in enumerate(gq)]
-    if any(len(a) != len(s) for a, s in zip(pq, ps)) or any(len(a) != len(c) for a, c in zip(gq, gc)):
-        raise ValueError('quads must pair up with their scores and care flags image by image')
-    B, M, N = len(gq), max([1] + [len(a) for a in gq]), max([1] + [len(a) for a in pq])
-    if M > MAX_QUADS or N > MAX_QUADS:
-        raise ValueError(f'at most {MAX_QUADS} quads per image and side, got {M} annotations / {N} predictions')
-    h_gt, h_pred = np.zeros((B, M, 4, 2), np.float64), np.zeros((B, N, 4, 2), np.float64)
-    h_care, h_probs = np.zeros((B, M), np.uint8), np.zeros((B, N), np.float32)
-    for b in range(B):
-        h_gt[b, :len(gq[b])], h_care[b, :len(gq[b])] = gq[b], gc[b]
-        h_pred[b, :len(pq[b])], h_probs[b, :len(pq[b])] = pq[b], ps[b]
-    gt_count = np.array([len(a) for a in gq], dtype=np.int32)
-    pred_count = np.array([len(a) for a in pq], dtype=np.int32)
-    return h_gt, gt_count, h_care, h_pred, pred_count, h_probs
-
-
 def ranked_score(outs, pred_count, probs, iou_thrs) -> RankedScore:
     """The outputs of the op or of an oracle, the counts and the (B, N) probs -> the batch's ``RankedScore``."""
     pred_state, stats = np.asarray(outs[1]), np.asarray(outs[5])
@@ -464,11 +377,9 @@ def evaluate_quads_ranked_host(pred: Sequence, gt: Sequence, pred_scores: Sequen
     """What ``evaluate_quads_ranked`` returns, through ``match_rows`` and ``match_quads_ranked_host``: the slow route, for
     checks and for timing against."""
     thrs, cover_thr = check_thresholds(iou_thrs, cover_thr)
-    tables = _padded(pred, gt, pred_scores, gt_care)
+    tables = padded_sides(pred, gt, gt_care, pred_scores)
     h_gt, gt_count, care, h_pred, pred_count, probs = tables
-    B, M, N = h_gt.shape[0], h_gt.shape[1], h_pred.shape[1]
-    gt_rows = match_rows(h_gt.reshape(-1, 4, 2))[0].reshape(B, M, ROW_WORDS)
-    pred_rows = match_rows(h_pred.reshape(-1, 4, 2))[0].reshape(B, N, ROW_WORDS)
+    gt_rows, pred_rows = quad_rows_host(h_gt), quad_rows_host(h_pred)
     outs = match_quads_ranked_host(gt_rows, gt_count, care, pred_rows, pred_count, probs, thrs, cover_thr)
     return _ranked_results(tables, gt_rows[:, :, ROW_VALID] != 0, (pred_rows[:, :, ROW_VALID] != 0) & np.isfinite(probs), outs,
                            thrs)
@@ -483,11 +394,9 @@ def evaluate_quads_ranked(pred: Sequence, gt: Sequence, pred_scores: Sequence, g
     are read back; if an image reports ``status`` the call is repeated once with the reported candidate count as capacity.
     Returns ``(per-image RankedMatchResult list, RankedScore over the batch)``."""
     from .. import ops
-    device = torch.device(device)
-    if device.type != 'cuda':
-        raise ValueError(f'evaluate_quads_ranked runs on the GPU, got device {device} (host route: evaluate_quads_ranked_host)')
+    device = require_gpu('evaluate_quads_ranked', device, 'evaluate_quads_ranked_host')
     thrs, cover_thr = check_thresholds(iou_thrs, cover_thr)
-    tables = _padded(pred, gt, pred_scores, gt_care)
+    tables = padded_sides(pred, gt, gt_care, pred_scores)
     if len(tables[1]) == 0:
         return [], ranked_score((None, np.zeros((0, len(thrs), 1), np.uint8), None, None, None,
                                  np.zeros((0, len(thrs), 8), np.int64)), tables[4], tables[5], thrs)
@@ -496,13 +405,7 @@ def evaluate_quads_ranked(pred: Sequence, gt: Sequence, pred_scores: Sequence, g
     d_gt_rows, d_pred_rows = ops.quad_rows(d_gt), ops.quad_rows(d_pred)
     call = lambda cap: ops.match_quads_ranked(d_gt_rows, d_gt_count, d_care, d_pred_rows, d_pred_count, d_probs, thrs,
                                               cover_thr, max_pairs=cap)
-    outs = call(None)
-    stats = outs[5].cpu().numpy()
-    if stats[:, 0, 7].any():
-        outs = call(int(stats[:, 0, 6].max()))
-        stats = outs[5].cpu().numpy()
-        if stats[:, 0, 7].any():
-            raise RuntimeError('evaluate_quads_ranked: the retry with the reported capacity overflowed again')
+    outs, _ = with_capacity('evaluate_quads_ranked', call, lambda o: o[5].cpu().numpy(), np.s_[:, 0, 7], np.s_[:, 0, 6])
     gt_valid = (d_gt_rows[:, :, ROW_VALID] != 0).cpu().numpy()
     pred_valid = (d_pred_rows[:, :, ROW_VALID] != 0).cpu().numpy() & np.isfinite(tables[5])
     return _ranked_results(tables, gt_valid, pred_valid, [o.cpu().numpy() for o in outs], thrs)

@@ -2563,9 +2563,8 @@ def match_quads(gt_rows: torch.Tensor, gt_count: torch.Tensor, pred_rows: torch.
     candidates than ``max_pairs`` keeps its true ``pairs`` and ``candidates`` and gets ``status = 1``, every match -1 and
     ``tp = 0``.  ``rounds``, if given, is a (B,) int32 device tensor that receives the matching rounds of each image.  Four
     launches; never synchronises, so it can be captured into a HIP graph."""
-    iou_thr = float(iou_thr)
-    if not (iou_thr > 0.0 and iou_thr <= 1.0):
-        raise ValueError(f'match_quads: iou_thr must lie in (0, 1], got {iou_thr}')
+    from .inferencing.evaluation import check_iou_thr  # the rule's own check, stated once
+    iou_thr = check_iou_thr(iou_thr, 'match_quads')
     (gt_rows, gt_count, pred_rows, pred_count, _, _), B, M, N, max_pairs = _quad_tables(
         'match_quads', gt_rows, gt_count, pred_rows, pred_count, max_pairs, rounds)
     dev = gt_rows.device
@@ -2684,9 +2683,8 @@ def nms_quads(rows: torch.Tensor, count: torch.Tensor, probs: torch.Tensor, iou_
     true ``pairs`` and ``candidates`` and gets ``status = 1``, every quad within the count kept and every suppressor -1.
     ``rounds``, if given, is a (B,) int32 device tensor that receives the rounds of each image.  Four launches; never
     synchronises, so it can be captured into a HIP graph."""
-    iou_thr = float(iou_thr)
-    if not (iou_thr > 0.0 and iou_thr <= 1.0):
-        raise ValueError(f'nms_quads: iou_thr must lie in (0, 1], got {iou_thr}')
+    from .inferencing.evaluation import check_iou_thr  # the rule's own check, stated once
+    iou_thr = check_iou_thr(iou_thr, 'nms_quads')
     (rows, count, probs), B, K, max_pairs = _quad_table('nms_quads', rows, count, probs, max_pairs, rounds)
     dev = rows.device
     keep = torch.empty((B, K), dtype=torch.uint8, device=dev)
