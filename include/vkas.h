@@ -681,6 +681,32 @@ int vkas_line_match(const int* gt_rows, const int* gt_count, const unsigned char
                     const int* pred_count, int B, int M, int N, int tr_q8, int tp_q8, double cover_thr, int max_pairs,
                     void* workspace, size_t workspace_bytes, unsigned char* gt_kind, int* gt_group, unsigned char* pred_kind,
                     int* pred_group, long long* stats, int* rounds, void* stream);
+/* Scoring curved text lines as ribbons of quads (inferencing/ribbon_evaluation.py holds the rule - this project's own - and
+ * the host oracles match_ribbons_host, the sequential form, and match_ribbons_rounds_host).  Per side a ribbon table
+ * (B,K,16) int32 with counts as for vkas_line_match and a segment table (B,S,16) int32 of match rows.  A ribbon row: word 0 =
+ * seg_start, an index into its image's segment table; word 1 = seg_count in 1..256; words 2..7 zero; 8..11 the union of the
+ * segment boxes; 12..13 the sum of the segments' area2 as one int64; 14 valid; 15 zero.  For a pair of ribbons that both take
+ * part and whose boxes overlap, I = min(sum over the segment pairs (i, j) whose boxes overlap and whose valid words are set
+ * of int64(floor(min(inter2(gseg_i, pseg_j), 2^41))), 2^41), inter2 from the one clip of vkas_quad_match on the two segment
+ * rows; the sum is over integers.  Everything else is vkas_line_match's with this I in place of floor(inter2): the coverage
+ * test of a don't-care gt is (double)I >= cover_thr * area2_p, A_g and A_p are the clamped areas of the ribbon rows, and the
+ * tests, the phases, the outputs, stats, rounds, capacity and status are those of vkas_line_match word for word.  A ribbon
+ * row with seg_count outside 1..256, seg_start < 0 or seg_start + seg_count > S has no segments (every I with it is 0) and
+ * still takes part as its valid word says; both are checked against S before any use as an index.  Segment boxes and areas
+ * are believed as written.  Four launches on one stream (counting pass over 64 x 64 tiles of ribbons with one wave per listed
+ * pair, its lanes striding over the segment pairs; scan; filling pass, which computes I again for the candidates only;
+ * the phases); integer atomics in LDS only, no allocation, no synchronisation, every output element and every workspace
+ * word that is read is written by the call's own kernels: capture-safe and bit-identical from run to run; reads are bounded
+ * by the tables and stores by the buffers whatever the tables hold.  B in 0..65535, M and N in 1..8192, Sg and Sp in
+ * 1..2^21 (beyond: an error, not a clamp), max_pairs >= 0, B*max_pairs < 2^31; all four tables and the workspace 16-byte
+ * aligned, stats 8-byte aligned, workspace at least vkas_ribbon_match_workspace_bytes (-1 on bad arguments; the size is that
+ * of vkas_line_match).  Argument errors return before any launch. */
+long long vkas_ribbon_match_workspace_bytes(int B, int M, int N, int max_pairs);
+int vkas_ribbon_match(const int* gt_rows, const int* gt_count, const unsigned char* gt_care, const int* gt_segs, int Sg,
+                      const int* pred_rows, const int* pred_count, const int* pred_segs, int Sp, int B, int M, int N, int tr_q8,
+                      int tp_q8, double cover_thr, int max_pairs, void* workspace, size_t workspace_bytes,
+                      unsigned char* gt_kind, int* gt_group, unsigned char* pred_kind, int* pred_group, long long* stats,
+                      int* rounds, void* stream);
 /* Grouping character quadrilaterals into text lines (inferencing/lines.py holds the rule - this project's own, all integer -
  * and the host oracle quad_lines_host).  rows (B,K,16) int32 match rows, count (B) clamped to [0, K] on the device; gap_q4
  * and cross_q4 in 1..4096, ratio_q4 in 16..256 (Q4).  A row takes part iff it lies within the count and its valid word is

@@ -209,6 +209,9 @@ _SIGS = {
     'vkas_line_match_workspace_bytes': (c_longlong, [c_int, c_int, c_int, c_int]),
     'vkas_line_match': (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_double, c_int, _P, c_size_t, _P, _P, _P,
                                 _P, _P, _P, _P]),
+    'vkas_ribbon_match_workspace_bytes': (c_longlong, [c_int, c_int, c_int, c_int]),
+    'vkas_ribbon_match': (c_int, [_P, _P, _P, _P, c_int, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_int,
+                                  _P, c_size_t, _P, _P, _P, _P, _P, _P, _P]),
     'vkas_quad_lines_workspace_bytes': (c_longlong, [c_int, c_int]),
     'vkas_quad_lines': (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P, c_size_t, _P, _P, _P, _P, _P]),
     'vkas_text_regions_workspace_bytes': (c_longlong, [c_int, c_int, c_int, c_int]),

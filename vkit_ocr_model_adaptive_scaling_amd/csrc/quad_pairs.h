@@ -1,5 +1,6 @@
 // The three passes over pairs of match rows that every pair-based op runs before its own rounds kernel (quadmatch.hip: the
-// one-to-one, the self and the ranked matching of character quads; linematch.hip: the text-line score), stated once:
+// one-to-one, the self and the ranked matching of character quads; linematch.hip: the text-line score; ribbonmatch.hip:
+// the same score with every line a ribbon of quads), stated once:
 //
 //   count  qp_tile<false>  a 128-thread workgroup owns a 64 gt x 64 pred tile of one image.  The boxes and valid words of its
 //                          128 rows go to LDS; wave w box-tests gts [32w, 32w + 32) against pred = lane and appends the
@@ -26,6 +27,11 @@
 //   status(b)                     the image's status word, as the scan left it
 //   pair<FILL>(s, g3, p3, pj, iou, inter2, val)   what a clipped pair means: true = a candidate, val = what its slot holds
 //                                 beside the pred; side effects go to s (counting pass only)
+//   PAIR_LANES, group_inter2(g, p, b, ring, lane)   1: a listed pair is one thread's work and its quantity the clip of the
+//                                 two rows (qm_inter2_iou).  L = 2..64, a power of two: a listed pair is the work of L
+//                                 neighbouring lanes of one wave, the rule computes the quantity itself from the two
+//                                 LDS rows (all L lanes call with lane = 0..L-1 and all get the same value; iou is 0),
+//                                 and lane 0 of the group alone goes on to pair() and the store
 //   store(at, pred, val)          fills slot `at` (image and slot in one index)
 //   apart(s)                      the tile's pairs that its pair count leaves out
 //   tile_out(s, tile, tid)        the rule's outputs per tile; an empty tile takes the same path with s as begin left it
@@ -54,6 +60,7 @@ struct QpTables {
 };
 
 struct QpRule {
+  static constexpr int PAIR_LANES = 1;
   struct Tile {};
   template <class S> __device__ __forceinline__ void begin(S&, int) const {}
   __device__ __forceinline__ void fix(int4&, bool, int, int, int, int, int) const {}
@@ -144,19 +151,29 @@ __device__ __forceinline__ void qp_tile(const QpTables& t, const Rule& r) {
   }
   stage(0);
   __syncthreads();
-  for (int e = tid; e < total; e += QM_THREADS) {
-    const int q = e < c0 ? s_list[e] : s_list[QM_LIST + e - c0];
-    const int gi = q >> 6, pj = q & 63;
-    double inter2;
-    const double iou = qm_inter2_iou(s_rows + gi * 4, s_rows + (QM_TILE + pj) * 4, s_ring + tid, &inter2);
+  const auto settle = [&](int gi, int pj, double iou, double inter2) {  // what the rule makes of a clipped pair
     unsigned long long val = 0ull;
-    if (!r.template pair<FILL>(s_rule, s_rows[gi * 4 + 3], s_rows[(QM_TILE + pj) * 4 + 3], pj, iou, inter2, val)) continue;
+    if (!r.template pair<FILL>(s_rule, s_rows[gi * 4 + 3], s_rows[(QM_TILE + pj) * 4 + 3], pj, iou, inter2, val)) return;
     if (FILL) {
       const long slot = (long)t.rowoff[(long)b * (t.Mp + 1) + g0 + gi] + t.tpre[word_at + gi] +
                         __popcll(s_word[gi] & ((1ull << pj) - 1ull));
       if (slot >= 0 && slot < t.max_pairs) r.store((long)b * t.max_pairs + slot, p0 + pj, val);
     } else {
       atomicOr(&s_word[gi], 1ull << pj);
+    }
+  };
+  constexpr int PL = Rule::PAIR_LANES;
+  static_assert(PL >= 1 && PL <= 64 && (PL & (PL - 1)) == 0, "a group of lanes lies inside one wave");
+  for (int e = tid / PL; e < total; e += QM_THREADS / PL) {
+    const int q = e < c0 ? s_list[e] : s_list[QM_LIST + e - c0];
+    const int gi = q >> 6, pj = q & 63;
+    if constexpr (PL > 1) {  // e is uniform over the group: all its lanes are in the call, one settles
+      const double inter2 = r.group_inter2(s_rows + gi * 4, s_rows + (QM_TILE + pj) * 4, b, s_ring + tid, tid % PL);
+      if (tid % PL == 0) settle(gi, pj, 0.0, inter2);
+    } else {
+      double inter2;
+      const double iou = qm_inter2_iou(s_rows + gi * 4, s_rows + (QM_TILE + pj) * 4, s_ring + tid, &inter2);
+      settle(gi, pj, iou, inter2);
     }
   }
   if (!FILL) {

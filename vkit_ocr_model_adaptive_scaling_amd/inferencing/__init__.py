@@ -35,3 +35,6 @@ from .spines import (SpineLayout, SpineStrips, check_spine_rows, knot_status, sp
 from .line_strips import quad_strips, result_lines, spine_strips, spine_strips_for_results, strips_for_results
 from .line_evaluation import (LineMatchResult, LineScore, check_line_thresholds, evaluate_lines, evaluate_lines_host,
                               line_pairs, match_lines_host, match_lines_rounds_host)
+from .ribbon_evaluation import (evaluate_ribbons, evaluate_ribbons_host, match_ribbons_host, match_ribbons_rounds_host,
+                                polygon_ribbon, quad_ribbon, result_ribbons, ribbon_inter, ribbon_list, ribbon_pairs,
+                                ribbon_rows, ribbon_tables, spine_ribbon)

@@ -2647,6 +2647,41 @@ def match_lines(gt_rows: torch.Tensor, gt_count: torch.Tensor, gt_care: Optional
     return gt_kind, gt_group, pred_kind, pred_group, stats
 
 
+def match_ribbons(gt_rows: torch.Tensor, gt_count: torch.Tensor, gt_care: Optional[torch.Tensor], gt_segs: torch.Tensor,
+                  pred_rows: torch.Tensor, pred_count: torch.Tensor, pred_segs: torch.Tensor, recall_thr: float = 0.8,
+                  precision_thr: float = 0.4, cover_thr: float = 0.5, max_pairs: Optional[int] = None,
+                  rounds: Optional[torch.Tensor] = None):
+    """Curved text lines scored as ribbons of quads on the device (csrc/ribbonmatch.hip; the rule and the host oracles:
+    inferencing/ribbon_evaluation.py).  ``gt_rows`` (B, M, 16) / ``gt_count`` (B,) and ``pred_rows`` (B, N, 16) / ``pred_count``
+    (B,): int32 ribbon rows and counts; ``gt_segs`` (B, Sg, 16) and ``pred_segs`` (B, Sp, 16): the int32 segment tables the
+    ribbon rows index (``inferencing.ribbon_tables``), Sg and Sp in 1..2^21; ``gt_care`` (B, M) uint8 with 0 = don't care, or
+    None; all on the device.  Thresholds, ``max_pairs``, ``rounds`` and the five results are those of ``match_lines``.  Four
+    launches; allocates only its outputs and workspace and never synchronises, so it can be captured into a HIP graph."""
+    what = 'match_ribbons'
+    from .inferencing.line_evaluation import check_line_thresholds  # the rule's own check, stated once
+    tr_q8, tp_q8, cover_thr = check_line_thresholds(recall_thr, precision_thr, cover_thr)
+    (gt_rows, gt_count, pred_rows, pred_count, gt_care, _), B, M, N, max_pairs = _quad_tables(
+        what, gt_rows, gt_count, pred_rows, pred_count, max_pairs, rounds, (2,), gt_care)
+    for name, segs in (('gt_segs', gt_segs), ('pred_segs', pred_segs)):
+        if segs.dim() != 3 or segs.shape[0] != B or segs.shape[2] != 16 or segs.dtype != torch.int32:
+            raise ValueError(f'{what}: {name} must be a ({B}, S, 16) int32 tensor, got {tuple(segs.shape)} {segs.dtype}')
+        if not 1 <= segs.shape[1] <= 1 << 21:
+            raise ValueError(f'{what}: {name} holds {segs.shape[1]} rows per image, outside 1..2^21')
+    gt_segs, pred_segs = _one_device(what, gt_segs, pred_segs, also=gt_rows)
+    dev = gt_rows.device
+    new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+    gt_kind, gt_group = new((B, M), torch.uint8), new((B, M), torch.int32)
+    pred_kind, pred_group = new((B, N), torch.uint8), new((B, N), torch.int32)
+    stats = new((B, 16), torch.int64)
+    if B:
+        ws = _workspace(what, lib.vkas_ribbon_match_workspace_bytes(B, M, N, max_pairs), dev)
+        check(lib.vkas_ribbon_match(_p(gt_rows), _p(gt_count), _p(gt_care), _p(gt_segs), int(gt_segs.shape[1]), _p(pred_rows),
+                                    _p(pred_count), _p(pred_segs), int(pred_segs.shape[1]), B, M, N, tr_q8, tp_q8, cover_thr,
+                                    max_pairs, _p(ws), ws.numel(), _p(gt_kind), _p(gt_group), _p(pred_kind), _p(pred_group),
+                                    _p(stats), _p(rounds), _stream()), what)
+    return gt_kind, gt_group, pred_kind, pred_group, stats
+
+
 def quad_rows(quads: torch.Tensor, valid: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``inferencing.match_rows`` on the device (csrc/quadmatch.hip): ``quads`` (B, K, 4, 2) float64 ``(y, x)`` corners and an
     optional ``valid`` (B, K) uint8 on the device -> (B, K, 16) int32 match rows, equal to the host's on every input (an
