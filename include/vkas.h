@@ -828,6 +828,22 @@ int vkas_warp_region_labels(const int* labels, int Hl, int Wl, int valid_h, int 
  * out is 16-byte aligned, plain stores otherwise. */
 int vkas_crop_warp_f32(const unsigned char* arena, long long arena_bytes, const long long* sources, int S,
                        const long long* rows, int B, float* out, int H, int W, void* stream);
+/* The same crops, blurred between the geometric value and the jitter (dataset/blur.py holds the rule and the host oracle
+ * crop_blur_host).  blur_rows (B,226) int32, one per output image: the radius R in 0..7, then a 15 x 15 weight table, row-major,
+ * centred at (7,7); valid when every weight is in 0..65536, every weight outside the central (2R+1)^2 square is 0 and the sum
+ * is 65536.  With v(i, j) the geometric value of vkas_crop_warp_f32 at crop cell (i, j) - the row's map continues outside the
+ * H x W crop, zero outside the page - acc = sum over a, b in -R..R of w[7+a][7+b] * v(y+a, x+b) (below 2^24), and the steps of
+ * vkas_crop_warp_f32 run on fp32(acc) * 2^-16 (exact) instead of v; R = 0 gives its output bit for bit.  An image whose crop row
+ * cannot be trusted (as there) or whose blur row is invalid or has R > radius_max is written as zeros.  Two launches (none for
+ * B = 0): the geometric values of the cells -radius_max .. H+radius_max-1 x -radius_max .. W+radius_max-1, each computed once,
+ * as uint8 planes (B, 3, H + 2*radius_max, pitch), pitch = W + 2*radius_max rounded up to 16, in `work` (work_bytes at least
+ * that size, else VKAS_E_ARG before any launch); then the weighted sums from 16 x 64 tiles staged through LDS.  Every out
+ * element is written exactly once; capture-safe: no allocation, no synchronisation, no atomics; bit-identical from run to
+ * run.  B in 0..65535, H, W in 1..8192, radius_max in 0..7; tables 8-byte aligned, blur_rows 4-byte, work 16-byte; the stores
+ * of vkas_crop_warp_f32. */
+int vkas_crop_warp_blur_f32(const unsigned char* arena, long long arena_bytes, const long long* sources, int S,
+                            const long long* rows, const int* blur_rows, int B, int radius_max, unsigned char* work,
+                            long long work_bytes, float* out, int H, int W, void* stream);
 /* Text lines cut into upright strips of one height h (inferencing/strips.py holds the rule from a quadrilateral to a row and
  * the host oracle quad_strips_host).  The images lie in one byte arena with the (S,4) int64 source table of
  * vkas_resample_pack_u8_multi.  The table `rows` holds 13*n + 1 int64 words: n strip rows of 12 words (src, offset, slot_w,

@@ -227,6 +227,7 @@ _SIGS = {
     'vkas_warp_region_labels': (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, c_int, _P, c_int, c_int,
                                         _P]),
     'vkas_crop_warp_f32': (c_int, [_P, c_longlong, _P, c_int, _P, c_int, _P, c_int, c_int, _P]),
+    'vkas_crop_warp_blur_f32': (c_int, [_P, c_longlong, _P, c_int, _P, _P, c_int, c_int, _P, c_longlong, _P, c_int, c_int, _P]),
     'vkas_quad_strips_u8': (c_int, [_P, c_longlong, _P, c_int, _P, c_int, c_int, _P, c_longlong, _P]),
     'vkas_spine_strips_workspace_bytes': (c_longlong, [c_longlong]),
     'vkas_spine_columns': (c_int, [_P, c_int, c_longlong, c_int, _P, c_longlong, _P]),

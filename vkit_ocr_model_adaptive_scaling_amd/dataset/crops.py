@@ -5,8 +5,8 @@ The reference cuts its samples out of synthetic pages with vkit's ``page_croppin
 have been rescaled to about 35 px.  vkit and cv2 are absent here, so the step is restated as ONE affine map per sample - a
 similarity: scale, a small rotation, a translation - sampled by the integer rule of inferencing/packing.py::warp_host, then a
 photometric jitter in float32 without contraction, so that the device kernel (csrc/crops.hip, ``ops.crop_warp``) and
-``crop_host`` are held to each other bit for bit.  No perspective, blur, JPEG or page synthesis; outside the page a crop is
-zero padded, and bias and noise still apply there.
+``crop_host`` are held to each other bit for bit.  No perspective, JPEG or page synthesis (blur: dataset/blur.py); outside the
+page a crop is zero padded, and bias and noise still apply there.
 
 A **crop row** is 16 int64:
     0       source: the index of the page in the batch's source list
@@ -67,6 +67,7 @@ class CropConfig:
     bias: float = 20.0                      # +-, one draw for the three channels
     noise_amp: Tuple[float, float] = (0.0, 8.0)
     photometric: bool = True
+    blur: Optional[Any] = None              # a dataset/blur.py::BlurConfig; None: every crop is as sharp as its page
 
     def check(self) -> 'CropConfig':
         H, W = (int(v) for v in self.size)
@@ -80,6 +81,8 @@ class CropConfig:
             raise ValueError('CropConfig: rotate_max_deg in [0, 45], precise_char_height and rough_short_side positive')
         if self.core_margin < 0 or 2 * self.core_margin + 2 >= min(H, W):
             raise ValueError(f'CropConfig: core_margin {self.core_margin} leaves no core box in {(H, W)}')
+        if self.blur is not None:
+            self.blur.check()
         return self
 
 

@@ -6,10 +6,11 @@ from typing import Any, Dict, Iterable, Tuple
 import numpy as np
 import torch
 
+from .blur import blur_row, crop_blur_host
 from .crops import AnnotatedPage, CropConfig, crop_host, crop_quads, crop_row, _page_mat
 from .labels import collate_quad_pass
 
-_CROP_KEYS = ('crop_rows', 'crop_sources', 'crop_size')
+_CROP_KEYS = ('crop_rows', 'crop_sources', 'crop_size', 'crop_blur')
 
 
 def adaptive_scaling_pages_collate_fn(batch: Iterable[Tuple[AnnotatedPage, AnnotatedPage]], config: CropConfig, P: int,
@@ -18,7 +19,8 @@ def adaptive_scaling_pages_collate_fn(batch: Iterable[Tuple[AnnotatedPage, Annot
     """``(rough page, precise page)`` pairs (the same page twice is fine) -> the batch of
     ``adaptive_scaling_quads_collate_fn`` with ``image`` replaced by ``crop_rows`` (B, 16) int64 - row b reads source b - and
     ``crop_sources``, the list of the B uint8 page arrays (not copied), and ``crop_size``, the crops' (H, W), which the
-    warper needs and no other key holds.  The quads are carried into the crops
+    warper needs and no other key holds.  Only when ``config.blur`` is set with ``prob > 0`` a pass also holds ``crop_blur``
+    (B, 226) int32, the blur rows of its crops (dataset/blur.py).  The quads are carried into the crops
     (``crop_quads``) and go through the same ``quad_rows`` / ``label_points`` as there.  ``draw`` numbers the pass over the
     data: another draw, another crop of the same page.  ``config.core_margin`` must cover ``f * margin``, so that the anchor
     of a precise crop lies in the core box.  Host only."""
@@ -36,15 +38,19 @@ def adaptive_scaling_pages_collate_fn(batch: Iterable[Tuple[AnnotatedPage, Annot
         quads = [crop_quads(np.asarray(p.quads, dtype=np.float64).reshape(-1, 4, 2), r) for p, r in zip(pages, rows)]
         states = [{'seed': rng_seed, 'index': p.index, 'draw': draw} for p in pages]
         rest = collate_quad_pass(quads, [p.index for p in pages], states, size, kind == 'precise', P, f, margin, rng_seed)
-        return {'crop_rows': torch.from_numpy(rows), 'crop_sources': mats, 'crop_size': size, **rest}
+        out = {'crop_rows': torch.from_numpy(rows), 'crop_sources': mats, 'crop_size': size}
+        if config.blur is not None and config.blur.prob > 0:
+            out['crop_blur'] = torch.from_numpy(np.stack([blur_row(kind, p, config, rng_seed, draw) for p in pages]))
+        return {**out, **rest}
 
     return {'rough': one_pass([r for r, _ in pairs], 'rough'), 'precise': one_pass([p for _, p in pairs], 'precise')}
 
 
 class PageCropWarper:
     """Called in the main process on a batch of ``adaptive_scaling_pages_collate_fn``: the pages of both passes go into one
-    byte arena and one upload, one ``ops.crop_warp`` per pass writes its (B, 3, H, W) float32 ``image`` on the device, and
-    the batch comes back with ``image`` and without the crop keys - what ``CharLabelRasterizer`` takes."""
+    byte arena and one upload, one ``ops.crop_warp`` per pass - ``ops.crop_warp_blur`` for a pass that holds ``crop_blur`` -
+    writes its (B, 3, H, W) float32 ``image`` on the device, and the batch comes back with ``image`` and without the crop
+    keys - what ``CharLabelRasterizer`` takes."""
 
     def __init__(self, device):
         self.device = torch.device(device)
@@ -67,17 +73,25 @@ class PageCropWarper:
             part = batch[name]
             rows = part['crop_rows'].numpy().copy()
             rows[:, 0] = remap[name][rows[:, 0]]
-            image = ops.crop_warp(arena, table, rows, part['crop_size'])  # host tables: checked here, no copy back
+            if 'crop_blur' in part:  # host tables: checked here, no copy back
+                image = ops.crop_warp_blur(arena, table, rows, part['crop_blur'].numpy(), part['crop_size'])
+            else:
+                image = ops.crop_warp(arena, table, rows, part['crop_size'])
             out[name] = {'image': image, **{k: v for k, v in part.items() if k not in _CROP_KEYS}}
         return out
 
 
 def crops_host(batch: Dict[str, Dict[str, Any]]) -> Dict[str, Dict[str, Any]]:
-    """What ``PageCropWarper`` returns, through ``crop_host`` and with host tensors: the slow route, for checks and for
-    timing against."""
+    """What ``PageCropWarper`` returns, through ``crop_host`` (``crop_blur_host`` for a pass that holds ``crop_blur``) and with
+    host tensors: the slow route, for checks and for timing against."""
     out = {}
     for name in ('rough', 'precise'):
         part = batch[name]
-        image = torch.from_numpy(crop_host(part['crop_sources'], part['crop_rows'].numpy(), part['crop_size']))
+        rows = part['crop_rows'].numpy()
+        if 'crop_blur' in part:
+            image = crop_blur_host(part['crop_sources'], rows, part['crop_blur'].numpy(), part['crop_size'])
+        else:
+            image = crop_host(part['crop_sources'], rows, part['crop_size'])
+        image = torch.from_numpy(image)
         out[name] = {'image': image, **{k: v for k, v in part.items() if k not in _CROP_KEYS}}
     return out

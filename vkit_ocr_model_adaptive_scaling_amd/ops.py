@@ -3315,6 +3315,44 @@ def spine_strips_u8(arena: torch.Tensor, sources, table, n: int, knots_total: in
     return out
 
 
+def _crop_warp_args(who: str, arena: torch.Tensor, sources, rows, size, validate: bool, out):
+    """What the crop ops take alike, checked before anything is launched -> ``(device sources, device rows, host rows or None,
+    S, B, H, W)``."""
+    import numpy as np
+    from .dataset.crops import check_crop_rows
+    if arena.dim() != 1 or arena.dtype != torch.uint8:
+        raise ValueError(f'{who}: arena must be a 1-D uint8 tensor, got {arena.dtype} {tuple(arena.shape)}')
+    if arena.numel() < 1 or not arena.is_contiguous():
+        raise ValueError(f'{who}: arena must be contiguous and not empty')
+    try:
+        H, W = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f'{who}: size must be (height, width), got {size!r}') from None
+    if not (1 <= H <= _CROP_SIDE_MAX and 1 <= W <= _CROP_SIDE_MAX):
+        raise ValueError(f'{who}: size sides must be in [1, {_CROP_SIDE_MAX}], got {(H, W)}')
+    d_sources, h_sources = _pack_table(who, 'sources', sources, (None, 4), 'int64', arena.device, validate)
+    d_rows, h_rows = _pack_table(who, 'rows', rows, (None, 16), 'int64', arena.device, validate)
+    S, B = int(d_sources.shape[0]), int(d_rows.shape[0])
+    if S < 1:
+        raise ValueError(f'{who}: no sources')
+    if B > 65535:
+        raise ValueError(f'{who}: B = {B} above 65535')
+    if h_sources is not None:
+        t = h_sources
+        if ((t[:, 1:3] < 1) | (t[:, 1:3] > _CROP_SIDE_MAX)).any():
+            raise ValueError(f'{who}: source sides must be in [1, {_CROP_SIDE_MAX}]')
+        if ((t[:, 0] < 0) | (t[:, 0] + 3 * t[:, 1] * t[:, 2] > int(arena.numel()))).any():
+            raise ValueError(f'{who}: a source leaves the arena of {int(arena.numel())} bytes')
+        if h_rows is not None:
+            check_crop_rows(h_rows, t[:, 1:3])
+    elif h_rows is not None:
+        raise ValueError(f'{who}: host rows need a host source table (or validate=True) to be checked against')
+    if out is not None and (tuple(out.shape) != (B, 3, H, W) or out.dtype != torch.float32 or not out.is_contiguous() or
+                            out.device != arena.device):
+        raise ValueError(f'{who}: out must be a contiguous {(B, 3, H, W)} float32 tensor on {arena.device}')
+    return d_sources, d_rows, h_rows, S, B, H, W
+
+
 def crop_warp(arena: torch.Tensor, sources, rows, size: Tuple[int, int], validate: bool = True,
               out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Training crops of annotated pages: one affine map and one photometric jitter per output image, in one launch
@@ -3325,41 +3363,61 @@ def crop_warp(arena: torch.Tensor, sources, rows, size: Tuple[int, int], validat
     bit: every element is written.  An unchecked row that cannot be trusted gives a zero image (see include/vkas.h).
     Allocates only its output; with device tables and ``validate=False`` it never synchronises, so it can be captured into a
     HIP graph."""
-    import numpy as np
-    from .dataset.crops import check_crop_rows
-    if arena.dim() != 1 or arena.dtype != torch.uint8:
-        raise ValueError(f'crop_warp: arena must be a 1-D uint8 tensor, got {arena.dtype} {tuple(arena.shape)}')
-    if arena.numel() < 1 or not arena.is_contiguous():
-        raise ValueError('crop_warp: arena must be contiguous and not empty')
-    try:
-        H, W = (int(v) for v in size)
-    except (TypeError, ValueError):
-        raise ValueError(f'crop_warp: size must be (height, width), got {size!r}') from None
-    if not (1 <= H <= _CROP_SIDE_MAX and 1 <= W <= _CROP_SIDE_MAX):
-        raise ValueError(f'crop_warp: size sides must be in [1, {_CROP_SIDE_MAX}], got {(H, W)}')
-    d_sources, h_sources = _pack_table('crop_warp', 'sources', sources, (None, 4), 'int64', arena.device, validate)
-    d_rows, h_rows = _pack_table('crop_warp', 'rows', rows, (None, 16), 'int64', arena.device, validate)
-    S, B = int(d_sources.shape[0]), int(d_rows.shape[0])
-    if S < 1:
-        raise ValueError('crop_warp: no sources')
-    if B > 65535:
-        raise ValueError(f'crop_warp: B = {B} above 65535')
-    if h_sources is not None:
-        t = h_sources
-        if ((t[:, 1:3] < 1) | (t[:, 1:3] > _CROP_SIDE_MAX)).any():
-            raise ValueError(f'crop_warp: source sides must be in [1, {_CROP_SIDE_MAX}]')
-        if ((t[:, 0] < 0) | (t[:, 0] + 3 * t[:, 1] * t[:, 2] > int(arena.numel()))).any():
-            raise ValueError(f'crop_warp: a source leaves the arena of {int(arena.numel())} bytes')
-        if h_rows is not None:
-            check_crop_rows(h_rows, t[:, 1:3])
-    elif h_rows is not None:
-        raise ValueError('crop_warp: host rows need a host source table (or validate=True) to be checked against')
-    if out is not None and (tuple(out.shape) != (B, 3, H, W) or out.dtype != torch.float32 or not out.is_contiguous() or
-                            out.device != arena.device):
-        raise ValueError(f'crop_warp: out must be a contiguous {(B, 3, H, W)} float32 tensor on {arena.device}')
+    d_sources, d_rows, _, S, B, H, W = _crop_warp_args('crop_warp', arena, sources, rows, size, validate, out)
     _require_cuda(arena, out)
     crops = out if out is not None else torch.empty((B, 3, H, W), dtype=torch.float32, device=arena.device)
     if B:
         check(lib.vkas_crop_warp_f32(_p(arena), int(arena.numel()), _p(d_sources), S, _p(d_rows), B, _p(crops), H, W,
                                      _stream()), 'crop_warp')
+    return crops
+
+
+_BLUR_RADIUS_MAX = 7
+
+
+def crop_blur_work_bytes(B: int, size: Tuple[int, int], radius_max: int = _BLUR_RADIUS_MAX) -> int:
+    """The bytes of ``crop_warp_blur``'s ``work``: uint8 planes (B, 3, H + 2*radius_max, pitch), the pitch a multiple of 16."""
+    H, W = (int(v) for v in size)
+    return int(B) * 3 * (H + 2 * radius_max) * (-(-(W + 2 * radius_max) // 16) * 16)
+
+
+def crop_warp_blur(arena: torch.Tensor, sources, rows, blur_rows, size: Tuple[int, int], validate: bool = True,
+                   out: Optional[torch.Tensor] = None, work: Optional[torch.Tensor] = None,
+                   radius_max: Optional[int] = None) -> torch.Tensor:
+    """``crop_warp`` with one blur table per output image between the geometric value and the jitter, in two launches
+    (csrc/crops.hip; the rule and the oracle: dataset/blur.py::crop_blur_host).  ``arena``, ``sources``, ``rows``, ``size`` and
+    ``out`` as in ``crop_warp``; ``blur_rows`` (B,226) int32, host or device, checked like the rows (``check_blur_rows``).
+    ``radius_max`` in [0, 7] bounds the radii and sizes the halo of the intermediate: by default the table's maximum for a
+    table that is on the host and 7 otherwise; an unchecked row above it gives a zero image, as an invalid one does.
+    ``work``: a 1-D uint8 device tensor of at least ``crop_blur_work_bytes(B, size, radius_max)`` bytes, 16-byte aligned,
+    allocated when not given.  Returns the (B,3,H,W) float32 crops, equal to ``crop_blur_host`` bit for bit.  With host tables
+    whose radii are all 0 it is ``crop_warp`` and nothing else.  With device tables, ``validate=False`` and ``work`` and
+    ``out`` given it neither allocates nor synchronises, so it can be captured into a HIP graph."""
+    from .dataset.blur import check_blur_rows
+    d_sources, d_rows, _, S, B, H, W = _crop_warp_args('crop_warp_blur', arena, sources, rows, size, validate, out)
+    on_host = not (isinstance(blur_rows, torch.Tensor) and blur_rows.is_cuda)
+    d_blur, h_blur = _pack_table('crop_warp_blur', 'blur_rows', blur_rows, (B, 226), 'int32', arena.device, validate,
+                                 check_blur_rows)
+    table_max = int(h_blur[:, 0].max()) if h_blur is not None and B else 0
+    if radius_max is None:
+        radius_max = table_max if on_host else _BLUR_RADIUS_MAX
+    if radius_max != int(radius_max) or not 0 <= int(radius_max) <= _BLUR_RADIUS_MAX:
+        raise ValueError(f'crop_warp_blur: radius_max must be an integer in [0, {_BLUR_RADIUS_MAX}], got {radius_max}')
+    radius_max = int(radius_max)
+    if h_blur is not None and table_max > radius_max:
+        raise ValueError(f'crop_warp_blur: a blur row has radius {table_max}, above radius_max = {radius_max}')
+    need = crop_blur_work_bytes(B, (H, W), radius_max)
+    if work is not None and (work.dim() != 1 or work.dtype != torch.uint8 or not work.is_contiguous() or
+                             work.device != arena.device or int(work.numel()) < need or work.data_ptr() % 16):
+        raise ValueError(f'crop_warp_blur: work must be a contiguous 16-byte aligned 1-D uint8 tensor of at least {need} bytes '
+                         f'on {arena.device}')
+    if on_host and table_max == 0:
+        return crop_warp(arena, d_sources, d_rows, (H, W), validate=False, out=out)  # the tables are checked and uploaded
+    _require_cuda(arena, out)
+    crops = out if out is not None else torch.empty((B, 3, H, W), dtype=torch.float32, device=arena.device)
+    if B:
+        if work is None:
+            work = torch.empty((need,), dtype=torch.uint8, device=arena.device)
+        check(lib.vkas_crop_warp_blur_f32(_p(arena), int(arena.numel()), _p(d_sources), S, _p(d_rows), _p(d_blur), B, radius_max,
+                                          _p(work), int(work.numel()), _p(crops), H, W, _stream()), 'crop_warp_blur')
     return crops
